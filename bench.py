@@ -3,6 +3,7 @@
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus 8 --steps 20 --warmup 3            # spawns its own 8 ranks (one per GPU)
     python bench.py --gpus 8 --single-process                 # ONE process, a kpdi_group over the 8 GPUs
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs out/   # + the last timed step's result as .npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3   # or under a launcher
 
@@ -568,6 +569,14 @@ def spawn_ranks(n_ranks, argv, script=None):
     return subprocess.run([sys.executable, script] + list(argv) + ["--single-process"], env=env).returncode
 
 
+def dump_outputs(out_dir, scores, indices):
+    """The (scores, indices) of the last timed step as .npy files, so that two builds can be compared output for output.
+    Whole arrays: (m, keep_n) is at most 40 000 x 20 here, well under 64 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scores.npy"), np.asarray(scores, dtype=np.float64 if scores.dtype == np.float64 else np.float32))
+    np.save(os.path.join(out_dir, "indices.npy"), np.asarray(indices, dtype=np.float64))
+
+
 _JSON_FD = None  # the real stdout, kept aside for the ONE JSON line (set once per process)
 
 
@@ -644,7 +653,12 @@ def _main(argv, context_factory=None, group_factory=None):
     ap.add_argument("--compute", default="f32", choices=["f32", "f16x2", "f16"],
                     help="arithmetic of the match kernel; f16x2 / f16 are the opt-in float16 modes (never the default; "
                          "f16 is reduced precision)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the result of the last timed step - what a caller of the timed path receives - to "
+                         "DIR/scores.npy (float32) and DIR/indices.npy (float64, exact for these indices); rank 0 only")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     single = a.single_process and a.gpus > 1 and "WORLD_SIZE" not in os.environ
     if "WORLD_SIZE" not in os.environ and a.gpus > 1 and not single:
@@ -823,6 +837,8 @@ def _main(argv, context_factory=None, group_factory=None):
     if rank != 0:
         ctx.close()
         return 0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, scores, indices)
 
     solo = world == 1 and not single  # one process, one GPU: the informational legs below belong to this form
     n_gpus = n_dev if single else world

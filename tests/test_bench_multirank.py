@@ -140,3 +140,30 @@ def test_rank_share_leg_of_the_default_run(monkeypatch, resident_prefix):
     rec = bench.rank_share_leg(_lib, make, 0, "toy", 8, d_dic, dic, 2, 12, shard_range, per=50)
     assert rec["shard_patterns"] == 125 and rec["check"]["rows"] == 12 and rec["check"]["index_agreement"] == 1.0
     assert rec["check"]["max_abs_score_diff"] < 1e-5 and rec["ms_per_step"] > 0
+
+
+def test_bench_dumps_the_last_timed_result(tmp_path):
+    """`--dump-outputs DIR`: rank 0 writes the merged (scores, indices) of the last timed step; the inputs are seeded, so
+    two runs - here with a different number of timed steps - write the same arrays, and `--steps` is the number of
+    match launches in the timed region."""
+    import numpy as np
+
+    dumps = []
+    for steps in (2, 3):
+        d = tmp_path / f"steps{steps}"
+        out = run([sys.executable, WORKER, "--gpus", "2", "--steps", str(steps), "--warmup", "1", "--check-rows", "8",
+                   "--no-cpu-baseline", "--dump-outputs", str(d)])
+        assert out["steps"] == steps and out["roofline"]["launches"] == steps
+        assert sorted(os.listdir(d)) == ["indices.npy", "scores.npy"]
+        scores, indices = np.load(d / "scores.npy"), np.load(d / "indices.npy")
+        assert scores.dtype == np.float32 and indices.dtype == np.float64
+        assert scores.shape == indices.shape == (out["config"]["experimental_patterns"], out["config"]["keep_n"])
+        assert (indices >= 0).all() and (indices < out["config"]["dictionary_patterns"]).all()
+        assert np.array_equal(indices, np.round(indices)) and (np.diff(scores, axis=1) <= 0).all()
+        dumps.append((scores, indices))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
+def test_bench_refuses_zero_steps():
+    p = subprocess.run([sys.executable, WORKER, "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--steps must be at least 1" in p.stderr
