@@ -180,6 +180,14 @@ int kpdi_remove_dynamic_background(kpdi_ctx *ctx, int operation, int filter_doma
  * dtype given to kpdi_set_experimental */
 int kpdi_get_experimental(kpdi_ctx *ctx, void *patterns_out);
 
+/* ---- image quality (EBSD.get_image_quality, signals/ebsd.py:1312-1375; pattern/_pattern.py:698-775) ------------
+ * Krieger Lassen's Q of every resident pattern, AFTER the recorded background steps (they run first, as in
+ * kpdi_get_experimental); the navigation mask is ignored.  `weights`: sy*sx float64 frequency vectors, NULL = the
+ * reference's fft_frequency_vectors((sy, sx)); `inertia_max` <= 0: sum(weights) / (sy*sx).  `iq_out`: m_all floats,
+ * NaN for a pattern with a non-finite value, a constant pattern with `normalize`, or an all-zero one.  uint8 / int8 /
+ * uint16 / int16 / float32 / float64 patterns; kernels and paths: csrc/iq.hip, csrc/iq_plan.h. */
+int kpdi_image_quality(kpdi_ctx *ctx, int normalize, const double *weights, double inertia_max, float *iq_out);
+
 /* ---- dictionary sweep (_dictionary_indexing loop, indexing/_dictionary_indexing.py:94-128)
  * One call = one loop iteration: prepare_dictionary (cast, mask, normalise) +
  * match + top-k of the chunk + merge into the running best-k, all on the GPU.

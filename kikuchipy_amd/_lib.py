@@ -131,6 +131,7 @@ SIGNATURES = {
     "kpdi_remove_static_background": (_i, [_vp, _vp, _i, _i]),
     "kpdi_remove_dynamic_background": (_i, [_vp, _i, _i, C.c_double, C.c_double]),
     "kpdi_get_experimental": (_i, [_vp, _vp]),
+    "kpdi_image_quality": (_i, [_vp, _i, _vp, C.c_double, _vp]),
     "kpdi_push_dictionary_chunk": (_i, [_vp, _vp, _i, _i64, _i64]),
     "kpdi_push_dictionary_chunk_dev": (_i, [_vp, _vp, _i, _i64, _i64]),
     "kpdi_set_master_pattern": (_i, [_vp, _vp, _vp, _i, _i, _i]),
@@ -438,6 +439,16 @@ class Context:
     def get_experimental(self):
         out = np.empty(self._exp_shape, dtype=self._exp_dtype)
         check(self._f.get_experimental(self._h, _ptr(out)))
+        return out
+
+    def image_quality(self, normalize=True, frequency_vectors=None, inertia_max=0.0):
+        """Q of every resident pattern (after the recorded background steps): float32 (m_all,).  `frequency_vectors`:
+        (sy, sx) weights or None (the reference's default); `inertia_max` <= 0: derived from the weights."""
+        w = None if frequency_vectors is None else np.ascontiguousarray(frequency_vectors, dtype=np.float64)
+        if w is not None and w.shape != self._detector:
+            raise KpdiError(f"frequency vectors of shape {w.shape}, patterns of shape {self._detector}")
+        out = np.empty(self._exp_shape[0], dtype=np.float32)
+        check(self._f.image_quality(self._h, int(bool(normalize)), _ptr(w), float(inertia_max), _ptr(out)))
         return out
 
     # -- sweep

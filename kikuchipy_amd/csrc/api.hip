@@ -172,7 +172,7 @@ int results_to_host(kpdi_ctx *c, void *dst, const void *d_src, size_t bytes) {
 
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.2.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.3.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 
@@ -234,7 +234,7 @@ int kpdi_destroy(kpdi_ctx *c) {
                     &c->bound_s, &c->bound_i, &c->gthr, &c->tile_ctr, &c->gather_s, &c->gather_i, &c->bg, &c->taps, &c->inv_map, &c->pre_scratch,
                     &c->mp_packed, &c->dcos, &c->rot, &c->proj_out,
                     &c->ref_raw, &c->ref_map, &c->ref_rowcol, &c->ref_pat, &c->ref_sqn, &c->ref_in, &c->ref_out,
-                    &c->ref_idx, &c->osm_idx, &c->osm_out, &c->stage[0], &c->stage[1], &c->pending.raw, &c->pending.raw_b, &c->pending_hold.raw})
+                    &c->ref_idx, &c->osm_idx, &c->osm_out, &c->iq_tab, &c->iq_ws, &c->iq_out, &c->stage[0], &c->stage[1], &c->pending.raw, &c->pending.raw_b, &c->pending_hold.raw})
     b->release();
   for (auto *l : {&c->ev_match, &c->ev_prep, &c->ev_merge, &c->ev_proj, &c->ev_pre, &c->ev_rescore})
     for (auto &pr : *l) {
@@ -494,6 +494,72 @@ int kpdi_get_experimental(kpdi_ctx *c, void *out) {
   HIPCHK(hipMemcpyAsync(out, c->exp_raw.p, bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return KPDI_OK;
+}
+
+int kpdi_image_quality(kpdi_ctx *c, int normalize, const double *weights, double inertia_max, float *iq_out) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
+  if (!iq_out) return fail(KPDI_EINVAL, "iq_out is NULL");
+  if (c->exp_dtype == KPDI_F16 || c->exp_dtype == KPDI_I32 || c->exp_dtype == KPDI_U32)
+    return fail(KPDI_EINVAL, "image quality takes uint8/int8/uint16/int16/float32/float64 patterns");
+  const int sy = c->sy, sx = c->sx, h = kpdi::iq_half_cols(sx);
+  const kpdi::IqPlan plan = kpdi::iq_plan(sy, sx, c->m_all);
+  if (plan.path < 0) return fail(KPDI_EINVAL, "image quality of %d x %d patterns: no kernel path takes this shape", sy, sx);
+  int rc = use_device(c);
+  if (rc) return rc;
+  bool dummy = false;
+  rc = flush_preprocess(c, false, &dummy);  // recorded background-removal steps run first
+  if (rc) return rc;
+  // weights w (pattern/_pattern.py:365-386 unless given), inertia_max = sum w / (sy sx) unless given
+  std::vector<double> w((size_t)sy * sx);
+  if (weights) {
+    std::copy(weights, weights + w.size(), w.begin());
+  } else {
+    auto line = [](int n, int i) { return (long)(i < n / 2 ? i + 1 : i - n); };  // arange(n) + 1, [n//2:] -= n + 1
+    for (int k = 0; k < sy; ++k)
+      for (int l = 0; l < sx; ++l)
+        w[(size_t)k * sx + l] = (double)(line(sy, k) * line(sy, k) + line(sx, l) * line(sx, l) - 1);
+  }
+  if (inertia_max <= 0) {
+    double sum = 0;
+    for (double v : w) sum += v;
+    inertia_max = sum / ((double)sy * sx);
+  }
+  // folded weights of the half spectrum (iq.hip) and the twiddle tables: one upload
+  const size_t wbytes = (size_t)sy * h * sizeof(double), tbytes = 2 * ((size_t)sx + sy) * sizeof(float);
+  std::vector<char> tab(wbytes + tbytes);
+  double *wf = (double *)tab.data();
+  for (int k = 0; k < sy; ++k)
+    for (int l = 0; l < h; ++l) {
+      const bool self = l == 0 || 2 * l == sx;
+      wf[(size_t)k * h + l] = w[(size_t)k * sx + l] + (self ? 0.0 : w[(size_t)((sy - k) % sy) * sx + (sx - l)]);
+    }
+  float *tw = (float *)(tab.data() + wbytes);
+  for (int n : {sx, sy})
+    for (int j = 0; j < n; ++j, tw += 2) {
+      const double a = 2.0 * M_PI * j / n;
+      tw[0] = (float)cos(a);
+      tw[1] = (float)sin(a);
+    }
+  HIPCHK(c->iq_tab.reserve(tab.size()));
+  HIPCHK(hipMemcpyAsync(c->iq_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c->iq_out.reserve((size_t)c->m_all * sizeof(float)));
+  if (plan.path == 1) HIPCHK(c->iq_ws.reserve(plan.workspace_bytes));
+  kpdi::IqLaunch a;
+  a.patterns = c->exp_raw.p;
+  a.dtype = c->exp_dtype;
+  a.n = c->m_all;
+  a.sy = sy;
+  a.sx = sx;
+  a.normalize = normalize ? 1 : 0;
+  a.wfold = (const double *)c->iq_tab.p;
+  a.twiddles = (const float *)((const char *)c->iq_tab.p + wbytes);
+  a.inertia_max = inertia_max;
+  a.workspace = c->iq_ws.p;
+  a.workspace_bytes = c->iq_ws.cap;
+  a.out = c->iq_out.as<float>();
+  HIPCHK(kpdi::launch_image_quality(a, c->stream));
+  return results_to_host(c, iq_out, c->iq_out.p, (size_t)c->m_all * sizeof(float));  // (synchronises: `tab` is read)
 }
 
 size_t kpdi_dtype_size(int dtype) { return kpdi::dtype_size(dtype); }

@@ -15,6 +15,7 @@
 #pragma once
 #include "../../include/kpdi.h"
 #include "kernels.h"
+#include "iq_plan.h"
 #include "plan.h"
 #include "group_hooks.h"
 
@@ -183,6 +184,7 @@ struct kpdi_ctx {
   int m = 0, m_pad = 0;
   bool have_nav_mask = false;
   kpdi::DevBuf exp_raw, row_map, exp_x;
+  kpdi::DevBuf iq_tab, iq_ws, iq_out;  // kpdi_image_quality: twiddles + folded weights, path-1 workspace, results
 
   // dictionary chunk
   kpdi::DevBuf dict_raw, dict_y;

@@ -333,4 +333,17 @@ hipError_t launch_nelder_mead_selftest(int kind, int nvar, const double *x0, con
 hipError_t launch_osm(const int *idx, int ny, int nx, int keep_n, int n_best, int from_n_best, const int *offsets,
                       int n_fp, int center_index, int normalize, float *out, hipStream_t s);
 
+
+// ---- image quality (iq.hip) -----------------------------------------------------
+struct IqLaunch {
+  const void *patterns; int dtype; int64_t n; int sy, sx;  // n x sy x sx of `dtype`, device
+  int normalize;
+  const float *twiddles;  // (cos, sin)(2 pi j / sx) for j < sx, then the same for sy: 2 (sx + sy) floats
+  const double *wfold;    // [sy][sx / 2 + 1] folded weights (iq.hip)
+  double inertia_max;
+  void *workspace; size_t workspace_bytes;  // path 1 of iq_plan.h
+  float *out;             // [n]
+};
+hipError_t launch_image_quality(const IqLaunch &a, hipStream_t s);
+
 }  // namespace kpdi

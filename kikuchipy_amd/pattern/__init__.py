@@ -1,4 +1,6 @@
 from kikuchipy_amd.pattern._pattern import (  # noqa: F401
+    fft_frequency_vectors,
+    get_image_quality,
     remove_dynamic_background,
     remove_static_background,
 )

@@ -1,10 +1,12 @@
-"""Static / dynamic background removal on the GPU.
+"""Static / dynamic background removal and image quality on the GPU.
 
 Array-level counterparts of `EBSD.remove_static_background`
 (signals/ebsd.py:442-573) and `EBSD.remove_dynamic_background`
 (signals/ebsd.py:575-696): same arguments, defaults, validation messages and
 output dtype; the per-pattern kernels of pattern/_pattern.py:392-509 run as
-one HIP workgroup per pattern (csrc/preproc.hip).
+one HIP workgroup per pattern (csrc/preproc.hip).  `get_image_quality`
+(pattern/_pattern.py:698-775) runs a half-spectrum DFT per pattern
+(csrc/iq.hip).
 """
 
 import numpy as np
@@ -33,11 +35,17 @@ def _upload(ctx, patterns):
     return patterns.shape
 
 
-def _process(patterns, record, context, device, contexts):
-    """Upload -> `record(ctx)` (the recorded step) -> download, on one context or - `contexts`: one per GPU, the members of a
-    `_lib.Group` - block-wise: the patterns are independent, every GPU takes a contiguous block of them over its own host
-    link from a host thread of its own (the library calls release the GIL); the blocks are concatenated."""
+def _download(ctx):
+    return ctx.get_experimental()
+
+
+def _process(patterns, record, context, device, contexts, collect=_download):
+    """Upload -> `record(ctx)` (the recorded step) -> `collect(ctx)` (one row per pattern), on one context or -
+    `contexts`: one per GPU, the members of a `_lib.Group` - block-wise: the patterns are independent, every GPU takes a
+    contiguous block of them over its own host link from a host thread of its own (the library calls release the GIL);
+    the blocks are concatenated and given the patterns' leading shape."""
     patterns = np.asarray(patterns)
+    lead = patterns.shape[:-2]
     if contexts and len(contexts) > 1 and patterns.ndim > 2 and int(np.prod(patterns.shape[:-2])) >= len(contexts):
         from concurrent.futures import ThreadPoolExecutor
 
@@ -50,16 +58,17 @@ def _process(patterns, record, context, device, contexts):
             c, (a, b) = job
             _upload(c, flat[a:b])
             record(c)
-            return c.get_experimental()
+            return collect(c)
 
         with ThreadPoolExecutor(len(contexts)) as pool:
             parts = list(pool.map(one, zip(contexts, blocks)))
-        return np.concatenate(parts, axis=0).reshape(patterns.shape)
+        return np.concatenate(parts, axis=0).reshape(lead + parts[0].shape[1:])
     ctx = contexts[0] if contexts else _context(context, device)
     try:
-        shape = _upload(ctx, patterns)
+        _upload(ctx, patterns)
         record(ctx)
-        return ctx.get_experimental().reshape(shape)
+        out = collect(ctx)
+        return out.reshape(lead + out.shape[1:])
     finally:
         if context is None and not contexts:
             ctx.close()
@@ -112,3 +121,45 @@ def remove_dynamic_background(patterns, operation="subtract", filter_domain="fre
         std = patterns.shape[-1] / 8
     return _process(patterns, lambda c: c.remove_dynamic_background(_OPS[operation], _DOMAINS[filter_domain], std, truncate),
                     context, device, contexts)
+
+
+def fft_frequency_vectors(shape):
+    """The weight of every frequency of a 2-D DFT spectrum of `shape` (pattern/_pattern.py:365-386): float64
+    `ly[k]**2 + lx[l]**2 - 1` with `lx = arange(sx) + 1`, `lx[sx // 2:] -= sx + 1` (`ly` alike).  Not symmetric under
+    (k, l) -> (-k, -l); that is the reference's convention."""
+    sy, sx = shape
+    linex = np.arange(sx) + 1
+    linex[sx // 2:] -= sx + 1
+    liney = np.arange(sy) + 1
+    liney[sy // 2:] -= sy + 1
+    return (liney[:, None] ** 2 + linex[None, :] ** 2 - 1).astype(np.float64)
+
+
+def get_image_quality(patterns, normalize=True, frequency_vectors=None, inertia_max=None, *,
+                      context=None, device=0, contexts=None):
+    """Image quality Q of Krieger Lassen (pattern/_pattern.py:698-775) of one pattern (a Python float) or of every
+    pattern of a stack (..., sy, sx) (float32 of the leading shape):
+    `Q = 1 - (sum |F| w / sum |F|) / inertia_max`, F the 2-D DFT of the pattern as float32, after subtracting its mean
+    when `normalize`.  `frequency_vectors` (sy, sx) default to `fft_frequency_vectors`, `inertia_max` to
+    `sum(frequency_vectors) / (sy * sx)`.
+
+    NaN where the reference's arithmetic gives 0/0 or meets a non-finite value: a pattern holding a NaN or inf, an
+    all-zero pattern without `normalize`, and, with `normalize`, a pattern whose values are all exactly equal.  For
+    float patterns of equal values whose float32 mean is not exact the reference divides round-off by round-off and
+    returns noise instead; here such a pattern is NaN too."""
+    patterns = np.asarray(patterns)
+    if patterns.ndim < 2:
+        raise ValueError("patterns need at least the two detector axes")
+    sig = patterns.shape[-2:]
+    w = None
+    if frequency_vectors is not None:
+        w = np.asarray(frequency_vectors, dtype=np.float64)
+        if w.shape != sig:
+            raise ValueError(f"frequency_vectors have shape {w.shape}, the patterns {sig}")
+    if inertia_max is None:
+        inertia_max = 0.0  # derived from the weights by the library
+    elif not inertia_max > 0:
+        raise ValueError(f"inertia_max must be positive, not {inertia_max}")
+    q = _process(patterns, lambda c: None, context, device, contexts,
+                 collect=lambda c: c.image_quality(normalize, w, inertia_max))
+    return float(q) if patterns.ndim == 2 else q

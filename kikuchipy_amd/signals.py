@@ -284,6 +284,16 @@ class EBSD:
             return None
         return self._like(out)
 
+    def get_image_quality(self, normalize=True, show_progressbar=None, *, devices=None):
+        """signals/ebsd.py:1312-1375: Q of every pattern (`kikuchipy_amd.pattern.get_image_quality` with the default
+        frequency vectors), float32 of the navigation shape (0-d without navigation axes).  `show_progressbar` is
+        accepted and has nothing to show."""
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        data = np.asarray(self.data)
+        q = _pattern.get_image_quality(data.reshape((-1,) + data.shape[-2:]), normalize,
+                                       context=None if contexts else self.context, contexts=contexts)
+        return q.reshape(self._navigation_shape_rc)
+
     # ------------------------------------------------------------------ refinement
     def _refine(self, mode, xmap, detector, master_pattern, energy, navigation_mask, signal_mask,
                 pseudo_symmetry_ops, method, method_kwargs, trust_region, initial_step, rtol, maxeval, compute,
