@@ -188,6 +188,20 @@ int kpdi_get_experimental(kpdi_ctx *ctx, void *patterns_out);
  * uint16 / int16 / float32 / float64 patterns; kernels and paths: csrc/iq.hip, csrc/iq_plan.h. */
 int kpdi_image_quality(kpdi_ctx *ctx, int normalize, const double *weights, double inertia_max, float *iq_out);
 
+/* ---- FFT filter (EBSD.fft_filter, signals/ebsd.py:805-930; pattern/chunk.py:75-127) ------------------------------
+ * Filters every resident pattern in place, AFTER the recorded background steps (they run first), and rescales it to
+ * the range of its dtype as the reference's rescale_intensity(dtype_out=<dtype>) does; the navigation mask is ignored
+ * and prepared rows made before the call are invalidated.
+ * KPDI_DOMAIN_FREQUENCY: `table` is the folded half spectrum of the transfer function, ty = sy rows of
+ *   tx = sx / 2 + 1 complex values stored as (re, im) float64 pairs: Hs(k, l) = (H'(k, l) + conj(H'(-k, -l))) / 2 with
+ *   H' the transfer function as applied to the unshifted spectrum (ifftshift(H) for shift=True).
+ * KPDI_DOMAIN_SPATIAL: `table` is a ty x tx float64 kernel, applied as Barnes' FFT filter does: a correlation with
+ *   edge-replicated borders centred at (ty / 2, tx / 2).
+ * A pattern holding a non-finite value, or whose filtered result is constant, becomes 0 (integer dtypes) or NaN (float
+ * dtypes).  uint8 / int8 / uint16 / int16 / float32 / float64 patterns; kernels and paths: csrc/fftfilter.hip,
+ * csrc/fftfilter_plan.h. */
+int kpdi_fft_filter(kpdi_ctx *ctx, int function_domain, const double *table, int ty, int tx);
+
 /* ---- dictionary sweep (_dictionary_indexing loop, indexing/_dictionary_indexing.py:94-128)
  * One call = one loop iteration: prepare_dictionary (cast, mask, normalise) +
  * match + top-k of the chunk + merge into the running best-k, all on the GPU.

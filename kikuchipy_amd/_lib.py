@@ -132,6 +132,7 @@ SIGNATURES = {
     "kpdi_remove_dynamic_background": (_i, [_vp, _i, _i, C.c_double, C.c_double]),
     "kpdi_get_experimental": (_i, [_vp, _vp]),
     "kpdi_image_quality": (_i, [_vp, _i, _vp, C.c_double, _vp]),
+    "kpdi_fft_filter": (_i, [_vp, _i, _vp, _i, _i]),
     "kpdi_push_dictionary_chunk": (_i, [_vp, _vp, _i, _i64, _i64]),
     "kpdi_push_dictionary_chunk_dev": (_i, [_vp, _vp, _i, _i64, _i64]),
     "kpdi_set_master_pattern": (_i, [_vp, _vp, _vp, _i, _i, _i]),
@@ -450,6 +451,19 @@ class Context:
         out = np.empty(self._exp_shape[0], dtype=np.float32)
         check(self._f.image_quality(self._h, int(bool(normalize)), _ptr(w), float(inertia_max), _ptr(out)))
         return out
+
+    def fft_filter(self, function_domain, table):
+        """Filter every resident pattern in place (after the recorded background steps) and rescale it to its dtype's
+        range.  DOMAIN_FREQUENCY: `table` is the folded half spectrum, complex (sy, sx // 2 + 1); DOMAIN_SPATIAL: a real
+        (ty, tx) correlation kernel (include/kpdi.h, kpdi_fft_filter)."""
+        if int(function_domain) == DOMAIN_FREQUENCY:
+            t = np.ascontiguousarray(table, dtype=np.complex128)
+            flat = t.view(np.float64)
+        else:
+            t = flat = np.ascontiguousarray(table, dtype=np.float64)
+        if t.ndim != 2:
+            raise KpdiError(f"filter table of shape {t.shape}")
+        check(self._f.fft_filter(self._h, int(function_domain), _ptr(flat), int(t.shape[0]), int(t.shape[1])))
 
     # -- sweep
     def set_dictionary_size(self, n_total):

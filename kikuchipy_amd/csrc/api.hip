@@ -172,7 +172,7 @@ int results_to_host(kpdi_ctx *c, void *dst, const void *d_src, size_t bytes) {
 
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.3.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.4.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 
@@ -234,7 +234,7 @@ int kpdi_destroy(kpdi_ctx *c) {
                     &c->bound_s, &c->bound_i, &c->gthr, &c->tile_ctr, &c->gather_s, &c->gather_i, &c->bg, &c->taps, &c->inv_map, &c->pre_scratch,
                     &c->mp_packed, &c->dcos, &c->rot, &c->proj_out,
                     &c->ref_raw, &c->ref_map, &c->ref_rowcol, &c->ref_pat, &c->ref_sqn, &c->ref_in, &c->ref_out,
-                    &c->ref_idx, &c->osm_idx, &c->osm_out, &c->iq_tab, &c->iq_ws, &c->iq_out, &c->stage[0], &c->stage[1], &c->pending.raw, &c->pending.raw_b, &c->pending_hold.raw})
+                    &c->ref_idx, &c->osm_idx, &c->osm_out, &c->iq_tab, &c->iq_ws, &c->iq_out, &c->ff_tab, &c->ff_ws, &c->stage[0], &c->stage[1], &c->pending.raw, &c->pending.raw_b, &c->pending_hold.raw})
     b->release();
   for (auto *l : {&c->ev_match, &c->ev_prep, &c->ev_merge, &c->ev_proj, &c->ev_pre, &c->ev_rescore})
     for (auto &pr : *l) {
@@ -560,6 +560,78 @@ int kpdi_image_quality(kpdi_ctx *c, int normalize, const double *weights, double
   a.out = c->iq_out.as<float>();
   HIPCHK(kpdi::launch_image_quality(a, c->stream));
   return results_to_host(c, iq_out, c->iq_out.p, (size_t)c->m_all * sizeof(float));  // (synchronises: `tab` is read)
+}
+
+int kpdi_fft_filter(kpdi_ctx *c, int function_domain, const double *table, int ty, int tx) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
+  if (!table) return fail(KPDI_EINVAL, "table is NULL");
+  if (c->exp_dtype == KPDI_F16 || c->exp_dtype == KPDI_I32 || c->exp_dtype == KPDI_U32)
+    return fail(KPDI_EINVAL, "the FFT filter takes uint8/int8/uint16/int16/float32/float64 patterns");
+  const int sy = c->sy, sx = c->sx, h = kpdi::ff_half_cols(sx);
+  const bool freq = function_domain == KPDI_DOMAIN_FREQUENCY;
+  if (!freq && function_domain != KPDI_DOMAIN_SPATIAL) return fail(KPDI_EINVAL, "unknown function domain %d", function_domain);
+  if (freq && (ty != sy || tx != h))
+    return fail(KPDI_EINVAL, "folded transfer function of %d x %d, patterns of %d x %d need %d x %d", ty, tx, sy, sx, sy, h);
+  if (!freq && (ty < 1 || tx < 1 || (int64_t)ty * tx > (1 << 20)))
+    return fail(KPDI_EINVAL, "spatial kernel of %d x %d", ty, tx);
+  const kpdi::FfPlan plan = kpdi::ff_plan(freq ? kpdi::FF_DOMAIN_FREQUENCY : kpdi::FF_DOMAIN_SPATIAL, sy, sx, c->m_all);
+  if (plan.path < 0) return fail(KPDI_EINVAL, "FFT filter of %d x %d patterns: no kernel path takes this shape", sy, sx);
+  int rc = use_device(c);
+  if (rc) return rc;
+  bool dummy = false;
+  rc = flush_preprocess(c, false, &dummy);  // recorded background-removal steps run first
+  if (rc) return rc;
+  // frequency: twiddles (f32) + the folded table / (sy sx) as f32 complex; spatial: the kernel rounded to f32, as doubles
+  std::vector<char> tab;
+  size_t tab_off = 0;
+  if (freq) {
+    const size_t tbytes = 2 * ((size_t)sx + sy) * sizeof(float), hbytes = 2 * (size_t)sy * h * sizeof(float);
+    tab.resize(tbytes + hbytes);
+    float *tw = (float *)tab.data();
+    for (int n : {sx, sy})
+      for (int j = 0; j < n; ++j, tw += 2) {
+        const double a = 2.0 * M_PI * j / n;
+        tw[0] = (float)cos(a);
+        tw[1] = (float)sin(a);
+      }
+    float *hs = (float *)(tab.data() + tbytes);
+    const double scale = 1.0 / ((double)sy * sx);
+    for (size_t i = 0; i < 2 * (size_t)sy * h; ++i) hs[i] = (float)(table[i] * scale);
+    tab_off = tbytes;
+  } else {
+    tab.resize((size_t)ty * tx * sizeof(double));
+    double *tp = (double *)tab.data();
+    for (size_t i = 0; i < (size_t)ty * tx; ++i) tp[i] = (double)(float)table[i];
+  }
+  HIPCHK(c->ff_tab.reserve(tab.size()));
+  HIPCHK(hipMemcpyAsync(c->ff_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+  if (plan.path == 1) HIPCHK(c->ff_ws.reserve(plan.workspace_bytes));
+  kpdi::FfLaunch a{};
+  a.patterns = c->exp_raw.p;
+  a.dtype = c->exp_dtype;
+  a.n = c->m_all;
+  a.sy = sy;
+  a.sx = sx;
+  a.domain = freq ? kpdi::FF_DOMAIN_FREQUENCY : kpdi::FF_DOMAIN_SPATIAL;
+  a.twiddles = freq ? (const float *)c->ff_tab.p : nullptr;
+  a.table = freq ? (const float *)((const char *)c->ff_tab.p + tab_off) : nullptr;
+  a.taps = freq ? nullptr : (const double *)c->ff_tab.p;
+  a.ty = ty;
+  a.tx = tx;
+  dtype_range(c->exp_dtype, &a.omin, &a.omax);
+  a.workspace = c->ff_ws.p;
+  a.workspace_bytes = c->ff_ws.cap;
+  hipError_t e = kpdi::launch_fft_filter(a, c->stream);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "FFT-filter kernel: %s (dtype %d, %dx%d)", hipGetErrorString(e), c->exp_dtype, sy, sx);
+  HIPCHK(hipStreamSynchronize(c->stream));  // `tab` dies at scope exit
+  // the resident patterns changed: what was prepared from them is stale
+  c->exp_prepared = false;
+  c->run_valid = false;
+  discard_pending(c);
+  c->final_valid = false;
+  return KPDI_OK;
 }
 
 size_t kpdi_dtype_size(int dtype) { return kpdi::dtype_size(dtype); }

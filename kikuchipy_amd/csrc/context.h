@@ -16,6 +16,7 @@
 #include "../../include/kpdi.h"
 #include "kernels.h"
 #include "iq_plan.h"
+#include "fftfilter_plan.h"
 #include "plan.h"
 #include "group_hooks.h"
 
@@ -185,6 +186,7 @@ struct kpdi_ctx {
   bool have_nav_mask = false;
   kpdi::DevBuf exp_raw, row_map, exp_x;
   kpdi::DevBuf iq_tab, iq_ws, iq_out;  // kpdi_image_quality: twiddles + folded weights, path-1 workspace, results
+  kpdi::DevBuf ff_tab, ff_ws;  // kpdi_fft_filter: twiddles + folded table (or the taps), path-1 workspace
 
   // dictionary chunk
   kpdi::DevBuf dict_raw, dict_y;

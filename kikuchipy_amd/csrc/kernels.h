@@ -346,4 +346,17 @@ struct IqLaunch {
 };
 hipError_t launch_image_quality(const IqLaunch &a, hipStream_t s);
 
+// ---- FFT filter (fftfilter.hip) ---------------------------------------------------
+struct FfLaunch {
+  void *patterns; int dtype; int64_t n; int sy, sx;  // n x sy x sx of `dtype`, device, filtered in place
+  int domain;             // FF_DOMAIN_FREQUENCY / FF_DOMAIN_SPATIAL (fftfilter_plan.h)
+  const float *twiddles;  // frequency: (cos, sin)(2 pi j / sx) for j < sx, then the same for sy: 2 (sx + sy) floats
+  const float *table;     // frequency: [sy][sx / 2 + 1] complex (re, im) folded transfer function / (sy sx)
+  const double *taps;     // spatial: [ty][tx] correlation kernel
+  int ty, tx;
+  float omin, omax;       // the dtype range (rescale_intensity)
+  void *workspace; size_t workspace_bytes;  // path 1 of fftfilter_plan.h
+};
+hipError_t launch_fft_filter(const FfLaunch &a, hipStream_t s);
+
 }  // namespace kpdi

@@ -1,8 +1,10 @@
-"""The two windows of `kikuchipy.filters.Window` that the accelerated path uses
+"""The windows of `kikuchipy.filters` that the accelerated path uses
 (filters/window.py of the reference): the circular detector mask of the canonical
 pipeline, `signal_mask = ~Window("circular", shape).astype(bool)`
-(doc/tutorials/pattern_matching.ipynb), and the Gaussian window behind
-`remove_dynamic_background`.  Other window types are not part of this path.
+(doc/tutorials/pattern_matching.ipynb), the Gaussian window behind
+`remove_dynamic_background`, and the transfer functions of `EBSD.fft_filter`
+(`lowpass_fft_filter`, `highpass_fft_filter`, `modified_hann`).  `Window` does
+not build the named FFT-filter windows; pass these arrays instead.
 """
 
 import numpy as np
@@ -19,6 +21,44 @@ def distance_to_origin(shape, origin=None):
         (x, y), (ox, oy) = coordinates, origin
         return np.sqrt((x - ox) ** 2 + (y - oy) ** 2)
     return np.abs(coordinates[0] - origin[0])
+
+
+def modified_hann(Nx):
+    """filters/window.py:419-451: the 1-D modified Hann window of Wilkinson et al. (2006), maximum 1:
+    `cos(pi * x / Nx)` with x the distance of sample 0 ... Nx - 1 to the window's centre."""
+    x = np.arange(Nx) - (Nx / 2) + 0.5
+    return np.cos(np.pi * x / Nx)
+
+
+def _cutoff_transfer_function(shape, cutoff, cutoff_width, low):
+    """A Gaussian edge of width `cutoff_width` (default cutoff / 2) around the radius `cutoff` from the centre of
+    `shape`: 1 inside the passband, 0 beyond two widths into the stopband."""
+    r = distance_to_origin(shape)
+    if cutoff_width is None:
+        cutoff_width = cutoff / 2
+    z = ((r - cutoff) if low else (cutoff - r)) / (np.sqrt(2) * cutoff_width / 2)
+    w = np.exp(-(z**2))
+    if low:
+        w[r > (cutoff + (2 * cutoff_width))] = 0
+        w[r < cutoff] = 1
+    else:
+        w[r < (cutoff - (2 * cutoff_width))] = 0
+        w[r > cutoff] = 1
+    return w
+
+
+def lowpass_fft_filter(shape, cutoff, cutoff_width=None):
+    """filters/window.py:454-517: 2-D low-pass transfer function, centred (use with `fft_filter(..., shift=True)`):
+    `exp(-((r - cutoff) / (sqrt(2) cutoff_width / 2))**2)`, 1 for r < cutoff, 0 for r > cutoff + 2 cutoff_width; r is the
+    distance to the centre, `cutoff_width` defaults to cutoff / 2."""
+    return _cutoff_transfer_function(shape, cutoff, cutoff_width, low=True)
+
+
+def highpass_fft_filter(shape, cutoff, cutoff_width=None):
+    """filters/window.py:520-590: 2-D high-pass transfer function, centred: `exp(-((cutoff - r) / (sqrt(2)
+    cutoff_width / 2))**2)`, 1 for r > cutoff, 0 for r < cutoff - 2 cutoff_width; `cutoff_width` defaults to
+    cutoff / 2."""
+    return _cutoff_transfer_function(shape, cutoff, cutoff_width, low=False)
 
 
 class Window(np.ndarray):

@@ -1,4 +1,5 @@
 from kikuchipy_amd.pattern._pattern import (  # noqa: F401
+    fft_filter_stack,
     fft_frequency_vectors,
     get_image_quality,
     remove_dynamic_background,

@@ -1,4 +1,4 @@
-"""Static / dynamic background removal and image quality on the GPU.
+"""Static / dynamic background removal, FFT filtering and image quality on the GPU.
 
 Array-level counterparts of `EBSD.remove_static_background`
 (signals/ebsd.py:442-573) and `EBSD.remove_dynamic_background`
@@ -6,7 +6,8 @@ Array-level counterparts of `EBSD.remove_static_background`
 output dtype; the per-pattern kernels of pattern/_pattern.py:392-509 run as
 one HIP workgroup per pattern (csrc/preproc.hip).  `get_image_quality`
 (pattern/_pattern.py:698-775) runs a half-spectrum DFT per pattern
-(csrc/iq.hip).
+(csrc/iq.hip).  `fft_filter_stack` is what `EBSD.fft_filter`
+(signals/ebsd.py:805-930) runs on a stack (csrc/fftfilter.hip).
 """
 
 import numpy as np
@@ -163,3 +164,44 @@ def get_image_quality(patterns, normalize=True, frequency_vectors=None, inertia_
     q = _process(patterns, lambda c: None, context, device, contexts,
                  collect=lambda c: c.image_quality(normalize, w, inertia_max))
     return float(q) if patterns.ndim == 2 else q
+
+
+_FUNCTION_DOMAINS = ["frequency", "spatial"]
+
+
+def fft_filter_table(transfer_function, function_domain, shift, shape):
+    """(domain code, table) of `Context.fft_filter` for patterns of `shape` (sy, sx), with the reference's checks.
+
+    Frequency domain: the reference computes `Re(ifft2(fft2(p) H'))` with `H' = ifftshift(H)` for `shift` (its
+    fftshift -> multiply -> ifftshift, for odd shapes too), else `H`.  For real `p` that equals `ifft2(fft2(p) Hs)` with
+    `Hs(k) = (H'(k) + conj(H'(-k))) / 2`, so `H` may be complex or not symmetric; the table is `Hs` on the half
+    spectrum, (sy, sx // 2 + 1) complex.  Spatial domain: the kernel (ty, tx) as float64."""
+    if function_domain == "frequency":
+        h = np.asarray(transfer_function)
+        if h.shape != tuple(shape):
+            raise ValueError(f"transfer_function has shape {h.shape}, the patterns {tuple(shape)}")
+        h = np.asarray(np.fft.ifftshift(h) if shift else h, dtype=np.complex128)
+        sy, sx = h.shape
+        mirror = np.conj(h[(-np.arange(sy)) % sy][:, (-np.arange(sx)) % sx])
+        return _lib.DOMAIN_FREQUENCY, (0.5 * (h + mirror))[:, : sx // 2 + 1]
+    if function_domain == "spatial":
+        w = np.asarray(transfer_function)
+        if w.ndim != 2 or np.iscomplexobj(w):
+            raise ValueError(f"a spatial kernel must be a real 2D array, not of shape {w.shape} and dtype {w.dtype}")
+        return _lib.DOMAIN_SPATIAL, w.astype(np.float64)
+    raise ValueError(f"{function_domain} must be either of {_FUNCTION_DOMAINS}")
+
+
+def fft_filter_stack(patterns, transfer_function, function_domain, shift=False, *, context=None, device=0,
+                     contexts=None):
+    """`EBSD.fft_filter` on an array (..., sy, sx): every pattern as float32, filtered
+    (`fft_filter_table`), then `rescale_intensity(filtered, dtype_out=patterns.dtype)`; returns a new array of the
+    input's dtype and shape.  A pattern holding a NaN or inf, or whose filtered result is constant (the reference's
+    0 / 0), becomes 0 for integer dtypes and NaN for float dtypes.
+
+    Not the reference's `pattern.fft_filter`, which returns one unrescaled float pattern."""
+    patterns = np.asarray(patterns)
+    if patterns.ndim < 2:
+        raise ValueError("patterns need at least the two detector axes")
+    domain, table = fft_filter_table(transfer_function, function_domain, shift, patterns.shape[-2:])
+    return _process(patterns, lambda c: c.fft_filter(domain, table), context, device, contexts)

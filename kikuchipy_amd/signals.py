@@ -284,6 +284,23 @@ class EBSD:
             return None
         return self._like(out)
 
+    def fft_filter(self, transfer_function, function_domain, shift=False, show_progressbar=None, inplace=True,
+                   lazy_output=None, *, devices=None):
+        """signals/ebsd.py:805-930: filter every pattern in the frequency domain (`transfer_function` of the pattern
+        shape, applied to the spectrum; `shift`: it is centred) or the spatial domain (a kernel, applied as Barnes' FFT
+        convolution with edge-replicated borders), then rescale it to its dtype's range
+        (`kikuchipy_amd.pattern.fft_filter_stack`); `show_progressbar` / `lazy_output` as in
+        `remove_static_background`."""
+        if lazy_output and inplace:
+            raise ValueError("'lazy_output=True' requires 'inplace=False'")
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        out = _pattern.fft_filter_stack(np.asarray(self.data), transfer_function, function_domain, shift,
+                                        context=None if contexts else self.context, contexts=contexts)
+        if inplace:
+            self.data = out
+            return None
+        return self._like(out)
+
     def get_image_quality(self, normalize=True, show_progressbar=None, *, devices=None):
         """signals/ebsd.py:1312-1375: Q of every pattern (`kikuchipy_amd.pattern.get_image_quality` with the default
         frequency vectors), float32 of the navigation shape (0-d without navigation axes).  `show_progressbar` is
