@@ -202,6 +202,27 @@ int kpdi_image_quality(kpdi_ctx *ctx, int normalize, const double *weights, doub
  * csrc/fftfilter_plan.h. */
 int kpdi_fft_filter(kpdi_ctx *ctx, int function_domain, const double *table, int ty, int tx);
 
+/* ---- intensity rescaling / normalization (EBSD.rescale_intensity / normalize_intensity,
+ * signals/_kikuchipy_signal.py:88-338; pattern/_pattern.py:31-111, :154-210) -----------------------------------------
+ * Each call maps every resident pattern, AFTER the recorded background steps (they run first), into `dtype_out`
+ * (KPDI_U8 / I8 / U16 / I16 / F32 / F64; the patterns themselves may be any of these).  A new dtype replaces the resident
+ * patterns (kpdi_get_experimental then returns `dtype_out`); the navigation mask is ignored and prepared rows made
+ * before the call are invalidated.  The arithmetic is the reference's under NumPy 1.26 dtype rules, float64 for integer
+ * and float64 patterns, float32 for float32 patterns; casts to integer dtypes truncate to int32 (NaN and values outside
+ * int32: INT32_MIN) and keep the low bits, as ndarray.astype does on x86-64.  Kernels and paths: csrc/intensity.hip,
+ * csrc/intensity_plan.h.
+ * kpdi_rescale_intensity: ((clip(p, imin, imax) - imin) / (imax - imin)) * (omax - omin) + omin with (imin, imax) =
+ *   `in_range` (2 doubles; no clip when NULL), else np.nanpercentile(p, `percentiles`) per pattern (2 doubles in
+ *   [0, 100]), else the pattern's nanmin / nanmax; in_range and percentiles are exclusive.  Integer patterns are
+ *   computed exactly (the reference's int8 / int16 arithmetic can wrap).
+ * kpdi_normalize_intensity: (p - mean) / (num_std * std [* sqrt(sy * sx)]) per pattern, sums in float64.
+ * kpdi_intensity_range: out[0], out[1] = min and max over all resident patterns (NaN if any value is NaN), for the
+ *   reference's relative=True. */
+int kpdi_rescale_intensity(kpdi_ctx *ctx, const double *in_range, const double *percentiles, double omin, double omax,
+                           int dtype_out);
+int kpdi_normalize_intensity(kpdi_ctx *ctx, double num_std, int divide_by_square_root, int dtype_out);
+int kpdi_intensity_range(kpdi_ctx *ctx, double *out);
+
 /* ---- dictionary sweep (_dictionary_indexing loop, indexing/_dictionary_indexing.py:94-128)
  * One call = one loop iteration: prepare_dictionary (cast, mask, normalise) +
  * match + top-k of the chunk + merge into the running best-k, all on the GPU.

@@ -133,6 +133,9 @@ SIGNATURES = {
     "kpdi_get_experimental": (_i, [_vp, _vp]),
     "kpdi_image_quality": (_i, [_vp, _i, _vp, C.c_double, _vp]),
     "kpdi_fft_filter": (_i, [_vp, _i, _vp, _i, _i]),
+    "kpdi_rescale_intensity": (_i, [_vp, _vp, _vp, C.c_double, C.c_double, _i]),
+    "kpdi_normalize_intensity": (_i, [_vp, C.c_double, _i, _i]),
+    "kpdi_intensity_range": (_i, [_vp, _vp]),
     "kpdi_push_dictionary_chunk": (_i, [_vp, _vp, _i, _i64, _i64]),
     "kpdi_push_dictionary_chunk_dev": (_i, [_vp, _vp, _i, _i64, _i64]),
     "kpdi_set_master_pattern": (_i, [_vp, _vp, _vp, _i, _i, _i]),
@@ -464,6 +467,29 @@ class Context:
         if t.ndim != 2:
             raise KpdiError(f"filter table of shape {t.shape}")
         check(self._f.fft_filter(self._h, int(function_domain), _ptr(flat), int(t.shape[0]), int(t.shape[1])))
+
+    def rescale_intensity(self, in_range=None, percentiles=None, omin=0.0, omax=1.0, dtype_out=None):
+        """Rescale every resident pattern (after the recorded background steps) onto [omin, omax] from `in_range`,
+        the per-pattern `percentiles` or the per-pattern min / max, into `dtype_out` (None: the patterns' dtype); the
+        resident patterns take the new dtype (include/kpdi.h, kpdi_rescale_intensity)."""
+        dt = self._exp_dtype if dtype_out is None else np.dtype(dtype_out)
+        ir = None if in_range is None else np.ascontiguousarray(in_range, dtype=np.float64).reshape(2)
+        pc = None if percentiles is None else np.ascontiguousarray(percentiles, dtype=np.float64).reshape(2)
+        check(self._f.rescale_intensity(self._h, _ptr(ir), _ptr(pc), float(omin), float(omax), dtype_code(dt)))
+        self._exp_dtype = dt
+
+    def normalize_intensity(self, num_std=1, divide_by_square_root=False, dtype_out=None):
+        """(p - mean) / (num_std * std [* sqrt(size)]) of every resident pattern into `dtype_out` (None: the patterns'
+        dtype); the resident patterns take the new dtype (include/kpdi.h, kpdi_normalize_intensity)."""
+        dt = self._exp_dtype if dtype_out is None else np.dtype(dtype_out)
+        check(self._f.normalize_intensity(self._h, float(num_std), int(bool(divide_by_square_root)), dtype_code(dt)))
+        self._exp_dtype = dt
+
+    def intensity_range(self):
+        """(min, max) over every resident pattern, NaN if any value is NaN: float64 (2,)."""
+        out = np.empty(2, dtype=np.float64)
+        check(self._f.intensity_range(self._h, _ptr(out)))
+        return out
 
     # -- sweep
     def set_dictionary_size(self, n_total):

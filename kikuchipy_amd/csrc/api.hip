@@ -172,7 +172,7 @@ int results_to_host(kpdi_ctx *c, void *dst, const void *d_src, size_t bytes) {
 
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.4.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.5.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 
@@ -234,7 +234,7 @@ int kpdi_destroy(kpdi_ctx *c) {
                     &c->bound_s, &c->bound_i, &c->gthr, &c->tile_ctr, &c->gather_s, &c->gather_i, &c->bg, &c->taps, &c->inv_map, &c->pre_scratch,
                     &c->mp_packed, &c->dcos, &c->rot, &c->proj_out,
                     &c->ref_raw, &c->ref_map, &c->ref_rowcol, &c->ref_pat, &c->ref_sqn, &c->ref_in, &c->ref_out,
-                    &c->ref_idx, &c->osm_idx, &c->osm_out, &c->iq_tab, &c->iq_ws, &c->iq_out, &c->ff_tab, &c->ff_ws, &c->stage[0], &c->stage[1], &c->pending.raw, &c->pending.raw_b, &c->pending_hold.raw})
+                    &c->ref_idx, &c->osm_idx, &c->osm_out, &c->iq_tab, &c->iq_ws, &c->iq_out, &c->ff_tab, &c->ff_ws, &c->int_out, &c->int_ws, &c->stage[0], &c->stage[1], &c->pending.raw, &c->pending.raw_b, &c->pending_hold.raw})
     b->release();
   for (auto *l : {&c->ev_match, &c->ev_prep, &c->ev_merge, &c->ev_proj, &c->ev_pre, &c->ev_rescore})
     for (auto &pr : *l) {
@@ -632,6 +632,112 @@ int kpdi_fft_filter(kpdi_ctx *c, int function_domain, const double *table, int t
   discard_pending(c);
   c->final_valid = false;
   return KPDI_OK;
+}
+
+}  // extern "C"
+
+namespace kpdi {
+
+static bool intensity_dtype(int d) {
+  return d == KPDI_U8 || d == KPDI_I8 || d == KPDI_U16 || d == KPDI_I16 || d == KPDI_F32 || d == KPDI_F64;
+}
+
+// common part of kpdi_rescale_intensity / kpdi_normalize_intensity: the recorded background steps first, then one
+// kernel from exp_raw into exp_raw (same dtype) or into int_out, which then becomes exp_raw (a new dtype: converting in
+// place would let one workgroup's writes overtake another's reads whenever the element size changes)
+static int run_intensity(kpdi_ctx *c, IntLaunch &a) {
+  if (!intensity_dtype(c->exp_dtype))
+    return fail(KPDI_EINVAL, "intensity rescaling takes uint8/int8/uint16/int16/float32/float64 patterns");
+  if (!intensity_dtype(a.dtype_out))
+    return fail(KPDI_EINVAL, "dtype_out %d: intensity rescaling writes uint8/int8/uint16/int16/float32/float64", a.dtype_out);
+  if (int_plan(c->exp_dtype, c->sy, c->sx, c->m_all).path < 0)
+    return fail(KPDI_EINVAL, "intensity rescaling of %lld patterns of %d x %d: no kernel path takes this shape",
+                (long long)c->m_all, c->sy, c->sx);
+  int rc = use_device(c);
+  if (rc) return rc;
+  bool dummy = false;
+  rc = flush_preprocess(c, false, &dummy);  // recorded background-removal steps run first
+  if (rc) return rc;
+  const bool same = a.dtype_out == c->exp_dtype;
+  if (!same) HIPCHK(c->int_out.reserve((size_t)c->m_all * c->npix * dtype_size(a.dtype_out)));
+  a.src = c->exp_raw.p;
+  a.dtype = c->exp_dtype;
+  a.dst = same ? c->exp_raw.p : c->int_out.p;
+  a.n = c->m_all;
+  a.sy = c->sy;
+  a.sx = c->sx;
+  hipError_t e = launch_intensity(a, c->stream);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "intensity kernel: %s (dtype %d -> %d, %dx%d)", hipGetErrorString(e), c->exp_dtype,
+                a.dtype_out, c->sy, c->sx);
+  if (!same) {
+    std::swap(c->exp_raw, c->int_out);
+    c->exp_dtype = a.dtype_out;
+  }
+  // the resident patterns changed: what was prepared from them is stale
+  c->exp_prepared = false;
+  c->run_valid = false;
+  discard_pending(c);
+  c->final_valid = false;
+  return KPDI_OK;
+}
+
+}  // namespace kpdi
+
+extern "C" {
+
+int kpdi_rescale_intensity(kpdi_ctx *c, const double *in_range, const double *percentiles, double omin, double omax,
+                           int dtype_out) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
+  if (in_range && percentiles) return fail(KPDI_EINVAL, "in_range and percentiles are exclusive");
+  kpdi::IntLaunch a{};
+  a.dtype_out = dtype_out;
+  a.omin = omin;
+  a.orange = omax - omin;
+  if (percentiles) {
+    a.mode = kpdi::INT_MODE_PERCENTILE;
+    a.q0 = percentiles[0] / 100.0;  // np.true_divide(q, 100.0)
+    a.q1 = percentiles[1] / 100.0;
+    if (!(a.q0 >= 0 && a.q0 <= 1 && a.q1 >= 0 && a.q1 <= 1)) return fail(KPDI_EINVAL, "Percentiles must be in the range [0, 100]");
+  } else if (in_range) {
+    a.mode = kpdi::INT_MODE_RANGE;
+    a.lo = in_range[0];
+    a.hi = in_range[1];
+  } else {
+    a.mode = kpdi::INT_MODE_MINMAX;
+  }
+  return kpdi::run_intensity(c, a);
+}
+
+int kpdi_normalize_intensity(kpdi_ctx *c, double num_std, int divide_by_square_root, int dtype_out) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
+  kpdi::IntLaunch a{};
+  a.dtype_out = dtype_out;
+  a.mode = kpdi::INT_MODE_NORMALIZE;
+  a.num_std = num_std;
+  a.divide_by_square_root = divide_by_square_root != 0;
+  return kpdi::run_intensity(c, a);
+}
+
+int kpdi_intensity_range(kpdi_ctx *c, double *out) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
+  if (!out) return fail(KPDI_EINVAL, "out is NULL");
+  if (!kpdi::intensity_dtype(c->exp_dtype))
+    return fail(KPDI_EINVAL, "intensity rescaling takes uint8/int8/uint16/int16/float32/float64 patterns");
+  int rc = use_device(c);
+  if (rc) return rc;
+  bool dummy = false;
+  rc = flush_preprocess(c, false, &dummy);  // recorded background-removal steps run first
+  if (rc) return rc;
+  HIPCHK(c->int_ws.reserve((3 * (size_t)kpdi::INT_RANGE_BLOCKS + 2) * sizeof(double)));
+  double *ws = c->int_ws.as<double>();
+  hipError_t e = kpdi::launch_intensity_range(c->exp_raw.p, c->exp_dtype, c->m_all * (int64_t)c->npix, ws + 2, ws,
+                                              c->stream);
+  if (e != hipSuccess) return fail(KPDI_EHIP, "intensity range kernel: %s", hipGetErrorString(e));
+  return results_to_host(c, out, ws, 2 * sizeof(double));
 }
 
 size_t kpdi_dtype_size(int dtype) { return kpdi::dtype_size(dtype); }

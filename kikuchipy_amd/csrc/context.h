@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "iq_plan.h"
 #include "fftfilter_plan.h"
+#include "intensity_plan.h"
 #include "plan.h"
 #include "group_hooks.h"
 
@@ -187,6 +188,7 @@ struct kpdi_ctx {
   kpdi::DevBuf exp_raw, row_map, exp_x;
   kpdi::DevBuf iq_tab, iq_ws, iq_out;  // kpdi_image_quality: twiddles + folded weights, path-1 workspace, results
   kpdi::DevBuf ff_tab, ff_ws;  // kpdi_fft_filter: twiddles + folded table (or the taps), path-1 workspace
+  kpdi::DevBuf int_out, int_ws;  // kpdi_*_intensity: the patterns in a new dtype (swapped with exp_raw), range partials
 
   // dictionary chunk
   kpdi::DevBuf dict_raw, dict_y;

@@ -359,4 +359,20 @@ struct FfLaunch {
 };
 hipError_t launch_fft_filter(const FfLaunch &a, hipStream_t s);
 
+// ---- intensity rescaling / normalization (intensity.hip) ----------------------------
+struct IntLaunch {
+  const void *src; int dtype;      // n x sy x sx of `dtype`, device
+  void *dst; int dtype_out;        // n x sy x sx of `dtype_out`; == src when the dtype stays (in place)
+  int64_t n; int sy, sx;
+  int mode;                        // INT_MODE_* (intensity_plan.h)
+  double lo, hi;                   // INT_MODE_RANGE: in_range
+  double q0, q1;                   // INT_MODE_PERCENTILE: the percentiles / 100
+  double omin, orange;             // rescale: out_range[0], out_range[1] - out_range[0]
+  double num_std; int divide_by_square_root;  // INT_MODE_NORMALIZE
+};
+hipError_t launch_intensity(const IntLaunch &a, hipStream_t s);
+// NaN-propagating min / max over n x npix values of `dtype` -> out[0], out[1] (device); `partial`: 3 x
+// INT_RANGE_BLOCKS doubles
+hipError_t launch_intensity_range(const void *src, int dtype, int64_t count, double *partial, double *out, hipStream_t s);
+
 }  // namespace kpdi

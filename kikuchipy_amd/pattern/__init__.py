@@ -2,6 +2,10 @@ from kikuchipy_amd.pattern._pattern import (  # noqa: F401
     fft_filter_stack,
     fft_frequency_vectors,
     get_image_quality,
+    normalize_intensity,
+    normalize_intensity_stack,
     remove_dynamic_background,
     remove_static_background,
+    rescale_intensity,
+    rescale_intensity_stack,
 )

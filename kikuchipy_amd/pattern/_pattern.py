@@ -1,4 +1,4 @@
-"""Static / dynamic background removal, FFT filtering and image quality on the GPU.
+"""Static / dynamic background removal, FFT filtering, intensity rescaling / normalization and image quality on the GPU.
 
 Array-level counterparts of `EBSD.remove_static_background`
 (signals/ebsd.py:442-573) and `EBSD.remove_dynamic_background`
@@ -8,6 +8,10 @@ one HIP workgroup per pattern (csrc/preproc.hip).  `get_image_quality`
 (pattern/_pattern.py:698-775) runs a half-spectrum DFT per pattern
 (csrc/iq.hip).  `fft_filter_stack` is what `EBSD.fft_filter`
 (signals/ebsd.py:805-930) runs on a stack (csrc/fftfilter.hip).
+`rescale_intensity` / `normalize_intensity` (pattern/_pattern.py:31-93,
+:154-210) and their `_stack` forms, which `EBSD.rescale_intensity` /
+`normalize_intensity` (signals/_kikuchipy_signal.py:88-338) run, map every
+pattern in one HIP workgroup (csrc/intensity.hip).
 """
 
 import numpy as np
@@ -205,3 +209,140 @@ def fft_filter_stack(patterns, transfer_function, function_domain, shift=False, 
         raise ValueError("patterns need at least the two detector axes")
     domain, table = fft_filter_table(transfer_function, function_domain, shift, patterns.shape[-2:])
     return _process(patterns, lambda c: c.fft_filter(domain, table), context, device, contexts)
+
+
+# skimage.util.dtype.dtype_range (skimage need not be importable): the default out_range of rescale_intensity
+DTYPE_RANGE = {
+    np.bool_: (False, True),
+    np.float16: (-1, 1),
+    np.float32: (-1, 1),
+    np.float64: (-1, 1),
+    np.uint8: (0, 255),
+    np.uint16: (0, 65535),
+    np.uint32: (0, 2**32 - 1),
+    np.uint64: (0, 2**64 - 1),
+    np.int8: (-128, 127),
+    np.int16: (-32768, 32767),
+    np.int32: (-(2**31), 2**31 - 1),
+    np.int64: (-(2**63), 2**63 - 1),
+}
+INTENSITY_DTYPES = (np.uint8, np.int8, np.uint16, np.int16, np.float32, np.float64)
+
+
+def intensity_dtype_out(dtype_out, default):
+    """`dtype_out` (None: `default`) as a NumPy dtype the intensity kernels write, else ValueError."""
+    dt = np.dtype(default) if dtype_out is None else np.dtype(dtype_out)
+    if dt.type not in INTENSITY_DTYPES:
+        raise ValueError(f"dtype_out {dt} is not supported: the GPU intensity kernels write "
+                         f"{', '.join(np.dtype(t).name for t in INTENSITY_DTYPES)}")
+    return dt
+
+
+def _out_range(out_range, dtype_out):
+    return DTYPE_RANGE[dtype_out.type] if out_range is None else tuple(out_range)
+
+
+def _check_percentiles(percentiles):
+    q = np.asarray(percentiles, dtype=np.float64)
+    if q.shape != (2,):
+        raise ValueError(f"percentiles must be a pair, not {percentiles!r}")
+    if not np.all((q >= 0) & (q <= 100)):
+        raise ValueError("Percentiles must be in the range [0, 100]")
+    return q
+
+
+def _rescale_record(in_range, out_range, dtype_out, percentiles):
+    omin, omax = out_range
+    return lambda c, rng=in_range: c.rescale_intensity(None if percentiles is not None else rng, percentiles,
+                                                       omin, omax, dtype_out)
+
+
+def _process_relative(patterns, rescale, context, device, contexts):
+    """`rescale(ctx, in_range)` with in_range the global (min, max) of all patterns, NaN-propagating as
+    `data.min()` / `data.max()`.  One context: upload, reduce, rescale, download.  Several (`contexts`, block-wise as
+    `_process`): every member uploads its block and reduces it, the host combines the ranges, then every member
+    rescales and downloads its block."""
+    patterns = np.asarray(patterns)
+    lead = patterns.shape[:-2]
+    if not (contexts and len(contexts) > 1 and patterns.ndim > 2 and int(np.prod(lead)) >= len(contexts)):
+        return _process(patterns, lambda c: rescale(c, c.intensity_range()), context, device, contexts)
+    from concurrent.futures import ThreadPoolExecutor
+
+    from kikuchipy_amd.parallel import shard_range
+
+    flat = np.ascontiguousarray(patterns).reshape((-1,) + patterns.shape[-2:])
+    blocks = [shard_range(len(flat), i, len(contexts)) for i in range(len(contexts))]
+
+    def reduce(job):
+        c, (a, b) = job
+        _upload(c, flat[a:b])
+        return c.intensity_range()
+
+    def finish(c):
+        rescale(c, rng)
+        return _download(c)
+
+    with ThreadPoolExecutor(len(contexts)) as pool:
+        ranges = np.array(list(pool.map(reduce, zip(contexts, blocks))))
+        rng = np.array([ranges[:, 0].min(), ranges[:, 1].max()])  # NaN in any block -> NaN
+        parts = list(pool.map(finish, contexts))
+    return np.concatenate(parts, axis=0).reshape(lead + parts[0].shape[1:])
+
+
+def rescale_intensity(pattern, in_range=None, out_range=None, dtype_out=None, percentiles=None, *, context=None,
+                      device=0):
+    """pattern/_pattern.py:31-93: `((clip(p, imin, imax) - imin) / (imax - imin)) * (omax - omin) + omin` as
+    `dtype_out` (default: the pattern's dtype), with (imin, imax) = `np.nanpercentile(p, percentiles)` (which overwrites
+    `in_range`), else `in_range`, else the pattern's nanmin / nanmax; (omin, omax) = `out_range`, default the dtype
+    range of `dtype_out` (`DTYPE_RANGE`).  As in the reference the whole input is ONE image, whatever its shape.
+    NumPy 1.26 arithmetic: float64 for integer and float64 patterns, float32 for float32 patterns; integer patterns
+    are computed exactly (the reference's int8 / int16 differences can wrap); casts to integer dtypes truncate to int32
+    and keep the low bits (NaN -> 0)."""
+    pattern = np.asarray(pattern)
+    dt = intensity_dtype_out(dtype_out, pattern.dtype)
+    if percentiles is not None:
+        percentiles = _check_percentiles(percentiles)
+    one = pattern.reshape((1, 1, pattern.size))
+    out = _process(one, _rescale_record(in_range, _out_range(out_range, dt), dt, percentiles), context, device, None)
+    return out.reshape(pattern.shape)
+
+
+def normalize_intensity(pattern, num_std=1, divide_by_square_root=False, dtype_out=None, *, context=None, device=0):
+    """pattern/_pattern.py:154-210: `(p - mean) / (num_std * std [* sqrt(p.size)])` of the whole input as one image,
+    as `dtype_out`; None gives the arithmetic's dtype, float64 (integer and float64 input) or float32 (float32 input).
+    Sums run in float64."""
+    pattern = np.asarray(pattern)
+    arith = np.float32 if pattern.dtype == np.float32 else np.float64
+    dt = intensity_dtype_out(dtype_out, arith)
+    one = pattern.reshape((1, 1, pattern.size))
+    out = _process(one, lambda c: c.normalize_intensity(num_std, divide_by_square_root, dt), context, device, None)
+    return out.reshape(pattern.shape)
+
+
+def rescale_intensity_stack(patterns, in_range=None, out_range=None, dtype_out=None, percentiles=None, *,
+                            relative=False, context=None, device=0, contexts=None):
+    """`rescale_intensity` of every pattern of (..., sy, sx), what `EBSD.rescale_intensity` maps: `relative` takes
+    (imin, imax) as the global min / max of all patterns (NaN if any is NaN) unless `percentiles` are given; returns a
+    new array of `dtype_out` (default: the patterns' dtype) and the input's shape."""
+    patterns = np.asarray(patterns)
+    if patterns.ndim < 2:
+        raise ValueError("patterns need at least the two detector axes")
+    dt = intensity_dtype_out(dtype_out, patterns.dtype)
+    if percentiles is not None:
+        percentiles = _check_percentiles(percentiles)
+    record = _rescale_record(in_range, _out_range(out_range, dt), dt, percentiles)
+    if relative and percentiles is None:
+        return _process_relative(patterns, lambda c, rng: record(c, rng), context, device, contexts)
+    return _process(patterns, record, context, device, contexts)
+
+
+def normalize_intensity_stack(patterns, num_std=1, divide_by_square_root=False, dtype_out=None, *, context=None,
+                              device=0, contexts=None):
+    """`normalize_intensity` of every pattern of (..., sy, sx), what `EBSD.normalize_intensity` maps; `dtype_out`
+    defaults to the patterns' dtype, as there."""
+    patterns = np.asarray(patterns)
+    if patterns.ndim < 2:
+        raise ValueError("patterns need at least the two detector axes")
+    dt = intensity_dtype_out(dtype_out, patterns.dtype)
+    return _process(patterns, lambda c: c.normalize_intensity(num_std, divide_by_square_root, dt), context, device,
+                    contexts)

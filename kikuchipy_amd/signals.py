@@ -301,6 +301,45 @@ class EBSD:
             return None
         return self._like(out)
 
+    def rescale_intensity(self, relative=False, in_range=None, out_range=None, dtype_out=None, percentiles=None,
+                          show_progressbar=None, inplace=True, lazy_output=None, *, devices=None):
+        """signals/_kikuchipy_signal.py:88-243: rescale every pattern onto `out_range` (default: the dtype range of
+        `dtype_out`, which defaults to the data's dtype) from `in_range`, the global min / max (`relative`; NaN if any
+        value is NaN), the per-pattern `percentiles` or the per-pattern min / max
+        (`kikuchipy_amd.pattern.rescale_intensity_stack`).  With `inplace` `self.data` is replaced and may change its
+        dtype; `show_progressbar` / `lazy_output` as in `remove_static_background`."""
+        if lazy_output and inplace:
+            raise ValueError("'lazy_output=True' requires 'inplace=False'")
+        if in_range is not None and percentiles is not None:
+            raise ValueError("'percentiles' must be None if 'in_range' is not None")
+        elif relative is True and in_range is not None:
+            raise ValueError("'in_range' must be None if 'relative' is True")
+        _pattern.intensity_dtype_out(dtype_out, self.data.dtype)  # before any GPU work
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        out = _pattern.rescale_intensity_stack(np.asarray(self.data), in_range, out_range, dtype_out, percentiles,
+                                               relative=bool(relative), context=None if contexts else self.context,
+                                               contexts=contexts)
+        if inplace:
+            self.data = out
+            return None
+        return self._like(out)
+
+    def normalize_intensity(self, num_std=1, divide_by_square_root=False, dtype_out=None, show_progressbar=None,
+                            inplace=True, lazy_output=None, *, devices=None):
+        """signals/_kikuchipy_signal.py:245-338: `(p - mean) / (num_std * std [* sqrt(size)])` of every pattern as
+        `dtype_out` (default: the data's dtype; `kikuchipy_amd.pattern.normalize_intensity_stack`); `inplace`,
+        `show_progressbar` / `lazy_output` as in `rescale_intensity`."""
+        if lazy_output and inplace:
+            raise ValueError("'lazy_output=True' requires 'inplace=False'")
+        _pattern.intensity_dtype_out(dtype_out, self.data.dtype)  # before any GPU work
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        out = _pattern.normalize_intensity_stack(np.asarray(self.data), num_std, divide_by_square_root, dtype_out,
+                                                 context=None if contexts else self.context, contexts=contexts)
+        if inplace:
+            self.data = out
+            return None
+        return self._like(out)
+
     def get_image_quality(self, normalize=True, show_progressbar=None, *, devices=None):
         """signals/ebsd.py:1312-1375: Q of every pattern (`kikuchipy_amd.pattern.get_image_quality` with the default
         frequency vectors), float32 of the navigation shape (0-d without navigation axes).  `show_progressbar` is
