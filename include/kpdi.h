@@ -223,6 +223,17 @@ int kpdi_rescale_intensity(kpdi_ctx *ctx, const double *in_range, const double *
 int kpdi_normalize_intensity(kpdi_ctx *ctx, double num_std, int divide_by_square_root, int dtype_out);
 int kpdi_intensity_range(kpdi_ctx *ctx, double *out);
 
+/* ---- adaptive histogram equalization (EBSD.adaptive_histogram_equalization, signals/_kikuchipy_signal.py:340-470;
+ * pattern/_pattern.py:810-840: scikit-image 0.18.3's equalize_adapthist, then rescale_intensity to the dtype's range) --
+ * Equalizes every resident pattern in place, AFTER the recorded background steps (they run first); the dtype stays,
+ * the navigation mask is ignored and prepared rows made before the call are invalidated.  `ky` x `kx`: the kernel
+ * (contextual region) in rows x columns, any size >= 1 (larger than the pattern too); `clip_count`: the integer clip
+ * limit the reference derives, int(max(clip_limit * ky * kx, 1)) for clip_limit > 0, else ky * kx (no clipping);
+ * 1 <= `nbins` <= 16384.  Float patterns are taken as the reference takes values in [-1, 1] (the caller checks the
+ * range; values outside are clipped, NaN counts as 0).  Bit-exact with the reference under NumPy 1.26; kernels and
+ * paths: csrc/clahe.hip, csrc/clahe_plan.h.  KPDI_EINVAL where no path takes the shape, kernel and bins. */
+int kpdi_adaptive_histogram_equalization(kpdi_ctx *ctx, int ky, int kx, int clip_count, int nbins);
+
 /* ---- dictionary sweep (_dictionary_indexing loop, indexing/_dictionary_indexing.py:94-128)
  * One call = one loop iteration: prepare_dictionary (cast, mask, normalise) +
  * match + top-k of the chunk + merge into the running best-k, all on the GPU.

@@ -136,6 +136,7 @@ SIGNATURES = {
     "kpdi_rescale_intensity": (_i, [_vp, _vp, _vp, C.c_double, C.c_double, _i]),
     "kpdi_normalize_intensity": (_i, [_vp, C.c_double, _i, _i]),
     "kpdi_intensity_range": (_i, [_vp, _vp]),
+    "kpdi_adaptive_histogram_equalization": (_i, [_vp, _i, _i, _i, _i]),
     "kpdi_push_dictionary_chunk": (_i, [_vp, _vp, _i, _i64, _i64]),
     "kpdi_push_dictionary_chunk_dev": (_i, [_vp, _vp, _i, _i64, _i64]),
     "kpdi_set_master_pattern": (_i, [_vp, _vp, _vp, _i, _i, _i]),
@@ -490,6 +491,12 @@ class Context:
         out = np.empty(2, dtype=np.float64)
         check(self._f.intensity_range(self._h, _ptr(out)))
         return out
+
+    def adaptive_histogram_equalization(self, ky, kx, clip_count, nbins):
+        """Equalize every resident pattern in place (after the recorded background steps) with a `ky` x `kx` kernel,
+        the integer clip limit `clip_count` (>= ky * kx: none) and `nbins` bins; the dtype stays (include/kpdi.h,
+        kpdi_adaptive_histogram_equalization)."""
+        check(self._f.adaptive_histogram_equalization(self._h, int(ky), int(kx), int(clip_count), int(nbins)))
 
     # -- sweep
     def set_dictionary_size(self, n_total):

@@ -172,7 +172,7 @@ int results_to_host(kpdi_ctx *c, void *dst, const void *d_src, size_t bytes) {
 
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.5.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.6.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 
@@ -234,7 +234,7 @@ int kpdi_destroy(kpdi_ctx *c) {
                     &c->bound_s, &c->bound_i, &c->gthr, &c->tile_ctr, &c->gather_s, &c->gather_i, &c->bg, &c->taps, &c->inv_map, &c->pre_scratch,
                     &c->mp_packed, &c->dcos, &c->rot, &c->proj_out,
                     &c->ref_raw, &c->ref_map, &c->ref_rowcol, &c->ref_pat, &c->ref_sqn, &c->ref_in, &c->ref_out,
-                    &c->ref_idx, &c->osm_idx, &c->osm_out, &c->iq_tab, &c->iq_ws, &c->iq_out, &c->ff_tab, &c->ff_ws, &c->int_out, &c->int_ws, &c->stage[0], &c->stage[1], &c->pending.raw, &c->pending.raw_b, &c->pending_hold.raw})
+                    &c->ref_idx, &c->osm_idx, &c->osm_out, &c->iq_tab, &c->iq_ws, &c->iq_out, &c->ff_tab, &c->ff_ws, &c->int_out, &c->int_ws, &c->cl_ws, &c->stage[0], &c->stage[1], &c->pending.raw, &c->pending.raw_b, &c->pending_hold.raw})
     b->release();
   for (auto *l : {&c->ev_match, &c->ev_prep, &c->ev_merge, &c->ev_proj, &c->ev_pre, &c->ev_rescore})
     for (auto &pr : *l) {
@@ -738,6 +738,52 @@ int kpdi_intensity_range(kpdi_ctx *c, double *out) {
                                               c->stream);
   if (e != hipSuccess) return fail(KPDI_EHIP, "intensity range kernel: %s", hipGetErrorString(e));
   return results_to_host(c, out, ws, 2 * sizeof(double));
+}
+
+int kpdi_adaptive_histogram_equalization(kpdi_ctx *c, int ky, int kx, int clip_count, int nbins) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
+  if (!kpdi::intensity_dtype(c->exp_dtype))
+    return fail(KPDI_EINVAL, "adaptive histogram equalization takes uint8/int8/uint16/int16/float32/float64 patterns");
+  if (ky < 1 || kx < 1) return fail(KPDI_EINVAL, "kernel of %d x %d", ky, kx);
+  if (nbins < 1 || nbins > kpdi::CLAHE_MAX_NBINS) return fail(KPDI_EINVAL, "nbins %d outside [1, %d]", nbins, kpdi::CLAHE_MAX_NBINS);
+  if (clip_count < 1) return fail(KPDI_EINVAL, "clip_count %d < 1", clip_count);
+  const kpdi::ClahePlan plan = kpdi::clahe_launch_plan(c->exp_dtype, c->sy, c->sx, ky, kx, nbins, c->m_all);
+  if (plan.path < 0)
+    return fail(KPDI_EINVAL, "adaptive histogram equalization of %d x %d patterns with a %d x %d kernel and %d bins: no kernel path takes this shape",
+                c->sy, c->sx, ky, kx, nbins);
+  int rc = use_device(c);
+  if (rc) return rc;
+  bool dummy = false;
+  rc = flush_preprocess(c, false, &dummy);  // recorded background-removal steps run first
+  if (rc) return rc;
+  if (plan.path == 1) HIPCHK(c->cl_ws.reserve(plan.workspace_bytes));
+  kpdi::ClaheLaunch a{};
+  a.patterns = c->exp_raw.p;
+  a.dtype = c->exp_dtype;
+  a.n = c->m_all;
+  a.sy = c->sy;
+  a.sx = c->sx;
+  a.ky = ky;
+  a.kx = kx;
+  a.clip_count = clip_count;
+  a.nbins = nbins;
+  float omin, omax;
+  dtype_range(c->exp_dtype, &omin, &omax);
+  a.omin = omin;
+  a.omax = omax;
+  a.workspace = c->cl_ws.p;
+  a.workspace_bytes = c->cl_ws.cap;
+  hipError_t e = kpdi::launch_clahe(a, c->stream);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "adaptive histogram equalization kernel: %s (dtype %d, %dx%d)", hipGetErrorString(e),
+                c->exp_dtype, c->sy, c->sx);
+  // the resident patterns changed: what was prepared from them is stale
+  c->exp_prepared = false;
+  c->run_valid = false;
+  discard_pending(c);
+  c->final_valid = false;
+  return KPDI_OK;
 }
 
 size_t kpdi_dtype_size(int dtype) { return kpdi::dtype_size(dtype); }

@@ -18,6 +18,7 @@
 #include "iq_plan.h"
 #include "fftfilter_plan.h"
 #include "intensity_plan.h"
+#include "clahe_plan.h"
 #include "plan.h"
 #include "group_hooks.h"
 
@@ -188,6 +189,7 @@ struct kpdi_ctx {
   kpdi::DevBuf exp_raw, row_map, exp_x;
   kpdi::DevBuf iq_tab, iq_ws, iq_out;  // kpdi_image_quality: twiddles + folded weights, path-1 workspace, results
   kpdi::DevBuf ff_tab, ff_ws;  // kpdi_fft_filter: twiddles + folded table (or the taps), path-1 workspace
+  kpdi::DevBuf cl_ws;  // kpdi_adaptive_histogram_equalization: path-1 workspace
   kpdi::DevBuf int_out, int_ws;  // kpdi_*_intensity: the patterns in a new dtype (swapped with exp_raw), range partials
 
   // dictionary chunk

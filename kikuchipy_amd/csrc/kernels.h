@@ -5,6 +5,8 @@
 
 #include <vector>
 
+#include "clahe_plan.h"
+
 namespace kpdi {
 
 // ---- tile geometry of the match kernel (match.hip) -------------------------
@@ -374,5 +376,18 @@ hipError_t launch_intensity(const IntLaunch &a, hipStream_t s);
 // NaN-propagating min / max over n x npix values of `dtype` -> out[0], out[1] (device); `partial`: 3 x
 // INT_RANGE_BLOCKS doubles
 hipError_t launch_intensity_range(const void *src, int dtype, int64_t count, double *partial, double *out, hipStream_t s);
+
+// ---- adaptive histogram equalization (clahe.hip) ----------------------------------------
+struct ClaheLaunch {
+  void *patterns; int dtype;       // n x sy x sx of `dtype`, device, equalized in place
+  int64_t n; int sy, sx;
+  int ky, kx;                      // the kernel (contextual region), rows x columns
+  int clip_count, nbins;           // the integer clip limit (>= ky * kx: no clipping), 1 <= nbins <= 16384
+  double omin, omax;               // dtype_range of the dtype
+  void *workspace; size_t workspace_bytes;  // path 1 (clahe_plan.h)
+};
+// the plan launch_clahe follows (KPDI_CLAHE_PATH=1 forces path 1)
+ClahePlan clahe_launch_plan(int dtype, int sy, int sx, int ky, int kx, int nbins, int64_t n);
+hipError_t launch_clahe(const ClaheLaunch &a, hipStream_t s);
 
 }  // namespace kpdi

@@ -1,4 +1,6 @@
 from kikuchipy_amd.pattern._pattern import (  # noqa: F401
+    adaptive_histogram_equalization,
+    adaptive_histogram_equalization_stack,
     fft_filter_stack,
     fft_frequency_vectors,
     get_image_quality,

@@ -11,8 +11,13 @@ one HIP workgroup per pattern (csrc/preproc.hip).  `get_image_quality`
 `rescale_intensity` / `normalize_intensity` (pattern/_pattern.py:31-93,
 :154-210) and their `_stack` forms, which `EBSD.rescale_intensity` /
 `normalize_intensity` (signals/_kikuchipy_signal.py:88-338) run, map every
-pattern in one HIP workgroup (csrc/intensity.hip).
+pattern in one HIP workgroup (csrc/intensity.hip).  `adaptive_histogram_equalization` (pattern/_pattern.py:810-840)
+and `adaptive_histogram_equalization_stack`, which `EBSD.adaptive_histogram_equalization`
+(signals/_kikuchipy_signal.py:340-470) runs, equalize every pattern in one HIP workgroup (csrc/clahe.hip).
 """
+
+import numbers
+import operator
 
 import numpy as np
 
@@ -346,3 +351,80 @@ def normalize_intensity_stack(patterns, num_std=1, divide_by_square_root=False, 
     dt = intensity_dtype_out(dtype_out, patterns.dtype)
     return _process(patterns, lambda c: c.normalize_intensity(num_std, divide_by_square_root, dt), context, device,
                     contexts)
+
+
+CLAHE_MAX_NBINS = 16384  # csrc/clahe_plan.h: 2**14 grey levels
+
+
+def clahe_kernel_size(kernel_size, sig_shape):
+    """The kernel (rows, cols) `EBSD.adaptive_histogram_equalization` derives for patterns of `sig_shape` (sy, sx):
+    None gives (sx // 4, sy // 4) - the reference takes HyperSpy's signal_shape (x, y) as (rows, cols), so the default
+    is transposed for non-square patterns - a number (k, k), a pair is taken as it is; int() of each entry."""
+    sy, sx = sig_shape
+    if kernel_size is None:
+        kernel_size = (sx // 4, sy // 4)
+    elif isinstance(kernel_size, numbers.Number):
+        kernel_size = (kernel_size,) * 2
+    elif len(kernel_size) != 2:
+        raise ValueError(f"Incorrect value of `shape`: {kernel_size}")
+    return [int(k) for k in kernel_size]
+
+
+def clahe_arguments(patterns, kernel_size, clip_limit, nbins):
+    """(ky, kx, clip_count, nbins) of `Context.adaptive_histogram_equalization` for `patterns` (..., sy, sx) and a
+    kernel of (rows, cols), raising what the reference raises for its first pattern, in its order, before any GPU work:
+    a float pattern outside [-1, 1] without a NaN (img_as_uint), a kernel entry of 0 (ZeroDivisionError) or below,
+    nbins of 0 (ZeroDivisionError) or below.  nbins above 16384 is refused; the reference accepts it and lets the extra,
+    always empty bins take part in the clip redistribution."""
+    ky, kx = kernel_size
+    if patterns.dtype.kind == "f" and patterns.size:
+        flat = patterns.reshape(-1, patterns.shape[-2] * patterns.shape[-1])
+        mn, mx = flat.min(axis=1), flat.max(axis=1)  # NaN in a pattern: no check for it, as np.min gives NaN there
+        if np.any((mn < -1.0) | (mx > 1.0)):
+            raise ValueError("Images of type float must be between -1 and 1.")
+    if ky == 0 or kx == 0:
+        raise ZeroDivisionError("integer division or modulo by zero")
+    if ky < 0 or kx < 0:
+        raise ValueError("index can't contain negative values")
+    nbins = operator.index(nbins)
+    if nbins == 0:
+        raise ZeroDivisionError("integer division or modulo by zero")
+    if nbins < 0:
+        raise ValueError("'minlength' must not be negative")
+    if nbins > CLAHE_MAX_NBINS:
+        raise ValueError(f"nbins={nbins}: at most {CLAHE_MAX_NBINS} bins (the 2**14 grey levels of the equalization) "
+                         "are supported")
+    kk = ky * kx
+    clim = int(np.clip(clip_limit * kk, 1, None)) if clip_limit > 0 else kk
+    return ky, kx, min(clim, kk), nbins  # a limit of ky * kx or more clips nothing
+
+
+def adaptive_histogram_equalization(pattern, kernel_size, clip_limit=0, nbins=128, *, context=None, device=0):
+    """pattern/_pattern.py:810-840 on one 2-D pattern: scikit-image 0.18.3's
+    `equalize_adapthist(pattern, kernel_size, clip_limit, nbins)`, then `rescale_intensity` to the range of the pattern's
+    dtype; returns a new array of that dtype.  `kernel_size`: None gives scikit-image's default (sy // 8, sx // 8), a
+    number (k, k), a pair (rows, cols); a length other than 2 raises (scikit-image builds that error without raising
+    it).  Errors: `clahe_arguments`."""
+    pattern = np.asarray(pattern)
+    if pattern.ndim != 2:
+        raise ValueError(f"one 2-D pattern is equalized, not an array of shape {pattern.shape}")
+    if kernel_size is None:
+        kernel_size = (pattern.shape[0] // 8, pattern.shape[1] // 8)
+    elif isinstance(kernel_size, numbers.Number):
+        kernel_size = (kernel_size,) * 2
+    elif len(kernel_size) != 2:
+        raise ValueError(f"Incorrect value of `kernel_size`: {kernel_size}")
+    args = clahe_arguments(pattern, [int(k) for k in kernel_size], clip_limit, nbins)
+    return _process(pattern, lambda c: c.adaptive_histogram_equalization(*args), context, device, None)
+
+
+def adaptive_histogram_equalization_stack(patterns, kernel_size=None, clip_limit=0, nbins=128, *, context=None,
+                                          device=0, contexts=None):
+    """`adaptive_histogram_equalization` of every pattern of (..., sy, sx), what
+    `EBSD.adaptive_histogram_equalization` maps: `kernel_size` as `clahe_kernel_size` derives it (None: the reference's
+    (sx // 4, sy // 4)); returns a new array of the input's dtype and shape."""
+    patterns = np.asarray(patterns)
+    if patterns.ndim < 2:
+        raise ValueError("patterns need at least the two detector axes")
+    args = clahe_arguments(patterns, clahe_kernel_size(kernel_size, patterns.shape[-2:]), clip_limit, nbins)
+    return _process(patterns, lambda c: c.adaptive_histogram_equalization(*args), context, device, contexts)

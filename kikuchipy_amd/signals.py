@@ -340,6 +340,34 @@ class EBSD:
             return None
         return self._like(out)
 
+    def adaptive_histogram_equalization(self, kernel_size=None, clip_limit=0.0, nbins=128, show_progressbar=None,
+                                        inplace=True, lazy_output=None, *, devices=None):
+        """signals/_kikuchipy_signal.py:340-470: scikit-image 0.18.3's equalize_adapthist of every pattern, then a
+        rescale to the range of the data's dtype (`kikuchipy_amd.pattern.adaptive_histogram_equalization_stack`).
+        `kernel_size` None gives (sx // 4, sy // 4) as (rows, cols), as the reference's HyperSpy order does; the
+        reference's warnings for NaN and float data; `show_progressbar` / `lazy_output` as in
+        `remove_static_background`."""
+        if lazy_output and inplace:
+            raise ValueError("'lazy_output=True' requires 'inplace=False'")
+        data = np.asarray(self.data)
+        if np.isnan(data).any():
+            warnings.warn("Equalization of signals with NaN data has been shown to give bad results")
+        elif np.issubdtype(data.dtype, np.floating):
+            warnings.warn(
+                "Equalization of signals with floating point data type has been shown to give bad results. Rescaling "
+                "intensities to integer intensities is recommended."
+            )
+        kernel_size = _pattern.clahe_kernel_size(kernel_size, self._signal_shape_rc)
+        _pattern.clahe_arguments(data, kernel_size, clip_limit, nbins)  # before any GPU work
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        out = _pattern.adaptive_histogram_equalization_stack(data, kernel_size, clip_limit, nbins,
+                                                             context=None if contexts else self.context,
+                                                             contexts=contexts)
+        if inplace:
+            self.data = out
+            return None
+        return self._like(out)
+
     def get_image_quality(self, normalize=True, show_progressbar=None, *, devices=None):
         """signals/ebsd.py:1312-1375: Q of every pattern (`kikuchipy_amd.pattern.get_image_quality` with the default
         frequency vectors), float32 of the navigation shape (0-d without navigation axes).  `show_progressbar` is
