@@ -168,6 +168,47 @@ int results_to_host(kpdi_ctx *c, void *dst, const void *d_src, size_t bytes) {
   return KPDI_OK;
 }
 
+// the six dtypes the ops on the resident patterns take; kpdi_set_experimental accepts dtypes 0 - 8, so this is "not
+// float16 / int32 / uint32"
+static bool intensity_dtype(int d) {
+  return d == KPDI_U8 || d == KPDI_I8 || d == KPDI_U16 || d == KPDI_I16 || d == KPDI_F32 || d == KPDI_F64;
+}
+
+// what every op on the resident patterns checks first; `op` names it in the error text
+static int check_patterns(kpdi_ctx *c, const char *op) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
+  if (!intensity_dtype(c->exp_dtype))
+    return fail(KPDI_EINVAL, "%s takes uint8/int8/uint16/int16/float32/float64 patterns", op);
+  return KPDI_OK;
+}
+
+// once its own arguments are checked: the device, then the recorded background-removal steps, which run first
+static int start_pattern_op(kpdi_ctx *c) {
+  int rc = use_device(c);
+  if (rc) return rc;
+  bool dummy = false;
+  return flush_preprocess(c, false, &dummy);
+}
+
+// the resident patterns changed: what was prepared from them is stale
+static void patterns_changed(kpdi_ctx *c) {
+  c->exp_prepared = false;
+  c->run_valid = false;
+  discard_pending(c);
+  c->final_valid = false;
+}
+
+// (cos, sin)(2 pi j / n) as f32 pairs for j < sx, then for j < sy: 2 (sx + sy) floats
+static void write_twiddles(float *tw, int sy, int sx) {
+  for (int n : {sx, sy})
+    for (int j = 0; j < n; ++j, tw += 2) {
+      const double a = 2.0 * M_PI * j / n;
+      tw[0] = (float)cos(a);
+      tw[1] = (float)sin(a);
+    }
+}
+
 }  // namespace kpdi
 
 extern "C" {
@@ -214,28 +255,15 @@ int kpdi_destroy(kpdi_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   release_held(c);
-  c->pin_out.release();
-  for (auto &st : c->rot_stage) {
-    st.pin.release();
+  for (auto &st : c->rot_stage)
     if (st.copied) (void)hipEventDestroy(st.copied);
-  }
-  c->pend64.flag.release();
   if (c->pend64.ready) (void)hipEventDestroy(c->pend64.ready);
-  for (auto &rs : c->slots) {
-    rs.pin.release();
+  for (auto &rs : c->slots)
     if (rs.ready) (void)hipEventDestroy(rs.ready);
-  }
   if (c->result_done) (void)hipEventDestroy(c->result_done);
   if (c->result_stream) (void)hipStreamDestroy(c->result_stream);
   if (c->lists_final) (void)hipEventDestroy(c->lists_final);
   if (c->peer_read) (void)hipEventDestroy(c->peer_read);
-  for (DevBuf *b : {&c->pix_map, &c->quad_desc, &c->exp_raw, &c->row_map, &c->exp_x, &c->dict_raw, &c->dict_y, &c->part_s,
-                    &c->part_i, &c->part_cnt, &c->tail_s, &c->tail_i, &c->tail_scores, &c->list16, &c->run_s[0], &c->run_s[1], &c->run_i[0], &c->run_i[1], &c->loc_s, &c->loc_i,
-                    &c->bound_s, &c->bound_i, &c->gthr, &c->tile_ctr, &c->gather_s, &c->gather_i, &c->bg, &c->taps, &c->inv_map, &c->pre_scratch,
-                    &c->mp_packed, &c->dcos, &c->rot, &c->proj_out,
-                    &c->ref_raw, &c->ref_map, &c->ref_rowcol, &c->ref_pat, &c->ref_sqn, &c->ref_in, &c->ref_out,
-                    &c->ref_idx, &c->osm_idx, &c->osm_out, &c->iq_tab, &c->iq_ws, &c->iq_out, &c->ff_tab, &c->ff_ws, &c->int_out, &c->int_ws, &c->cl_ws, &c->stage[0], &c->stage[1], &c->pending.raw, &c->pending.raw_b, &c->pending_hold.raw})
-    b->release();
   for (auto *l : {&c->ev_match, &c->ev_prep, &c->ev_merge, &c->ev_proj, &c->ev_pre, &c->ev_rescore})
     for (auto &pr : *l) {
       (void)hipEventDestroy(pr.first);
@@ -259,7 +287,7 @@ int kpdi_destroy(kpdi_ctx *c) {
     (void)hipEventDestroy(c->ev_join);
   }
   (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // (the device and pinned buffers free themselves)
   return KPDI_OK;
 }
 
@@ -409,10 +437,7 @@ int kpdi_remove_static_background(kpdi_ctx *c, const float *static_bg, int opera
   c->pend.st_scale = scale_bg ? 1 : 0;
   c->pend.bg_min = *std::min_element(static_bg, static_bg + c->npix);
   c->pend.bg_max = *std::max_element(static_bg, static_bg + c->npix);
-  c->exp_prepared = false;
-  c->run_valid = false;
-  discard_pending(c);
-  c->final_valid = false;
+  patterns_changed(c);
   return KPDI_OK;
 }
 
@@ -475,10 +500,7 @@ int kpdi_remove_dynamic_background(kpdi_ctx *c, int operation, int filter_domain
   c->pend.reflect = reflect;
   c->pend.ntaps = n;
   c->pend.centre = centre;
-  c->exp_prepared = false;
-  c->run_valid = false;
-  discard_pending(c);
-  c->final_valid = false;
+  patterns_changed(c);
   return KPDI_OK;
 }
 
@@ -497,18 +519,13 @@ int kpdi_get_experimental(kpdi_ctx *c, void *out) {
 }
 
 int kpdi_image_quality(kpdi_ctx *c, int normalize, const double *weights, double inertia_max, float *iq_out) {
-  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
-  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
+  int rc = check_patterns(c, "image quality");
+  if (rc) return rc;
   if (!iq_out) return fail(KPDI_EINVAL, "iq_out is NULL");
-  if (c->exp_dtype == KPDI_F16 || c->exp_dtype == KPDI_I32 || c->exp_dtype == KPDI_U32)
-    return fail(KPDI_EINVAL, "image quality takes uint8/int8/uint16/int16/float32/float64 patterns");
-  const int sy = c->sy, sx = c->sx, h = kpdi::iq_half_cols(sx);
+  const int sy = c->sy, sx = c->sx, h = kpdi::half_cols(sx);
   const kpdi::IqPlan plan = kpdi::iq_plan(sy, sx, c->m_all);
   if (plan.path < 0) return fail(KPDI_EINVAL, "image quality of %d x %d patterns: no kernel path takes this shape", sy, sx);
-  int rc = use_device(c);
-  if (rc) return rc;
-  bool dummy = false;
-  rc = flush_preprocess(c, false, &dummy);  // recorded background-removal steps run first
+  rc = start_pattern_op(c);
   if (rc) return rc;
   // weights w (pattern/_pattern.py:365-386 unless given), inertia_max = sum w / (sy sx) unless given
   std::vector<double> w((size_t)sy * sx);
@@ -534,17 +551,11 @@ int kpdi_image_quality(kpdi_ctx *c, int normalize, const double *weights, double
       const bool self = l == 0 || 2 * l == sx;
       wf[(size_t)k * h + l] = w[(size_t)k * sx + l] + (self ? 0.0 : w[(size_t)((sy - k) % sy) * sx + (sx - l)]);
     }
-  float *tw = (float *)(tab.data() + wbytes);
-  for (int n : {sx, sy})
-    for (int j = 0; j < n; ++j, tw += 2) {
-      const double a = 2.0 * M_PI * j / n;
-      tw[0] = (float)cos(a);
-      tw[1] = (float)sin(a);
-    }
-  HIPCHK(c->iq_tab.reserve(tab.size()));
-  HIPCHK(hipMemcpyAsync(c->iq_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+  write_twiddles((float *)(tab.data() + wbytes), sy, sx);
+  HIPCHK(c->op_tab.reserve(tab.size()));
+  HIPCHK(hipMemcpyAsync(c->op_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c->iq_out.reserve((size_t)c->m_all * sizeof(float)));
-  if (plan.path == 1) HIPCHK(c->iq_ws.reserve(plan.workspace_bytes));
+  if (plan.path == 1) HIPCHK(c->op_ws.reserve(plan.workspace_bytes));
   kpdi::IqLaunch a;
   a.patterns = c->exp_raw.p;
   a.dtype = c->exp_dtype;
@@ -552,23 +563,21 @@ int kpdi_image_quality(kpdi_ctx *c, int normalize, const double *weights, double
   a.sy = sy;
   a.sx = sx;
   a.normalize = normalize ? 1 : 0;
-  a.wfold = (const double *)c->iq_tab.p;
-  a.twiddles = (const float *)((const char *)c->iq_tab.p + wbytes);
+  a.wfold = (const double *)c->op_tab.p;
+  a.twiddles = (const float *)((const char *)c->op_tab.p + wbytes);
   a.inertia_max = inertia_max;
-  a.workspace = c->iq_ws.p;
-  a.workspace_bytes = c->iq_ws.cap;
+  a.workspace = c->op_ws.p;
+  a.workspace_bytes = c->op_ws.cap;
   a.out = c->iq_out.as<float>();
   HIPCHK(kpdi::launch_image_quality(a, c->stream));
   return results_to_host(c, iq_out, c->iq_out.p, (size_t)c->m_all * sizeof(float));  // (synchronises: `tab` is read)
 }
 
 int kpdi_fft_filter(kpdi_ctx *c, int function_domain, const double *table, int ty, int tx) {
-  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
-  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
+  int rc = check_patterns(c, "the FFT filter");
+  if (rc) return rc;
   if (!table) return fail(KPDI_EINVAL, "table is NULL");
-  if (c->exp_dtype == KPDI_F16 || c->exp_dtype == KPDI_I32 || c->exp_dtype == KPDI_U32)
-    return fail(KPDI_EINVAL, "the FFT filter takes uint8/int8/uint16/int16/float32/float64 patterns");
-  const int sy = c->sy, sx = c->sx, h = kpdi::ff_half_cols(sx);
+  const int sy = c->sy, sx = c->sx, h = kpdi::half_cols(sx);
   const bool freq = function_domain == KPDI_DOMAIN_FREQUENCY;
   if (!freq && function_domain != KPDI_DOMAIN_SPATIAL) return fail(KPDI_EINVAL, "unknown function domain %d", function_domain);
   if (freq && (ty != sy || tx != h))
@@ -577,10 +586,7 @@ int kpdi_fft_filter(kpdi_ctx *c, int function_domain, const double *table, int t
     return fail(KPDI_EINVAL, "spatial kernel of %d x %d", ty, tx);
   const kpdi::FfPlan plan = kpdi::ff_plan(freq ? kpdi::FF_DOMAIN_FREQUENCY : kpdi::FF_DOMAIN_SPATIAL, sy, sx, c->m_all);
   if (plan.path < 0) return fail(KPDI_EINVAL, "FFT filter of %d x %d patterns: no kernel path takes this shape", sy, sx);
-  int rc = use_device(c);
-  if (rc) return rc;
-  bool dummy = false;
-  rc = flush_preprocess(c, false, &dummy);  // recorded background-removal steps run first
+  rc = start_pattern_op(c);
   if (rc) return rc;
   // frequency: twiddles (f32) + the folded table / (sy sx) as f32 complex; spatial: the kernel rounded to f32, as doubles
   std::vector<char> tab;
@@ -588,13 +594,7 @@ int kpdi_fft_filter(kpdi_ctx *c, int function_domain, const double *table, int t
   if (freq) {
     const size_t tbytes = 2 * ((size_t)sx + sy) * sizeof(float), hbytes = 2 * (size_t)sy * h * sizeof(float);
     tab.resize(tbytes + hbytes);
-    float *tw = (float *)tab.data();
-    for (int n : {sx, sy})
-      for (int j = 0; j < n; ++j, tw += 2) {
-        const double a = 2.0 * M_PI * j / n;
-        tw[0] = (float)cos(a);
-        tw[1] = (float)sin(a);
-      }
+    write_twiddles((float *)tab.data(), sy, sx);
     float *hs = (float *)(tab.data() + tbytes);
     const double scale = 1.0 / ((double)sy * sx);
     for (size_t i = 0; i < 2 * (size_t)sy * h; ++i) hs[i] = (float)(table[i] * scale);
@@ -604,9 +604,9 @@ int kpdi_fft_filter(kpdi_ctx *c, int function_domain, const double *table, int t
     double *tp = (double *)tab.data();
     for (size_t i = 0; i < (size_t)ty * tx; ++i) tp[i] = (double)(float)table[i];
   }
-  HIPCHK(c->ff_tab.reserve(tab.size()));
-  HIPCHK(hipMemcpyAsync(c->ff_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
-  if (plan.path == 1) HIPCHK(c->ff_ws.reserve(plan.workspace_bytes));
+  HIPCHK(c->op_tab.reserve(tab.size()));
+  HIPCHK(hipMemcpyAsync(c->op_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c->stream));
+  if (plan.path == 1) HIPCHK(c->op_ws.reserve(plan.workspace_bytes));
   kpdi::FfLaunch a{};
   a.patterns = c->exp_raw.p;
   a.dtype = c->exp_dtype;
@@ -614,23 +614,19 @@ int kpdi_fft_filter(kpdi_ctx *c, int function_domain, const double *table, int t
   a.sy = sy;
   a.sx = sx;
   a.domain = freq ? kpdi::FF_DOMAIN_FREQUENCY : kpdi::FF_DOMAIN_SPATIAL;
-  a.twiddles = freq ? (const float *)c->ff_tab.p : nullptr;
-  a.table = freq ? (const float *)((const char *)c->ff_tab.p + tab_off) : nullptr;
-  a.taps = freq ? nullptr : (const double *)c->ff_tab.p;
+  a.twiddles = freq ? (const float *)c->op_tab.p : nullptr;
+  a.table = freq ? (const float *)((const char *)c->op_tab.p + tab_off) : nullptr;
+  a.taps = freq ? nullptr : (const double *)c->op_tab.p;
   a.ty = ty;
   a.tx = tx;
   dtype_range(c->exp_dtype, &a.omin, &a.omax);
-  a.workspace = c->ff_ws.p;
-  a.workspace_bytes = c->ff_ws.cap;
+  a.workspace = c->op_ws.p;
+  a.workspace_bytes = c->op_ws.cap;
   hipError_t e = kpdi::launch_fft_filter(a, c->stream);
   if (e != hipSuccess)
     return fail(KPDI_EHIP, "FFT-filter kernel: %s (dtype %d, %dx%d)", hipGetErrorString(e), c->exp_dtype, sy, sx);
   HIPCHK(hipStreamSynchronize(c->stream));  // `tab` dies at scope exit
-  // the resident patterns changed: what was prepared from them is stale
-  c->exp_prepared = false;
-  c->run_valid = false;
-  discard_pending(c);
-  c->final_valid = false;
+  patterns_changed(c);
   return KPDI_OK;
 }
 
@@ -638,25 +634,18 @@ int kpdi_fft_filter(kpdi_ctx *c, int function_domain, const double *table, int t
 
 namespace kpdi {
 
-static bool intensity_dtype(int d) {
-  return d == KPDI_U8 || d == KPDI_I8 || d == KPDI_U16 || d == KPDI_I16 || d == KPDI_F32 || d == KPDI_F64;
-}
-
 // common part of kpdi_rescale_intensity / kpdi_normalize_intensity: the recorded background steps first, then one
 // kernel from exp_raw into exp_raw (same dtype) or into int_out, which then becomes exp_raw (a new dtype: converting in
 // place would let one workgroup's writes overtake another's reads whenever the element size changes)
 static int run_intensity(kpdi_ctx *c, IntLaunch &a) {
-  if (!intensity_dtype(c->exp_dtype))
-    return fail(KPDI_EINVAL, "intensity rescaling takes uint8/int8/uint16/int16/float32/float64 patterns");
+  int rc = check_patterns(c, "intensity rescaling");
+  if (rc) return rc;
   if (!intensity_dtype(a.dtype_out))
     return fail(KPDI_EINVAL, "dtype_out %d: intensity rescaling writes uint8/int8/uint16/int16/float32/float64", a.dtype_out);
   if (int_plan(c->exp_dtype, c->sy, c->sx, c->m_all).path < 0)
     return fail(KPDI_EINVAL, "intensity rescaling of %lld patterns of %d x %d: no kernel path takes this shape",
                 (long long)c->m_all, c->sy, c->sx);
-  int rc = use_device(c);
-  if (rc) return rc;
-  bool dummy = false;
-  rc = flush_preprocess(c, false, &dummy);  // recorded background-removal steps run first
+  rc = start_pattern_op(c);
   if (rc) return rc;
   const bool same = a.dtype_out == c->exp_dtype;
   if (!same) HIPCHK(c->int_out.reserve((size_t)c->m_all * c->npix * dtype_size(a.dtype_out)));
@@ -674,11 +663,7 @@ static int run_intensity(kpdi_ctx *c, IntLaunch &a) {
     std::swap(c->exp_raw, c->int_out);
     c->exp_dtype = a.dtype_out;
   }
-  // the resident patterns changed: what was prepared from them is stale
-  c->exp_prepared = false;
-  c->run_valid = false;
-  discard_pending(c);
-  c->final_valid = false;
+  patterns_changed(c);
   return KPDI_OK;
 }
 
@@ -722,15 +707,10 @@ int kpdi_normalize_intensity(kpdi_ctx *c, double num_std, int divide_by_square_r
 }
 
 int kpdi_intensity_range(kpdi_ctx *c, double *out) {
-  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
-  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
-  if (!out) return fail(KPDI_EINVAL, "out is NULL");
-  if (!kpdi::intensity_dtype(c->exp_dtype))
-    return fail(KPDI_EINVAL, "intensity rescaling takes uint8/int8/uint16/int16/float32/float64 patterns");
-  int rc = use_device(c);
+  int rc = kpdi::check_patterns(c, "intensity rescaling");
   if (rc) return rc;
-  bool dummy = false;
-  rc = flush_preprocess(c, false, &dummy);  // recorded background-removal steps run first
+  if (!out) return fail(KPDI_EINVAL, "out is NULL");
+  rc = kpdi::start_pattern_op(c);
   if (rc) return rc;
   HIPCHK(c->int_ws.reserve((3 * (size_t)kpdi::INT_RANGE_BLOCKS + 2) * sizeof(double)));
   double *ws = c->int_ws.as<double>();
@@ -741,10 +721,8 @@ int kpdi_intensity_range(kpdi_ctx *c, double *out) {
 }
 
 int kpdi_adaptive_histogram_equalization(kpdi_ctx *c, int ky, int kx, int clip_count, int nbins) {
-  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
-  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
-  if (!kpdi::intensity_dtype(c->exp_dtype))
-    return fail(KPDI_EINVAL, "adaptive histogram equalization takes uint8/int8/uint16/int16/float32/float64 patterns");
+  int rc = kpdi::check_patterns(c, "adaptive histogram equalization");
+  if (rc) return rc;
   if (ky < 1 || kx < 1) return fail(KPDI_EINVAL, "kernel of %d x %d", ky, kx);
   if (nbins < 1 || nbins > kpdi::CLAHE_MAX_NBINS) return fail(KPDI_EINVAL, "nbins %d outside [1, %d]", nbins, kpdi::CLAHE_MAX_NBINS);
   if (clip_count < 1) return fail(KPDI_EINVAL, "clip_count %d < 1", clip_count);
@@ -752,12 +730,9 @@ int kpdi_adaptive_histogram_equalization(kpdi_ctx *c, int ky, int kx, int clip_c
   if (plan.path < 0)
     return fail(KPDI_EINVAL, "adaptive histogram equalization of %d x %d patterns with a %d x %d kernel and %d bins: no kernel path takes this shape",
                 c->sy, c->sx, ky, kx, nbins);
-  int rc = use_device(c);
+  rc = kpdi::start_pattern_op(c);
   if (rc) return rc;
-  bool dummy = false;
-  rc = flush_preprocess(c, false, &dummy);  // recorded background-removal steps run first
-  if (rc) return rc;
-  if (plan.path == 1) HIPCHK(c->cl_ws.reserve(plan.workspace_bytes));
+  if (plan.path == 1) HIPCHK(c->op_ws.reserve(plan.workspace_bytes));
   kpdi::ClaheLaunch a{};
   a.patterns = c->exp_raw.p;
   a.dtype = c->exp_dtype;
@@ -772,17 +747,13 @@ int kpdi_adaptive_histogram_equalization(kpdi_ctx *c, int ky, int kx, int clip_c
   dtype_range(c->exp_dtype, &omin, &omax);
   a.omin = omin;
   a.omax = omax;
-  a.workspace = c->cl_ws.p;
-  a.workspace_bytes = c->cl_ws.cap;
+  a.workspace = c->op_ws.p;
+  a.workspace_bytes = c->op_ws.cap;
   hipError_t e = kpdi::launch_clahe(a, c->stream);
   if (e != hipSuccess)
     return fail(KPDI_EHIP, "adaptive histogram equalization kernel: %s (dtype %d, %dx%d)", hipGetErrorString(e),
                 c->exp_dtype, c->sy, c->sx);
-  // the resident patterns changed: what was prepared from them is stale
-  c->exp_prepared = false;
-  c->run_valid = false;
-  discard_pending(c);
-  c->final_valid = false;
+  patterns_changed(c);
   return KPDI_OK;
 }
 

@@ -368,15 +368,7 @@ hipError_t launch_clahe(const ClaheLaunch &a, hipStream_t s) {
   const ClahePlan pl = clahe_launch_plan(a.dtype, a.sy, a.sx, a.ky, a.kx, a.nbins, a.n);
   if (pl.path < 0 || !a.patterns || a.clip_count < 1) return hipErrorInvalidValue;
   if (pl.path == 1 && (!a.workspace || a.workspace_bytes < pl.workspace_bytes)) return hipErrorInvalidValue;
-  switch (a.dtype) {
-    case KPDI_U8: return launch_clahe_t<uint8_t>(a, pl, s);
-    case KPDI_I8: return launch_clahe_t<int8_t>(a, pl, s);
-    case KPDI_U16: return launch_clahe_t<uint16_t>(a, pl, s);
-    case KPDI_I16: return launch_clahe_t<int16_t>(a, pl, s);
-    case KPDI_F32: return launch_clahe_t<float>(a, pl, s);
-    case KPDI_F64: return launch_clahe_t<double>(a, pl, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_pattern_type(a.dtype, [&](auto t) { return launch_clahe_t<decltype(t)>(a, pl, s); });
 }
 
 }  // namespace kpdi

@@ -13,15 +13,7 @@
 //                       workspace stays under CLAHE_WS_CAP; beyond it there is no path.
 // Both paths do the same integer work per tile and the same per-pixel arithmetic, so they give the same bits.
 #pragma once
-#include <cstddef>
-#include <cstdint>
-
-// the layout helpers are evaluated by clahe.hip's kernel too
-#if defined(__HIPCC__) || defined(__HIP__)
-#define CLAHE_HD __host__ __device__
-#else
-#define CLAHE_HD
-#endif
+#include "pattern_plan.h"
 
 namespace kpdi {
 
@@ -43,22 +35,12 @@ struct ClahePlan {
   size_t workspace_bytes;  // path 1: slot_bytes * per_launch
 };
 
-inline int clahe_dtype_bytes(int dtype) {  // KPDI_U8, U16, F32, F64, I8, I16 = 0, 1, 2, 3, 4, 5
-  switch (dtype) {
-    case 0: case 4: return 1;
-    case 1: case 5: return 2;
-    case 2: return 4;
-    case 3: return 8;
-    default: return 0;
-  }
-}
-
-CLAHE_HD inline size_t clahe_align(size_t b) { return (b + 15) & ~(size_t)15; }
+PLAN_HD inline size_t clahe_align(size_t b) { return (b + 15) & ~(size_t)15; }
 
 // the LDS tables both paths keep: per detector row / column its interpolation block (int) and weight offset / k
 // (double); per row / column of the histogrammed region (nty * ky x ntx * kx, reflected past the pattern's end) the
 // detector row / column it reads and its tile (2 ints)
-CLAHE_HD inline size_t clahe_table_bytes(int sy, int sx, int nty, int ntx, int ky, int kx) {
+PLAN_HD inline size_t clahe_table_bytes(int sy, int sx, int nty, int ntx, int ky, int kx) {
   return clahe_align(((size_t)sy + sx) * (sizeof(int) + sizeof(double))) +
          clahe_align(((size_t)nty * ky + (size_t)ntx * kx) * 2 * sizeof(int));
 }
@@ -107,7 +89,7 @@ inline ClahePlan clahe_plan(int dtype, int sy, int sx, int ky, int kx, int nbins
   ClahePlan p{};
   p.path = -1;
   if (sy < 1 || sx < 1 || ky < 1 || kx < 1 || nbins < 1 || nbins > CLAHE_MAX_NBINS || n < 1 ||
-      n >= (int64_t)INT32_MAX || clahe_dtype_bytes(dtype) == 0)
+      n >= (int64_t)INT32_MAX || pattern_dtype_bytes(dtype) == 0)
     return p;
   if ((int64_t)sy * sx >= ((int64_t)1 << 30) || (int64_t)ky * kx >= ((int64_t)1 << 30) || ky >= (1 << 20) ||
       kx >= (1 << 20))

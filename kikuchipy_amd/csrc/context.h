@@ -33,6 +33,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace kpdi {
@@ -47,9 +48,21 @@ int fail(int code, const char *fmt, ...);
       return kpdi::fail(KPDI_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
+// device memory that grows on demand and is freed with its owner (move-only)
 struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr);
+      cap = std::exchange(o.cap, 0);
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     if (p) {
@@ -73,10 +86,21 @@ struct DevBuf {
 
 // page-locked host staging (results come back through it: a device-to-host copy into pageable
 // memory goes through the runtime's pin-on-the-fly path, measured at several ms per call and a
-// slower following sweep for a 40 000 x 20 result)
+// slower following sweep for a 40 000 x 20 result); freed with its owner (move-only)
 struct PinBuf {
   void *p = nullptr;
   size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(PinBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  PinBuf &operator=(PinBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr);
+      cap = std::exchange(o.cap, 0);
+    }
+    return *this;
+  }
+  ~PinBuf() { release(); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     release();
@@ -187,9 +211,9 @@ struct kpdi_ctx {
   int m = 0, m_pad = 0;
   bool have_nav_mask = false;
   kpdi::DevBuf exp_raw, row_map, exp_x;
-  kpdi::DevBuf iq_tab, iq_ws, iq_out;  // kpdi_image_quality: twiddles + folded weights, path-1 workspace, results
-  kpdi::DevBuf ff_tab, ff_ws;  // kpdi_fft_filter: twiddles + folded table (or the taps), path-1 workspace
-  kpdi::DevBuf cl_ws;  // kpdi_adaptive_histogram_equalization: path-1 workspace
+  // the per-pattern ops (image quality, FFT filter, CLAHE): host tables (twiddles + folded weights / transfer function,
+  // or the taps), their path-1 workspace, and the image quality results
+  kpdi::DevBuf op_tab, op_ws, iq_out;
   kpdi::DevBuf int_out, int_ws;  // kpdi_*_intensity: the patterns in a new dtype (swapped with exp_raw), range partials
 
   // dictionary chunk

@@ -9,9 +9,8 @@
 // host), an inverse column DFT, and a half-spectrum -> real inverse row DFT that counts twice every column whose mirror
 // is not stored (once l = 0 and, for even sx, l = sx/2).  The DFT runs on p - mean: a constant adds Hs(0, 0) times it
 // to every pixel, which the min / max rescale removes, and without it the other coefficients would carry the rounding of
-// partial sums as large as the pattern's.  Twiddles come from a host table of f32 cos / sin of 2 pi j / N (computed in
-// f64), indexed by the exact integer (k n) mod N, the sums run in f32 with explicit fmaf (this library builds with
-// -ffp-contract=off), and the rescale in f64: the reference's spectrum times a float64 transfer function is complex128.
+// partial sums as large as the pattern's.  The DFTs (pattern_dft.h) run in f32, the rescale in f64: the reference's
+// spectrum times a float64 transfer function is complex128.
 //
 // Spatial domain: Barnes' FFT convolution with its edge-replicating pad is a correlation with clamped indices centred
 // at (ty / 2, tx / 2) (scipy.ndimage.correlate(mode="nearest")).  It is evaluated directly, the taps wave-uniform
@@ -25,6 +24,7 @@
 #include "../../include/kpdi.h"
 #include "fftfilter_plan.h"
 #include "kernels.h"
+#include "pattern_dft.h"
 #include "prep_device.h"
 
 #include <algorithm>
@@ -35,47 +35,6 @@ namespace kpdi {
 namespace {
 
 constexpr int FF_WAVES = FF_THREADS / 64;
-
-// sum and non-finite flag of a pattern over the workgroup; every thread gets the result
-__device__ __forceinline__ void ff_block_sum_bad(double &s, int &bad, double *red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    s += __shfl_xor(s, o, 64);
-    bad |= __shfl_xor(bad, o, 64);
-  }
-  const int w = threadIdx.x >> 6;
-  __syncthreads();  // `red` may still be read from the previous use
-  if ((threadIdx.x & 63) == 0) {
-    red[2 * w] = s;
-    red[2 * w + 1] = bad;
-  }
-  __syncthreads();
-  s = 0;
-  bad = 0;
-  for (int i = 0; i < FF_WAVES; ++i) {
-    s += red[2 * i];
-    bad |= (int)red[2 * i + 1];
-  }
-}
-
-__device__ __forceinline__ void ff_block_minmax(float &mn, float &mx, double *red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, o, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  }
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-    red[2 * w] = mn;
-    red[2 * w + 1] = mx;
-  }
-  __syncthreads();
-  for (int i = 0; i < FF_WAVES; ++i) {
-    mn = fminf(mn, (float)red[2 * i]);
-    mx = fmaxf(mx, (float)red[2 * i + 1]);
-  }
-}
 
 // NaN before the cast -> 0 for integer dtypes, NaN for float dtypes; in-range values truncate as ndarray.astype
 template <typename T, typename V>
@@ -151,60 +110,9 @@ __device__ __forceinline__ void ff_load(const T *__restrict__ p, float *pat, int
   }
 }
 
-// forward row DFT of one detector row at column frequency l: sum_x (row(x) - mean) e^{-2 pi i l x / sx}
-template <typename Row>
-__device__ __forceinline__ float2 ff_row_dft(Row row, int sx, int l, float mean, const float2 *tw) {
-  float re = 0.f, im = 0.f;
-  int j = 0;
-#pragma unroll 4
-  for (int x = 0; x < sx; ++x) {
-    const float v = row(x) - mean;
-    const float2 t = tw[j];
-    re = fmaf(v, t.x, re);
-    im = fmaf(-v, t.y, im);
-    j += l;
-    j = j >= sx ? j - sx : j;
-  }
-  return make_float2(re, im);
-}
-
-// column DFT of the column `col` (stride h) at frequency k: sum_y col(y) e^{-+2 pi i k y / sy} (INV: +)
-template <bool INV>
-__device__ __forceinline__ float2 ff_col_dft(const float2 *col, int h, int sy, int k, const float2 *tw) {
-  float re = 0.f, im = 0.f;
-  int j = 0;
-#pragma unroll 4
-  for (int y = 0; y < sy; ++y) {
-    const float2 x = col[(size_t)y * h];
-    const float2 t = tw[j];
-    const float sn = INV ? t.y : -t.y;
-    re = fmaf(x.x, t.x, fmaf(-x.y, sn, re));
-    im = fmaf(x.y, t.x, fmaf(x.x, sn, im));
-    j += k;
-    j = j >= sy ? j - sy : j;
-  }
-  return make_float2(re, im);
-}
-
 __device__ __forceinline__ float2 ff_cmul(float2 a, float2 b) {
   return make_float2(fmaf(a.x, b.x, -a.y * b.y), fmaf(a.x, b.y, a.y * b.x));
 }
-
-// half spectrum -> real: sum_l Re(Y(l) e^{2 pi i l x / sx}) over the stored columns (the counts are folded into Y)
-__device__ __forceinline__ float ff_row_idft(const float2 *Y, int h, int sx, int x, const float2 *tw) {
-  float v = 0.f;
-  int j = 0;
-#pragma unroll 4
-  for (int l = 0; l < h; ++l) {
-    const float2 y = Y[l], t = tw[j];
-    v = fmaf(y.x, t.x, fmaf(-y.y, t.y, v));
-    j += x;
-    j = j >= sx ? j - sx : j;
-  }
-  return v;
-}
-
-__device__ __forceinline__ float ff_column_count(int l, int sx) { return (l == 0 || 2 * l == sx) ? 1.f : 2.f; }
 
 // spatial correlation with clamped indices at R vertically consecutive outputs (y0 .. y0 + R - 1, x) -> out[0 .. R-1];
 // `pix(i)` reads pixel i.  Sums over the kernel's columns v, then its rows u, in f64; along u the R outputs share a
@@ -243,7 +151,7 @@ __global__ __launch_bounds__(FF_THREADS) void ff_freq_lds_kernel(T *__restrict__
                                                                 const float2 *__restrict__ tw,
                                                                 const float2 *__restrict__ hs, float lo, float hi) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int h = sx / 2 + 1, npix = sy * sx, inter = sy * h, tid = threadIdx.x;
+  const int h = half_cols(sx), npix = sy * sx, inter = sy * h, tid = threadIdx.x;
   float *pat = (float *)smem;  // the pattern, then the filtered pattern
   float2 *X = (float2 *)(pat + ((npix + 3) & ~3));
   float2 *G = X + inter;
@@ -255,7 +163,7 @@ __global__ __launch_bounds__(FF_THREADS) void ff_freq_lds_kernel(T *__restrict__
   double s = 0;
   int bad = 0;
   ff_load(p, pat, npix, vec, s, bad);
-  ff_block_sum_bad(s, bad, red);  // (its barriers also publish `pat` and the twiddles)
+  block_reduce<FF_WAVES, RedSum, RedOr>(red, s, bad);  // (its barriers also publish `pat` and the twiddles)
   if (bad) {
     ff_store(p, pat, npix, FfRescale<double>(0.f, 0.f, lo, hi, 1), vec);
     return;
@@ -264,30 +172,30 @@ __global__ __launch_bounds__(FF_THREADS) void ff_freq_lds_kernel(T *__restrict__
   for (int o = tid; o < inter; o += FF_THREADS) {
     const int y = o / h, l = o - y * h;
     const float *row = pat + y * sx;
-    X[o] = ff_row_dft([row](int x) { return row[x]; }, sx, l, mean, twx);
+    X[o] = row_dft([row](int x) { return row[x]; }, sx, l, mean, twx);
   }
   __syncthreads();
   for (int o = tid; o < inter; o += FF_THREADS) {
     const int k = o / h, l = o - k * h;
-    G[o] = ff_cmul(ff_col_dft<false>(X + l, h, sy, k, twy), hs[o]);
+    G[o] = ff_cmul(col_dft<false>(X + l, h, sy, k, twy), hs[o]);
   }
   __syncthreads();
   for (int o = tid; o < inter; o += FF_THREADS) {
     const int y = o / h, l = o - y * h;
-    const float2 v = ff_col_dft<true>(G + l, h, sy, y, twy);
-    const float c = ff_column_count(l, sx);
+    const float2 v = col_dft<true>(G + l, h, sy, y, twy);
+    const float c = column_count<float>(l, sx);
     X[o] = make_float2(c * v.x, c * v.y);
   }
   __syncthreads();
   float mn = __builtin_inff(), mx = -__builtin_inff();
   for (int i = tid; i < npix; i += FF_THREADS) {
     const int y = i / sx, x = i - y * sx;
-    const float v = ff_row_idft(X + y * h, h, sx, x, twx);
+    const float v = row_idft(X + y * h, h, sx, x, twx);
     pat[i] = v;
     mn = fminf(mn, v);
     mx = fmaxf(mx, v);
   }
-  ff_block_minmax(mn, mx, red);  // (its barriers also publish `pat`)
+  block_reduce<FF_WAVES, RedMin, RedMax>(red, mn, mx);  // (its barriers also publish `pat`)
   ff_store(p, pat, npix, FfRescale<double>(mn, mx, lo, hi, 0), vec);
 }
 
@@ -305,7 +213,7 @@ __global__ __launch_bounds__(FF_THREADS) void ff_spatial_lds_kernel(T *__restric
   double s = 0;
   int bad = 0;
   ff_load(p, pat, npix, vec, s, bad);
-  ff_block_sum_bad(s, bad, red);
+  block_reduce<FF_WAVES, RedSum, RedOr>(red, s, bad);
   if (bad) {
     ff_store(p, res, npix, FfRescale<float>(0.f, 0.f, lo, hi, 1), vec);
     return;
@@ -324,7 +232,7 @@ __global__ __launch_bounds__(FF_THREADS) void ff_spatial_lds_kernel(T *__restric
         mx = fmaxf(mx, v[i]);
       }
   }
-  ff_block_minmax(mn, mx, red);
+  block_reduce<FF_WAVES, RedMin, RedMax>(red, mn, mx);
   ff_store(p, res, npix, FfRescale<float>(mn, mx, lo, hi, 0), vec);
 }
 
@@ -349,7 +257,7 @@ __global__ __launch_bounds__(FF_THREADS) void ff_stats_kernel(const T *__restric
     s += v;
     bad |= !isfinite(v);
   }
-  ff_block_sum_bad(s, bad, red);
+  block_reduce<FF_WAVES, RedSum, RedOr>(red, s, bad);
   if (threadIdx.x == 0) {
     ws.stats[2 * blockIdx.x] = (double)(float)(s / npix);
     ws.stats[2 * blockIdx.x + 1] = bad ? 1.0 : 0.0;
@@ -361,7 +269,7 @@ __global__ __launch_bounds__(FF_THREADS) void ff_rows_kernel(const T *__restrict
                                                             const float2 *__restrict__ tw, FfWs ws) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float2 *twx = (float2 *)smem;
-  const int h = sx / 2 + 1, inter = sy * h;
+  const int h = half_cols(sx), inter = sy * h;
   const int i = blockIdx.x / bpp, o = (blockIdx.x - i * bpp) * FF_THREADS + threadIdx.x;
   for (int j = threadIdx.x; j < sx; j += FF_THREADS) twx[j] = tw[j];
   __syncthreads();
@@ -369,7 +277,7 @@ __global__ __launch_bounds__(FF_THREADS) void ff_rows_kernel(const T *__restrict
   const float mean = (float)ws.stats[2 * i];
   const int y = o / h, l = o - y * h;
   const T *row = pats + (int64_t)i * sy * sx + (int64_t)y * sx;
-  ws.X[(int64_t)i * inter + o] = ff_row_dft([row](int x) { return (float)row[x]; }, sx, l, mean, twx);
+  ws.X[(int64_t)i * inter + o] = row_dft([row](int x) { return (float)row[x]; }, sx, l, mean, twx);
 }
 
 // INV = false: G = DFT_col(X) * Hs; INV = true: X = count * IDFT_col(G)
@@ -378,17 +286,17 @@ __global__ __launch_bounds__(FF_THREADS) void ff_cols_kernel(int sy, int sx, int
                                                             const float2 *__restrict__ hs, FfWs ws) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float2 *twy = (float2 *)smem;
-  const int h = sx / 2 + 1, inter = sy * h;
+  const int h = half_cols(sx), inter = sy * h;
   const int i = blockIdx.x / bpp, o = (blockIdx.x - i * bpp) * FF_THREADS + threadIdx.x;
   for (int j = threadIdx.x; j < sy; j += FF_THREADS) twy[j] = tw[sx + j];
   __syncthreads();
   if (o >= inter || ws.stats[2 * i + 1] != 0.0) return;
   const int k = o / h, l = o - k * h;
   if (!INV) {
-    ws.G[(int64_t)i * inter + o] = ff_cmul(ff_col_dft<false>(ws.X + (int64_t)i * inter + l, h, sy, k, twy), hs[o]);
+    ws.G[(int64_t)i * inter + o] = ff_cmul(col_dft<false>(ws.X + (int64_t)i * inter + l, h, sy, k, twy), hs[o]);
   } else {
-    const float2 v = ff_col_dft<true>(ws.G + (int64_t)i * inter + l, h, sy, k, twy);
-    const float c = ff_column_count(l, sx);
+    const float2 v = col_dft<true>(ws.G + (int64_t)i * inter + l, h, sy, k, twy);
+    const float c = column_count<float>(l, sx);
     ws.X[(int64_t)i * inter + o] = make_float2(c * v.x, c * v.y);
   }
 }
@@ -397,13 +305,13 @@ __global__ __launch_bounds__(FF_THREADS) void ff_irows_kernel(int sy, int sx, in
                                                              FfWs ws) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float2 *twx = (float2 *)smem;
-  const int h = sx / 2 + 1, inter = sy * h, npix = sy * sx;
+  const int h = half_cols(sx), inter = sy * h, npix = sy * sx;
   const int i = blockIdx.x / bpp, o = (blockIdx.x - i * bpp) * FF_THREADS + threadIdx.x;
   for (int j = threadIdx.x; j < sx; j += FF_THREADS) twx[j] = tw[j];
   __syncthreads();
   if (o >= npix || ws.stats[2 * i + 1] != 0.0) return;
   const int y = o / sx, x = o - y * sx;
-  ws.R[i * ws.rstride + o] = ff_row_idft(ws.X + (int64_t)i * inter + (int64_t)y * h, h, sx, x, twx);
+  ws.R[i * ws.rstride + o] = row_idft(ws.X + (int64_t)i * inter + (int64_t)y * h, h, sx, x, twx);
 }
 
 template <typename T>
@@ -432,7 +340,7 @@ __global__ __launch_bounds__(FF_THREADS) void ff_epilogue_kernel(T *__restrict__
       mn = fminf(mn, r[i]);
       mx = fmaxf(mx, r[i]);
     }
-  ff_block_minmax(mn, mx, red);
+  block_reduce<FF_WAVES, RedMin, RedMax>(red, mn, mx);
   ff_store(p, r, npix, FfRescale<V>(mn, mx, lo, hi, bad), ff_vec(p, npix));
 }
 
@@ -457,7 +365,7 @@ hipError_t launch_ff_t(const FfLaunch &a, const FfPlan &plan, hipStream_t s) {
     return hipGetLastError();
   }
   if (!a.workspace || a.workspace_bytes < plan.workspace_bytes) return hipErrorInvalidValue;
-  const int64_t inter = (int64_t)a.sy * ff_half_cols(a.sx), npix = (int64_t)a.sy * a.sx;
+  const int64_t inter = (int64_t)a.sy * half_cols(a.sx), npix = (int64_t)a.sy * a.sx;
   FfWs ws;
   if (freq) {
     ws.X = (float2 *)a.workspace;
@@ -509,15 +417,7 @@ hipError_t launch_fft_filter(const FfLaunch &a, hipStream_t s) {
     return hipErrorInvalidValue;
   if (a.domain == FF_DOMAIN_FREQUENCY ? (!a.table || !a.twiddles) : (!a.taps || a.ty < 1 || a.tx < 1))
     return hipErrorInvalidValue;
-  switch (a.dtype) {
-    case KPDI_U8: return launch_ff_t<uint8_t>(a, plan, s);
-    case KPDI_I8: return launch_ff_t<int8_t>(a, plan, s);
-    case KPDI_U16: return launch_ff_t<uint16_t>(a, plan, s);
-    case KPDI_I16: return launch_ff_t<int16_t>(a, plan, s);
-    case KPDI_F32: return launch_ff_t<float>(a, plan, s);
-    case KPDI_F64: return launch_ff_t<double>(a, plan, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_pattern_type(a.dtype, [&](auto t) { return launch_ff_t<decltype(t)>(a, plan, s); });
 }
 
 }  // namespace kpdi

@@ -8,37 +8,29 @@
 //   path 1 (workspace): the intermediates go to a device workspace; a few kernels per batch of patterns, each spread
 //                       over many workgroups per pattern (frequency: statistics, row DFT, column DFT x table, inverse
 //                       column DFT, inverse row DFT, epilogue; spatial: statistics, correlation, epilogue).  A batch
-//                       holds as many patterns as FF_WORKSPACE_CAP admits (1024 x 1024 in the frequency domain needs
+//                       holds as many patterns as PATTERN_WORKSPACE_CAP admits (1024 x 1024 in the frequency domain needs
 //                       8.4 MB per pattern).
 #pragma once
-#include <cstddef>
-#include <cstdint>
+#include "pattern_plan.h"
 
 namespace kpdi {
 
 constexpr int FF_THREADS = 256;
 constexpr int FF_DOMAIN_FREQUENCY = 0, FF_DOMAIN_SPATIAL = 1;  // = KPDI_DOMAIN_FREQUENCY / KPDI_DOMAIN_SPATIAL
-constexpr size_t FF_LDS_CAP = 150 * 1024;                    // of the 160 KiB per CU, as the other per-pattern kernels
-constexpr size_t FF_WORKSPACE_CAP = (size_t)256 << 20;       // path 1: intermediates + statistics of one batch
 constexpr size_t FF_RED_BYTES = 4 * (FF_THREADS / 64) * 8;   // block reductions: 4 doubles per wave
 
-struct FfPlan {
-  int path;                // 0 LDS, 1 workspace, -1 no path takes the shape
-  size_t lds_bytes;        // dynamic LDS per workgroup
-  int64_t batch;           // path 1: patterns per batch of launches
-  int blocks_half;         // path 1: workgroups per pattern over the sy x (sx/2 + 1) half spectrum
-  int blocks_pix;          // path 1: workgroups per pattern over the sy x sx pixels
-  size_t workspace_bytes;  // path 1: what one batch needs (<= FF_WORKSPACE_CAP)
+struct FfPlan : PatternPath {
+  int blocks_half;  // path 1: workgroups per pattern over the sy x (sx/2 + 1) half spectrum
+  int blocks_pix;   // path 1: workgroups per pattern over the sy x sx pixels
 };
 
-inline int ff_half_cols(int sx) { return sx / 2 + 1; }
 inline size_t ff_pix4(int sy, int sx) { return ((size_t)sy * sx + 3) & ~(size_t)3; }
 
 // path 0, frequency: pattern / result (f32, padded to quads) + two intermediates (float2) + twiddles (float2) + reduction
 // path 0, spatial:   pattern (f32) + result (f32) + reduction
 inline size_t ff_lds_path_bytes(int domain, int sy, int sx) {
   if (domain == FF_DOMAIN_SPATIAL) return 2 * ff_pix4(sy, sx) * 4 + FF_RED_BYTES;
-  const size_t inter = (size_t)sy * ff_half_cols(sx);
+  const size_t inter = (size_t)sy * half_cols(sx);
   return ff_pix4(sy, sx) * 4 + 2 * inter * 8 + ((size_t)sx + sy) * 8 + FF_RED_BYTES;
 }
 
@@ -46,7 +38,7 @@ inline size_t ff_lds_path_bytes(int domain, int sy, int sx) {
 // statistics (2 doubles: mean, non-finite)
 inline size_t ff_ws_pattern_bytes(int domain, int sy, int sx) {
   if (domain == FF_DOMAIN_SPATIAL) return ff_pix4(sy, sx) * 4 + 2 * 8;
-  return 2 * (size_t)sy * ff_half_cols(sx) * 8 + 2 * 8;
+  return 2 * (size_t)sy * half_cols(sx) * 8 + 2 * 8;
 }
 
 // path 1 LDS: the twiddles of the longer axis + the reduction
@@ -54,31 +46,13 @@ inline size_t ff_ws_lds_bytes(int sy, int sx) { return (size_t)(sx > sy ? sx : s
 
 // `n` patterns of sy x sx
 inline FfPlan ff_plan(int domain, int sy, int sx, int64_t n) {
-  FfPlan p{};
-  if (sy < 1 || sx < 1 || n < 1 || (domain != FF_DOMAIN_FREQUENCY && domain != FF_DOMAIN_SPATIAL)) {
-    p.path = -1;
-    return p;
+  if (sy < 1 || sx < 1 || n < 1 || (domain != FF_DOMAIN_FREQUENCY && domain != FF_DOMAIN_SPATIAL)) return FfPlan{{-1}};
+  FfPlan p{pattern_path(ff_lds_path_bytes(domain, sy, sx), ff_ws_lds_bytes(sy, sx), ff_ws_pattern_bytes(domain, sy, sx), n)};
+  if (p.path == 1) {
+    const size_t inter = (size_t)sy * half_cols(sx), npix = (size_t)sy * sx;
+    p.blocks_half = (int)((inter + FF_THREADS - 1) / FF_THREADS);
+    p.blocks_pix = (int)((npix + FF_THREADS - 1) / FF_THREADS);
   }
-  const size_t lds = ff_lds_path_bytes(domain, sy, sx);
-  if (lds <= FF_LDS_CAP) {
-    p.path = 0;
-    p.lds_bytes = lds;
-    p.batch = n;
-    return p;
-  }
-  const size_t per = ff_ws_pattern_bytes(domain, sy, sx);
-  p.lds_bytes = ff_ws_lds_bytes(sy, sx);
-  if (per > FF_WORKSPACE_CAP || p.lds_bytes > FF_LDS_CAP) {
-    p.path = -1;
-    return p;
-  }
-  p.path = 1;
-  const int64_t fit = (int64_t)(FF_WORKSPACE_CAP / per);
-  p.batch = n < fit ? n : fit;
-  const size_t inter = (size_t)sy * ff_half_cols(sx), npix = (size_t)sy * sx;
-  p.blocks_half = (int)((inter + FF_THREADS - 1) / FF_THREADS);
-  p.blocks_pix = (int)((npix + FF_THREADS - 1) / FF_THREADS);
-  p.workspace_bytes = (size_t)p.batch * per;
   return p;
 }
 

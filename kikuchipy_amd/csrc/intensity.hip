@@ -474,33 +474,17 @@ hipError_t launch_range_t(const void *src, int64_t count, double *partial, doubl
 hipError_t launch_intensity(const IntLaunch &a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   const IntPlan plan = int_plan(a.dtype, a.sy, a.sx, a.n);
-  if (plan.path < 0 || int_dtype_bytes(a.dtype_out) == 0 || !a.src || !a.dst) return hipErrorInvalidValue;
+  if (plan.path < 0 || pattern_dtype_bytes(a.dtype_out) == 0 || !a.src || !a.dst) return hipErrorInvalidValue;
   if (a.dst == a.src && a.dtype_out != a.dtype) return hipErrorInvalidValue;  // only the same dtype works in place
   int path = plan.path;
   if (const char *e = getenv("KPDI_INTENSITY_PATH")) path = atoi(e) == 1 ? 1 : path;  // tests: path 1 for any shape
-  switch (a.dtype) {
-    case KPDI_U8: return launch_int_t<uint8_t>(a, path, plan.lds_bytes, s);
-    case KPDI_I8: return launch_int_t<int8_t>(a, path, plan.lds_bytes, s);
-    case KPDI_U16: return launch_int_t<uint16_t>(a, path, plan.lds_bytes, s);
-    case KPDI_I16: return launch_int_t<int16_t>(a, path, plan.lds_bytes, s);
-    case KPDI_F32: return launch_int_t<float>(a, path, plan.lds_bytes, s);
-    case KPDI_F64: return launch_int_t<double>(a, path, plan.lds_bytes, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_pattern_type(a.dtype, [&](auto t) { return launch_int_t<decltype(t)>(a, path, plan.lds_bytes, s); });
 }
 
 hipError_t launch_intensity_range(const void *src, int dtype, int64_t count, double *partial, double *out,
                                   hipStream_t s) {
   if (count <= 0 || !src || !partial || !out) return hipErrorInvalidValue;
-  switch (dtype) {
-    case KPDI_U8: return launch_range_t<uint8_t>(src, count, partial, out, s);
-    case KPDI_I8: return launch_range_t<int8_t>(src, count, partial, out, s);
-    case KPDI_U16: return launch_range_t<uint16_t>(src, count, partial, out, s);
-    case KPDI_I16: return launch_range_t<int16_t>(src, count, partial, out, s);
-    case KPDI_F32: return launch_range_t<float>(src, count, partial, out, s);
-    case KPDI_F64: return launch_range_t<double>(src, count, partial, out, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_pattern_type(dtype, [&](auto t) { return launch_range_t<decltype(t)>(src, count, partial, out, s); });
 }
 
 }  // namespace kpdi

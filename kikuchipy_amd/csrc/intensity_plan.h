@@ -10,8 +10,7 @@
 // Both paths visit the pixels in the same order (thread t takes the quads t, t + INT_THREADS, ...), so their
 // reductions, and so their results, are bit-identical.
 #pragma once
-#include <cstddef>
-#include <cstdint>
+#include "pattern_plan.h"
 
 namespace kpdi {
 
@@ -26,24 +25,13 @@ struct IntPlan {
   int select_passes; // radix-select passes of 8 bits for percentiles: 1 (8-bit), 2 (16-bit), 4 (f32), 8 (f64)
 };
 
-// bytes of an element of the dtypes this path takes (KPDI_U8, U16, F32, F64, I8, I16 = 0, 1, 2, 3, 4, 5), 0 otherwise
-inline int int_dtype_bytes(int dtype) {
-  switch (dtype) {
-    case 0: case 4: return 1;
-    case 1: case 5: return 2;
-    case 2: return 4;
-    case 3: return 8;
-    default: return 0;
-  }
-}
-
 inline size_t int_staged_bytes(int dtype, int sy, int sx) {
-  return ((size_t)sy * sx * int_dtype_bytes(dtype) + 15) & ~(size_t)15;
+  return ((size_t)sy * sx * pattern_dtype_bytes(dtype) + 15) & ~(size_t)15;
 }
 
 inline IntPlan int_plan(int dtype, int sy, int sx, int64_t n) {
   IntPlan p{};
-  const int es = int_dtype_bytes(dtype);
+  const int es = pattern_dtype_bytes(dtype);
   if (sy < 1 || sx < 1 || n < 1 || es == 0 || (int64_t)sy * sx >= ((int64_t)1 << 30) || n >= (int64_t)INT32_MAX) {
     p.path = -1;
     return p;

@@ -7,16 +7,15 @@
 // F(0, 0) alone, so without `normalize` |F(0, 0)| is the pattern's f64 sum instead, and the other coefficients do not
 // carry the rounding of partial sums as large as the whole pattern's.
 //
-// Half-spectrum DFT: p is real, so |F(k, l)| = |F(-k, -l)|.  Only the columns l = 0 ... sx/2 are transformed: a row DFT
-// of length sx for those columns, then a column DFT of length sy over all k.  The host folds the weights
+// Half-spectrum DFT (pattern_dft.h): p is real, so |F(k, l)| = |F(-k, -l)|.  The host folds the weights
 // (W(k, l) = w(k, l) + w(-k, -l) for the columns whose mirror is not computed, else w(k, l)) and the count c(l) (2 or 1)
-// is applied to S here, so inertia = sum W S / sum c S is the full-spectrum sum exactly.  Twiddles come from a host table
-// of f32 cos / sin of 2 pi j / N (computed in f64), indexed by the exact integer (k n) mod N.  Sums of the DFT run in
-// f32 (explicit fmaf: this library builds with -ffp-contract=off), per-pattern statistics and the weighted sums in f64.
+// is applied to S here, so inertia = sum W S / sum c S is the full-spectrum sum exactly.  Sums of the DFT run in f32,
+// per-pattern statistics and the weighted sums in f64.
 // Which path takes a shape: iq_plan.h.
 #include "../../include/kpdi.h"
 #include "iq_plan.h"
 #include "kernels.h"
+#include "pattern_dft.h"
 
 namespace kpdi {
 
@@ -26,57 +25,6 @@ constexpr int IQ_WAVES = IQ_THREADS / 64;
 
 template <typename T>
 __device__ __forceinline__ float as_f32(T v) { return (float)v; }
-
-// the four statistics of a pattern, reduced over the workgroup; every thread gets the result
-__device__ __forceinline__ void block_stats(double &s, float &lo, float &hi, int &bad, double *red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    s += __shfl_xor(s, o, 64);
-    lo = fminf(lo, __shfl_xor(lo, o, 64));
-    hi = fmaxf(hi, __shfl_xor(hi, o, 64));
-    bad |= __shfl_xor(bad, o, 64);
-  }
-  const int w = threadIdx.x >> 6;
-  __syncthreads();  // `red` may still be read from the previous use
-  if ((threadIdx.x & 63) == 0) {
-    red[4 * w] = s;
-    red[4 * w + 1] = lo;
-    red[4 * w + 2] = hi;
-    red[4 * w + 3] = bad;
-  }
-  __syncthreads();
-  s = 0;
-  lo = __builtin_inff();
-  hi = -__builtin_inff();
-  bad = 0;
-  for (int i = 0; i < IQ_WAVES; ++i) {
-    s += red[4 * i];
-    lo = fminf(lo, (float)red[4 * i + 1]);
-    hi = fmaxf(hi, (float)red[4 * i + 2]);
-    bad |= (int)red[4 * i + 3];
-  }
-}
-
-__device__ __forceinline__ void block_sum2(double &a, double &b, double *red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-  }
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-    red[2 * w] = a;
-    red[2 * w + 1] = b;
-  }
-  __syncthreads();
-  a = 0;
-  b = 0;
-  for (int i = 0; i < IQ_WAVES; ++i) {
-    a += red[2 * i];
-    b += red[2 * i + 1];
-  }
-}
 
 // the value, the pattern statistics of one thread's pixels
 template <typename T>
@@ -88,40 +36,11 @@ __device__ __forceinline__ void stat_one(T raw, double &s, float &lo, float &hi,
   bad |= !isfinite(v);
 }
 
-// row DFT of one detector row at column frequency l: sum_x (row(x) - mean) e^{-2 pi i l x / sx}
-template <typename Row>
-__device__ __forceinline__ float2 row_dft(Row row, int sx, int l, float mean, const float2 *tw) {
-  float re = 0.f, im = 0.f;
-  int j = 0;
-#pragma unroll 4
-  for (int x = 0; x < sx; ++x) {
-    const float v = row(x) - mean;
-    const float2 t = tw[j];
-    re = fmaf(v, t.x, re);
-    im = fmaf(-v, t.y, im);
-    j += l;
-    j = j >= sx ? j - sx : j;
-  }
-  return make_float2(re, im);
-}
-
-// column DFT of the intermediate column `col` (stride h) at row frequency k, returned as |F(k, l)|
+// |F(k, l)| of the intermediate column `col` (pattern_dft.h)
 __device__ __forceinline__ float col_dft_abs(const float2 *col, int h, int sy, int k, const float2 *tw) {
-  float re = 0.f, im = 0.f;
-  int j = 0;
-#pragma unroll 4
-  for (int y = 0; y < sy; ++y) {
-    const float2 x = col[(size_t)y * h];
-    const float2 t = tw[j];
-    re = fmaf(x.x, t.x, fmaf(x.y, t.y, re));
-    im = fmaf(x.y, t.x, fmaf(-x.x, t.y, im));
-    j += k;
-    j = j >= sy ? j - sy : j;
-  }
-  return sqrtf(re * re + im * im);
+  const float2 f = col_dft<false>(col, h, sy, k, tw);
+  return sqrtf(f.x * f.x + f.y * f.y);
 }
-
-__device__ __forceinline__ double column_count(int l, int sx) { return (l == 0 || 2 * l == sx) ? 1.0 : 2.0; }
 
 // ---- path 0: one workgroup per pattern, everything in LDS ----------------------------------------------------------
 template <typename T>
@@ -129,7 +48,7 @@ __global__ __launch_bounds__(IQ_THREADS) void iq_lds_kernel(const T *__restrict_
                                                            const float2 *__restrict__ tw, const double *__restrict__ wfold,
                                                            double inertia_max, float *__restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int h = sx / 2 + 1, npix = sy * sx, inter = sy * h, tid = threadIdx.x;
+  const int h = half_cols(sx), npix = sy * sx, inter = sy * h, tid = threadIdx.x;
   float2 *X = (float2 *)smem;
   float2 *twx = X + inter, *twy = twx + sx;
   double *red = (double *)(twy + sy);
@@ -143,7 +62,7 @@ __global__ __launch_bounds__(IQ_THREADS) void iq_lds_kernel(const T *__restrict_
     stat_one(p[i], s, lo, hi, bad);
     pat[i] = as_f32(p[i]);
   }
-  block_stats(s, lo, hi, bad, red);  // (its barriers also publish `pat` and the twiddles)
+  block_reduce<IQ_WAVES, RedSum, RedMin, RedMax, RedOr>(red, s, lo, hi, bad);  // (its barriers also publish `pat` and the twiddles)
   if (bad || (normalize && lo == hi)) {
     if (tid == 0) out[blockIdx.x] = __builtin_nanf("");
     return;
@@ -161,9 +80,9 @@ __global__ __launch_bounds__(IQ_THREADS) void iq_lds_kernel(const T *__restrict_
     const float f = col_dft_abs(X + l, h, sy, k, twy);
     const double a = (o == 0 && !normalize) ? fabs(s) : (double)f;
     sw += wfold[o] * a;
-    ss += column_count(l, sx) * a;
+    ss += column_count<double>(l, sx) * a;
   }
-  block_sum2(sw, ss, red);
+  block_reduce<IQ_WAVES, RedSum, RedSum>(red, sw, ss);
   if (tid == 0) out[blockIdx.x] = (float)(1.0 - (sw / ss) / inertia_max);
 }
 
@@ -183,7 +102,7 @@ __global__ __launch_bounds__(IQ_THREADS) void iq_stats_kernel(const T *__restric
   float lo = __builtin_inff(), hi = -__builtin_inff();
   int bad = 0;
   for (int i = threadIdx.x; i < npix; i += IQ_THREADS) stat_one(p[i], s, lo, hi, bad);
-  block_stats(s, lo, hi, bad, red);
+  block_reduce<IQ_WAVES, RedSum, RedMin, RedMax, RedOr>(red, s, lo, hi, bad);
   if (threadIdx.x == 0) {
     ws.stats[3 * blockIdx.x] = (double)(float)(s / npix);
     ws.stats[3 * blockIdx.x + 1] = (bad || (normalize && lo == hi)) ? 1.0 : 0.0;
@@ -196,7 +115,7 @@ __global__ __launch_bounds__(IQ_THREADS) void iq_rows_kernel(const T *__restrict
                                                             const float2 *__restrict__ tw, IqWs ws) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float2 *twx = (float2 *)smem;
-  const int h = sx / 2 + 1, inter = sy * h;
+  const int h = half_cols(sx), inter = sy * h;
   const int i = blockIdx.x / bpp, o = (blockIdx.x - i * bpp) * IQ_THREADS + threadIdx.x;
   for (int j = threadIdx.x; j < sx; j += IQ_THREADS) twx[j] = tw[j];
   __syncthreads();
@@ -212,7 +131,7 @@ __global__ __launch_bounds__(IQ_THREADS) void iq_cols_kernel(int sy, int sx, int
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float2 *twy = (float2 *)smem;
   double *red = (double *)(twy + sy);
-  const int h = sx / 2 + 1, inter = sy * h;
+  const int h = half_cols(sx), inter = sy * h;
   const int i = blockIdx.x / bpp, b = blockIdx.x - i * bpp, o = b * IQ_THREADS + threadIdx.x;
   for (int j = threadIdx.x; j < sy; j += IQ_THREADS) twy[j] = tw[sx + j];
   __syncthreads();
@@ -223,9 +142,9 @@ __global__ __launch_bounds__(IQ_THREADS) void iq_cols_kernel(int sy, int sx, int
     const float f = col_dft_abs(ws.X + (int64_t)i * inter + l, h, sy, k, twy);
     const double a = (o == 0 && !normalize) ? fabs(ws.stats[3 * i + 2]) : (double)f;
     sw = wfold[o] * a;
-    ss = column_count(l, sx) * a;
+    ss = column_count<double>(l, sx) * a;
   }
-  block_sum2(sw, ss, red);
+  block_reduce<IQ_WAVES, RedSum, RedSum>(red, sw, ss);
   if (threadIdx.x == 0) {
     ws.partial[2 * ((int64_t)i * bpp + b)] = sw;
     ws.partial[2 * ((int64_t)i * bpp + b) + 1] = ss;
@@ -262,7 +181,7 @@ hipError_t launch_iq_t(const IqLaunch &a, const IqPlan &plan, hipStream_t s) {
     return hipGetLastError();
   }
   if (!a.workspace || a.workspace_bytes < plan.workspace_bytes) return hipErrorInvalidValue;
-  const int64_t inter = (int64_t)a.sy * iq_half_cols(a.sx), npix = (int64_t)a.sy * a.sx;
+  const int64_t inter = (int64_t)a.sy * half_cols(a.sx), npix = (int64_t)a.sy * a.sx;
   const int bpp = plan.blocks_per_pattern;
   IqWs ws;
   ws.X = (float2 *)a.workspace;
@@ -292,15 +211,7 @@ hipError_t launch_image_quality(const IqLaunch &a, hipStream_t s) {
   if (plan.path < 0 || (plan.path == 0 && a.n >= (int64_t)INT32_MAX) ||
       (plan.path == 1 && plan.batch * plan.blocks_per_pattern >= (int64_t)INT32_MAX))
     return hipErrorInvalidValue;
-  switch (a.dtype) {
-    case KPDI_U8: return launch_iq_t<uint8_t>(a, plan, s);
-    case KPDI_I8: return launch_iq_t<int8_t>(a, plan, s);
-    case KPDI_U16: return launch_iq_t<uint16_t>(a, plan, s);
-    case KPDI_I16: return launch_iq_t<int16_t>(a, plan, s);
-    case KPDI_F32: return launch_iq_t<float>(a, plan, s);
-    case KPDI_F64: return launch_iq_t<double>(a, plan, s);
-    default: return hipErrorInvalidValue;
-  }
+  return with_pattern_type(a.dtype, [&](auto t) { return launch_iq_t<decltype(t)>(a, plan, s); });
 }
 
 }  // namespace kpdi

@@ -335,6 +335,20 @@ hipError_t launch_nelder_mead_selftest(int kind, int nvar, const double *x0, con
 hipError_t launch_osm(const int *idx, int ny, int nx, int keep_n, int n_best, int from_n_best, const int *offsets,
                       int n_fp, int center_index, int normalize, float *out, hipStream_t s);
 
+// ---- the per-pattern pre-processing ops (iq.hip, fftfilter.hip, intensity.hip, clahe.hip) ----------------------
+// launch(T{}) with T the element type of one of the six pattern dtypes (pattern_plan.h); any other dtype is refused
+template <typename Launch>
+hipError_t with_pattern_type(int dtype, Launch launch) {
+  switch (dtype) {
+    case KPDI_U8: return launch(uint8_t{});
+    case KPDI_I8: return launch(int8_t{});
+    case KPDI_U16: return launch(uint16_t{});
+    case KPDI_I16: return launch(int16_t{});
+    case KPDI_F32: return launch(float{});
+    case KPDI_F64: return launch(double{});
+    default: return hipErrorInvalidValue;
+  }
+}
 
 // ---- image quality (iq.hip) -----------------------------------------------------
 struct IqLaunch {

@@ -841,7 +841,6 @@ void release_held(kpdi_ctx *c) {
   if (c->held.empty()) return;
   (void)hipStreamSynchronize(c->stream);
   if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-  for (auto &h : c->held) h.y.release();
   c->held.clear();
 }
 
@@ -959,7 +958,6 @@ int kpdi_hold_dictionary_chunk(kpdi_ctx *c, const void *patterns, int dtype, int
                      });
   if (rc) {
     (void)hipStreamSynchronize(c->stream);
-    c->held.back().y.release();
     c->held.pop_back();
   }
   return rc;
