@@ -234,6 +234,37 @@ int kpdi_intensity_range(kpdi_ctx *ctx, double *out);
  * paths: csrc/clahe.hip, csrc/clahe_plan.h.  KPDI_EINVAL where no path takes the shape, kernel and bins. */
 int kpdi_adaptive_histogram_equalization(kpdi_ctx *ctx, int ky, int kx, int clip_count, int nbins);
 
+/* ---- neighbour pattern averaging and neighbour dot products (EBSD.average_neighbour_patterns, signals/ebsd.py:943-1111,
+ * pattern/chunk.py:130-164; EBSD.get_neighbour_dot_product_matrices / get_average_neighbour_dot_product_map,
+ * signals/ebsd.py:1221-1491, signals/util/_map_helper.py) --------------------------------------------------------------
+ * The two ops whose result at a map point depends on the patterns around it.  The resident patterns are taken as a map
+ * of `ny` rows of `nx` points, row-major, ny * nx = the resident pattern count (a 1-D map: nx = 1 and a window of
+ * wy x 1); the navigation mask is ignored; both run AFTER the recorded background steps.  The window has `wy` x `wx`
+ * entries with its origin at (wy / 2, wx / 2), also for even sizes; a neighbour outside the map does not exist (it adds
+ * 0 to an average and is NaN in a dot product matrix).  Output is produced for the rows [row0, row1) only; the other
+ * resident rows serve as neighbours, so that a map can be split by rows over several contexts, each holding its rows
+ * plus a halo of wy / 2 rows above and wy - wy / 2 - 1 below (clipped at the map's edge) - the results then equal
+ * those of one context bit for bit.  Errors are KPDI_EINVAL before any launch.  Kernels: csrc/neighbours.hip.
+ * kpdi_average_neighbour_patterns: per point q, c = float32(sum_j window[j] * float32(p_{q+j})) accumulated in float64
+ *   over the non-zero coefficients in C order; a = float64(c) / window_sums[q]; the pattern (a - min a) / (max a -
+ *   min a) * (omax - omin) + omin in float64 with the dtype's range, truncated (integer dtypes) or rounded (float
+ *   dtypes) to the patterns' dtype, which stays.  `window_sums`: ny * nx integers, the reference's truncated window sum
+ *   of every resident point, computed by the caller from the WHOLE map (never from the rows held here); 0 for a point
+ *   in [row0, row1) is refused.  A constant averaged pattern becomes 0 (integer dtypes) or NaN (float dtypes), as in
+ *   kpdi_rescale_intensity.  The averaged patterns replace the resident ones (rows outside [row0, row1) keep theirs)
+ *   and prepared rows made before the call are invalidated.
+ * kpdi_neighbour_dot_products: `footprint`: wy * wx bytes, non-zero = the neighbour takes part; it must be true at its
+ *   origin.  Every pattern as float64, minus its mean (`zero_mean`), divided by sqrt(sum x^2) (`normalize`, after the
+ *   centring); dp[q, j] = x_{q+j} . x_q, accumulated in float64.  `matrices_out` (or NULL): (row1 - row0) * nx * wy * wx
+ *   values, NaN where the footprint is false or the neighbour is outside the map, sum x_q^2 at the origin; `map_out`
+ *   (or NULL): (row1 - row0) * nx values, the mean of the point's non-NaN dot products with its neighbours, NaN without
+ *   any.  Both are float64 for `f64`, else float32, and come from the same launch.  A pattern of zero norm under
+ *   `normalize` or one holding a NaN gives NaN dot products.  The patterns are only read. */
+int kpdi_average_neighbour_patterns(kpdi_ctx *ctx, int ny, int nx, const double *window, int wy, int wx,
+                                    const int64_t *window_sums, int row0, int row1);
+int kpdi_neighbour_dot_products(kpdi_ctx *ctx, int ny, int nx, const uint8_t *footprint, int wy, int wx, int zero_mean,
+                                int normalize, int f64, int row0, int row1, void *matrices_out, void *map_out);
+
 /* ---- dictionary sweep (_dictionary_indexing loop, indexing/_dictionary_indexing.py:94-128)
  * One call = one loop iteration: prepare_dictionary (cast, mask, normalise) +
  * match + top-k of the chunk + merge into the running best-k, all on the GPU.

@@ -137,6 +137,8 @@ SIGNATURES = {
     "kpdi_normalize_intensity": (_i, [_vp, C.c_double, _i, _i]),
     "kpdi_intensity_range": (_i, [_vp, _vp]),
     "kpdi_adaptive_histogram_equalization": (_i, [_vp, _i, _i, _i, _i]),
+    "kpdi_average_neighbour_patterns": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i]),
+    "kpdi_neighbour_dot_products": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "kpdi_push_dictionary_chunk": (_i, [_vp, _vp, _i, _i64, _i64]),
     "kpdi_push_dictionary_chunk_dev": (_i, [_vp, _vp, _i, _i64, _i64]),
     "kpdi_set_master_pattern": (_i, [_vp, _vp, _vp, _i, _i, _i]),
@@ -497,6 +499,40 @@ class Context:
         the integer clip limit `clip_count` (>= ky * kx: none) and `nbins` bins; the dtype stays (include/kpdi.h,
         kpdi_adaptive_histogram_equalization)."""
         check(self._f.adaptive_histogram_equalization(self._h, int(ky), int(kx), int(clip_count), int(nbins)))
+
+    def average_neighbour_patterns(self, ny, nx, window, window_sums, row0=0, row1=None):
+        """Average every resident pattern of the rows [row0, row1) of the ny x nx map with its neighbours under the
+        2-D `window` (float64 coefficients, origin at shape // 2) and rescale it to its dtype's range; `window_sums`:
+        (ny, nx) integers, the truncated window sum of every resident point taken from the WHOLE map.  The averaged
+        patterns replace the resident ones (include/kpdi.h, kpdi_average_neighbour_patterns)."""
+        w = np.ascontiguousarray(window, dtype=np.float64)
+        ws = np.ascontiguousarray(window_sums, dtype=np.int64)
+        if w.ndim != 2:
+            raise KpdiError(f"window of shape {w.shape}")
+        if ws.size != int(ny) * int(nx):
+            raise KpdiError(f"{ws.size} window sums for a map of {ny} x {nx} points")
+        check(self._f.average_neighbour_patterns(self._h, int(ny), int(nx), _ptr(w), int(w.shape[0]), int(w.shape[1]),
+                                                 _ptr(ws), int(row0), int(ny if row1 is None else row1)))
+
+    def neighbour_dot_products(self, ny, nx, footprint, zero_mean=True, normalize=True, dtype_out=np.float32, row0=0,
+                               row1=None, matrices=True, average=True):
+        """Dot products of every resident pattern of the rows [row0, row1) of the ny x nx map with its neighbours under
+        the 2-D boolean `footprint`: (matrices (rows, nx, wy, wx) or None, average map (rows, nx) or None) of
+        `dtype_out` (float32 / float64), from one launch (include/kpdi.h, kpdi_neighbour_dot_products)."""
+        fp = np.ascontiguousarray(np.asarray(footprint) != 0, dtype=np.uint8)
+        dt = np.dtype(dtype_out)
+        if fp.ndim != 2:
+            raise KpdiError(f"footprint of shape {fp.shape}")
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise KpdiError(f"dtype_out {dt}: the dot products are float32 or float64")
+        row1 = int(ny if row1 is None else row1)
+        rows = max(row1 - int(row0), 0)
+        mat = np.empty((rows, int(nx)) + fp.shape, dtype=dt) if matrices else None
+        adp = np.empty((rows, int(nx)), dtype=dt) if average else None
+        check(self._f.neighbour_dot_products(self._h, int(ny), int(nx), _ptr(fp), int(fp.shape[0]), int(fp.shape[1]),
+                                             int(bool(zero_mean)), int(bool(normalize)), int(dt == np.float64),
+                                             int(row0), row1, _ptr(mat), _ptr(adp)))
+        return mat, adp
 
     # -- sweep
     def set_dictionary_size(self, n_total):

@@ -213,7 +213,7 @@ static void write_twiddles(float *tw, int sy, int sx) {
 
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.6.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.7.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 
@@ -755,6 +755,138 @@ int kpdi_adaptive_histogram_equalization(kpdi_ctx *c, int ky, int kx, int clip_c
                 c->exp_dtype, c->sy, c->sx);
   patterns_changed(c);
   return KPDI_OK;
+}
+
+}  // extern "C"
+
+namespace kpdi {
+
+// what both neighbour ops check: the resident patterns as a map of ny x nx points, the window, the output rows
+static int check_neighbour_args(kpdi_ctx *c, const char *op, int ny, int nx, const void *window, int wy, int wx, int row0,
+                                int row1) {
+  int rc = check_patterns(c, op);
+  if (rc) return rc;
+  if (ny < 1 || nx < 1 || (int64_t)ny * nx != c->m_all)
+    return fail(KPDI_EINVAL, "%s: a map of %d x %d points, %lld patterns are resident", op, ny, nx, (long long)c->m_all);
+  if (!window || wy < 1 || wx < 1 || (int64_t)wy * wx > NB_MAX_WINDOW)
+    return fail(KPDI_EINVAL, "%s: window of %d x %d", op, wy, wx);
+  if (row0 < 0 || row1 > ny || row0 >= row1) return fail(KPDI_EINVAL, "%s: rows [%d, %d) of %d", op, row0, row1, ny);
+  if ((int64_t)(row1 - row0) * nx > INT_MAX) return fail(KPDI_EINVAL, "%s: too many map points in one call", op);
+  return KPDI_OK;
+}
+
+}  // namespace kpdi
+
+extern "C" {
+
+int kpdi_average_neighbour_patterns(kpdi_ctx *c, int ny, int nx, const double *window, int wy, int wx,
+                                    const int64_t *window_sums, int row0, int row1) {
+  int rc = kpdi::check_neighbour_args(c, "neighbour averaging", ny, nx, window, wy, wx, row0, row1);
+  if (rc) return rc;
+  if (!window_sums) return fail(KPDI_EINVAL, "window_sums is NULL");
+  std::vector<kpdi::NbTap> taps;
+  for (int j = 0; j < wy * wx; ++j) {
+    if (!std::isfinite(window[j])) return fail(KPDI_EINVAL, "window coefficient %d is not finite", j);
+    if (window[j] != 0.0) taps.push_back(kpdi::NbTap{window[j], j / wx - wy / 2, j % wx - wx / 2, j, 0});
+  }
+  const size_t n = (size_t)c->m_all;
+  std::vector<double> ws(n);
+  for (size_t i = 0; i < n; ++i) {
+    ws[i] = (double)window_sums[i];
+    if (window_sums[i] == 0 && i >= (size_t)row0 * nx && i < (size_t)row1 * nx)
+      return fail(KPDI_EINVAL, "the window sum of map point %zu is 0: its average is undefined", i);
+  }
+  rc = kpdi::start_pattern_op(c);
+  if (rc) return rc;
+  const size_t tbytes = (taps.size() + 1) * sizeof(kpdi::NbTap), bytes = n * c->npix * kpdi::dtype_size(c->exp_dtype);
+  HIPCHK(c->op_tab.reserve(tbytes + n * sizeof(double)));
+  if (!taps.empty())
+    HIPCHK(hipMemcpyAsync(c->op_tab.p, taps.data(), taps.size() * sizeof(kpdi::NbTap), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync((char *)c->op_tab.p + tbytes, ws.data(), n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c->int_out.reserve(bytes));
+  kpdi::NbAvgLaunch a{};
+  a.src = c->exp_raw.p;
+  a.dst = c->int_out.p;
+  a.dtype = c->exp_dtype;
+  a.ny = ny;
+  a.nx = nx;
+  a.sy = c->sy;
+  a.sx = c->sx;
+  a.row0 = row0;
+  a.row1 = row1;
+  a.taps = (const kpdi::NbTap *)c->op_tab.p;
+  a.ntaps = (int)taps.size();
+  a.ws = (const double *)((const char *)c->op_tab.p + tbytes);
+  float omin, omax;
+  dtype_range(c->exp_dtype, &omin, &omax);
+  a.omin = omin;
+  a.orange = (double)omax - (double)omin;
+  hipError_t e = kpdi::launch_neighbour_average(a, c->stream);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "neighbour averaging kernel: %s (dtype %d, %dx%d)", hipGetErrorString(e), c->exp_dtype, c->sy, c->sx);
+  // rows that are resident only as neighbours keep their patterns
+  const size_t row_bytes = bytes / ny;
+  if (row0 > 0)
+    HIPCHK(hipMemcpyAsync(c->int_out.p, c->exp_raw.p, row_bytes * row0, hipMemcpyDeviceToDevice, c->stream));
+  if (row1 < ny)
+    HIPCHK(hipMemcpyAsync((char *)c->int_out.p + row_bytes * row1, (const char *)c->exp_raw.p + row_bytes * row1,
+                          row_bytes * (ny - row1), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // `taps` and `ws` die at scope exit
+  std::swap(c->exp_raw, c->int_out);
+  patterns_changed(c);
+  return KPDI_OK;
+}
+
+int kpdi_neighbour_dot_products(kpdi_ctx *c, int ny, int nx, const uint8_t *footprint, int wy, int wx, int zero_mean,
+                                int normalize, int f64, int row0, int row1, void *matrices_out, void *map_out) {
+  int rc = kpdi::check_neighbour_args(c, "neighbour dot products", ny, nx, footprint, wy, wx, row0, row1);
+  if (rc) return rc;
+  if (!matrices_out && !map_out) return fail(KPDI_EINVAL, "matrices_out and map_out are both NULL");
+  const int wsize = wy * wx, jorigin = (wy / 2) * wx + wx / 2;
+  if (!footprint[jorigin]) return fail(KPDI_EINVAL, "the footprint is false at its own origin (%d, %d)", wy / 2, wx / 2);
+  std::vector<kpdi::NbTap> taps;
+  for (int j = 0; j < wsize; ++j)
+    if (footprint[j] && j != jorigin) taps.push_back(kpdi::NbTap{1.0, j / wx - wy / 2, j % wx - wx / 2, j, 0});
+  rc = kpdi::start_pattern_op(c);
+  if (rc) return rc;
+  const size_t n = (size_t)c->m_all, n_out = (size_t)(row1 - row0) * nx, esz = f64 ? 8 : 4;
+  const size_t stats_bytes = n * 2 * sizeof(double), mat_bytes = matrices_out ? n_out * wsize * esz : 0;
+  const size_t mat_off = stats_bytes, map_off = (mat_off + mat_bytes + 15) & ~(size_t)15;
+  HIPCHK(c->op_tab.reserve((taps.size() + 1) * sizeof(kpdi::NbTap)));
+  if (!taps.empty())
+    HIPCHK(hipMemcpyAsync(c->op_tab.p, taps.data(), taps.size() * sizeof(kpdi::NbTap), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c->op_ws.reserve(map_off + n_out * esz));
+  char *ws = (char *)c->op_ws.p;
+  hipError_t e = kpdi::launch_neighbour_stats(c->exp_raw.p, c->exp_dtype, c->m_all, c->sy, c->sx, zero_mean ? 1 : 0,
+                                              (double *)ws, c->stream);
+  if (e != hipSuccess) return fail(KPDI_EHIP, "neighbour statistics kernel: %s", hipGetErrorString(e));
+  kpdi::NbDotLaunch a{};
+  a.src = c->exp_raw.p;
+  a.dtype = c->exp_dtype;
+  a.ny = ny;
+  a.nx = nx;
+  a.sy = c->sy;
+  a.sx = c->sx;
+  a.row0 = row0;
+  a.row1 = row1;
+  a.taps = (const kpdi::NbTap *)c->op_tab.p;
+  a.ntaps = (int)taps.size();
+  a.wsize = wsize;
+  a.jorigin = jorigin;
+  a.stats = (const double2 *)ws;
+  a.normalize = normalize ? 1 : 0;
+  a.f64 = f64 ? 1 : 0;
+  a.matrices = matrices_out ? ws + mat_off : nullptr;
+  a.map = map_out ? ws + map_off : nullptr;
+  e = kpdi::launch_neighbour_dot(a, c->stream);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "neighbour dot product kernel: %s (dtype %d, %dx%d)", hipGetErrorString(e), c->exp_dtype, c->sy, c->sx);
+  if (matrices_out) {
+    rc = results_to_host(c, matrices_out, a.matrices, mat_bytes);
+    if (rc) return rc;
+  }
+  if (map_out) return results_to_host(c, map_out, a.map, n_out * esz);
+  return KPDI_OK;  // (results_to_host synchronised: `taps` may die)
 }
 
 size_t kpdi_dtype_size(int dtype) { return kpdi::dtype_size(dtype); }

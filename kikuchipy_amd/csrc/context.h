@@ -19,6 +19,7 @@
 #include "fftfilter_plan.h"
 #include "intensity_plan.h"
 #include "clahe_plan.h"
+#include "neighbours_plan.h"
 #include "plan.h"
 #include "group_hooks.h"
 
@@ -211,10 +212,12 @@ struct kpdi_ctx {
   int m = 0, m_pad = 0;
   bool have_nav_mask = false;
   kpdi::DevBuf exp_raw, row_map, exp_x;
-  // the per-pattern ops (image quality, FFT filter, CLAHE): host tables (twiddles + folded weights / transfer function,
+  // the per-pattern ops (image quality, FFT filter, CLAHE) and the neighbour ops: host tables (twiddles + folded weights / transfer function,
   // or the taps), their path-1 workspace, and the image quality results
   kpdi::DevBuf op_tab, op_ws, iq_out;
-  kpdi::DevBuf int_out, int_ws;  // kpdi_*_intensity: the patterns in a new dtype (swapped with exp_raw), range partials
+  // kpdi_*_intensity: the patterns in a new dtype, kpdi_average_neighbour_patterns: the averaged patterns (swapped with
+  // exp_raw); range partials
+  kpdi::DevBuf int_out, int_ws;
 
   // dictionary chunk
   kpdi::DevBuf dict_raw, dict_y;

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "clahe_plan.h"
+#include "neighbours_plan.h"
 
 namespace kpdi {
 
@@ -403,5 +404,30 @@ struct ClaheLaunch {
 // the plan launch_clahe follows (KPDI_CLAHE_PATH=1 forces path 1)
 ClahePlan clahe_launch_plan(int dtype, int sy, int sx, int ky, int kx, int nbins, int64_t n);
 hipError_t launch_clahe(const ClaheLaunch &a, hipStream_t s);
+
+// ---- neighbour pattern averaging and neighbour dot products (neighbours.hip) -------------------
+// the resident patterns are a map of ny x nx points (row-major); output is produced for the rows [row0, row1)
+struct NbAvgLaunch {
+  const void *src; void *dst; int dtype;  // ny * nx x sy x sx of `dtype`, device; dst != src
+  int ny, nx, sy, sx, row0, row1;
+  const NbTap *taps; int ntaps;           // the non-zero window coefficients in C order (device)
+  const double *ws;                       // [ny * nx] window sums (device)
+  double omin, orange;                    // dtype range: omin, omax - omin
+};
+hipError_t launch_neighbour_average(const NbAvgLaunch &a, hipStream_t s);
+// stats: [n] x (mean or 0, sum (x - mean)^2) as doubles
+hipError_t launch_neighbour_stats(const void *src, int dtype, int64_t n, int sy, int sx, int zero_mean, double *stats,
+                                  hipStream_t s);
+struct NbDotLaunch {
+  const void *src; int dtype;
+  int ny, nx, sy, sx, row0, row1;
+  const NbTap *taps; int ntaps;           // the true footprint entries other than the origin (device)
+  int wsize, jorigin;                     // entries of the window, flat index of its origin
+  const double2 *stats;                   // launch_neighbour_stats of all ny * nx patterns
+  int normalize, f64;                     // f64: the outputs are double, else float
+  void *matrices;                         // [(row1 - row0) * nx][wsize] or NULL
+  void *map;                              // [(row1 - row0) * nx] or NULL
+};
+hipError_t launch_neighbour_dot(const NbDotLaunch &a, hipStream_t s);
 
 }  // namespace kpdi

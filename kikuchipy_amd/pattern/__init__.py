@@ -11,3 +11,8 @@ from kikuchipy_amd.pattern._pattern import (  # noqa: F401
     rescale_intensity,
     rescale_intensity_stack,
 )
+from kikuchipy_amd.pattern._neighbours import (  # noqa: F401
+    average_neighbour_dot_product_map,
+    average_neighbour_patterns_stack,
+    neighbour_dot_product_matrices,
+)

@@ -26,7 +26,7 @@ import numpy as np
 
 from kikuchipy_amd import _lib
 from kikuchipy_amd.indexing._dictionary_indexing import dictionary_indexing as _dictionary_indexing
-from kikuchipy_amd.pattern import _pattern
+from kikuchipy_amd.pattern import _neighbours, _pattern
 from kikuchipy_amd.simulations import DTYPE_RANGE, ProjectedDictionary
 
 
@@ -377,6 +377,59 @@ class EBSD:
         q = _pattern.get_image_quality(data.reshape((-1,) + data.shape[-2:]), normalize,
                                        context=None if contexts else self.context, contexts=contexts)
         return q.reshape(self._navigation_shape_rc)
+
+    def average_neighbour_patterns(self, window="circular", window_shape=(3, 3), show_progressbar=None, inplace=True,
+                                   lazy_output=None, *, devices=None, **kwargs):
+        """signals/ebsd.py:943-1111: average every pattern with its neighbours in the map under `window` (a valid
+        `filters.Window`, or what `Window(window=window, shape=window_shape, **kwargs)` makes), divide by the point's
+        truncated window sum and rescale to the dtype's range (`kikuchipy_amd.pattern.average_neighbour_patterns_stack`).
+        A window of shape (1,) or (1, 1) warns and does nothing; a 1-D window on a 2-D map acts along the first
+        navigation axis of the array; `show_progressbar` / `lazy_output` as in `remove_static_background`."""
+        if lazy_output and inplace:
+            raise ValueError("'lazy_output=True' requires 'inplace=False'")
+        win = _neighbours.averaging_window(window, window_shape, **kwargs)
+        if win.shape in [(1,), (1, 1)]:
+            warnings.warn(f"A window of shape {win.shape} was passed, no averaging is therefore performed")
+            return None
+        nav = self._navigation_shape_rc
+        w = _neighbours.window_on_map(win, nav)  # before any GPU work, as the window sums the stack function checks
+        if not _neighbours.neighbour_window_sums(w, nav[0], nav[1] if len(nav) == 2 else 1).all():
+            raise ValueError("The window sum of a map point is 0: its average is undefined")
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        out = _neighbours.average_neighbour_patterns_stack(np.asarray(self.data), win,
+                                                           context=None if contexts else self.context, contexts=contexts)
+        if inplace:
+            self.data = out
+            return None
+        return self._like(out)
+
+    def get_neighbour_dot_product_matrices(self, window=None, zero_mean=True, normalize=True, dtype_out="float32",
+                                           show_progressbar=None, *, devices=None):
+        """signals/ebsd.py:1221-1310: per map point the dot products of its pattern with the neighbours `window`
+        selects (None: the nearest ones, `Window("circular", (3, 3)[:nav_dim])`), an array of the navigation shape +
+        the window's shape (`kikuchipy_amd.pattern.neighbour_dot_product_matrices`).  `show_progressbar` is accepted
+        and has nothing to show."""
+        nav = self._navigation_shape_rc
+        window = _neighbours.dot_product_window(window, nav)  # before any GPU work
+        _neighbours._dot_dtype(dtype_out)
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        return _neighbours.neighbour_dot_product_matrices(np.asarray(self.data), window, zero_mean, normalize, dtype_out,
+                                                          context=None if contexts else self.context, contexts=contexts)
+
+    def get_average_neighbour_dot_product_map(self, window=None, zero_mean=True, normalize=True, dtype_out="float32",
+                                              dp_matrices=None, show_progressbar=None, *, devices=None):
+        """signals/ebsd.py:1377-1491: the average dot product (ADP) map, per map point the mean of the dot products with
+        its neighbours (`kikuchipy_amd.pattern.average_neighbour_dot_product_map`); with `dp_matrices` (of
+        `get_neighbour_dot_product_matrices` and the same `window`) it is their mean, taken on the host."""
+        nav = self._navigation_shape_rc
+        window = _neighbours.dot_product_window(window, nav)  # before any GPU work
+        if dp_matrices is not None:
+            return _neighbours.average_dot_product_map_from_matrices(dp_matrices, window, len(nav))
+        _neighbours._dot_dtype(dtype_out)
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        return _neighbours.average_neighbour_dot_product_map(np.asarray(self.data), window, zero_mean, normalize,
+                                                             dtype_out, context=None if contexts else self.context,
+                                                             contexts=contexts)
 
     # ------------------------------------------------------------------ refinement
     def _refine(self, mode, xmap, detector, master_pattern, energy, navigation_mask, signal_mask,
