@@ -188,6 +188,16 @@ int kpdi_get_experimental(kpdi_ctx *ctx, void *patterns_out);
  * uint16 / int16 / float32 / float64 patterns; kernels and paths: csrc/iq.hip, csrc/iq_plan.h. */
 int kpdi_image_quality(kpdi_ctx *ctx, int normalize, const double *weights, double inertia_max, float *iq_out);
 
+/* ---- sums over detector rectangles (EBSD.get_virtual_bse_intensity, signals/ebsd.py:1555-1598; imaging/vbse.py) ----
+ * np.nansum of every resident pattern over `n_rects` rectangles, AFTER the recorded background steps (they run first,
+ * as in kpdi_get_experimental); the navigation mask is ignored and the patterns are only read - once, whatever
+ * `n_rects`.  `rects`: n_rects x (row0, row1, col0, col1), half-open, 0 <= row0 <= row1 <= sy and 0 <= col0 <= col1 <= sx;
+ * rectangles may overlap, an empty one sums to 0.  `sums_out`: m_all * n_rects values, pattern-major: uint64 for uint8 /
+ * uint16 patterns and int64 for int8 / int16 (exact), float32 for float32 and float64 for float64 patterns (summed in
+ * float64 in a fixed order, NaN counted as 0, rounded once).  n_rects == 0 does nothing; a bad argument gives
+ * KPDI_EINVAL before anything runs.  Kernels and paths: csrc/regionsum.hip, csrc/regionsum_plan.h. */
+int kpdi_region_sums(kpdi_ctx *ctx, const int32_t *rects, int n_rects, void *sums_out);
+
 /* ---- FFT filter (EBSD.fft_filter, signals/ebsd.py:805-930; pattern/chunk.py:75-127) ------------------------------
  * Filters every resident pattern in place, AFTER the recorded background steps (they run first), and rescales it to
  * the range of its dtype as the reference's rescale_intensity(dtype_out=<dtype>) does; the navigation mask is ignored

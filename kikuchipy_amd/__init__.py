@@ -22,10 +22,10 @@ from kikuchipy_amd.indexing import (  # noqa: E402,F401
 )
 from kikuchipy_amd.pattern import remove_dynamic_background, remove_static_background  # noqa: E402,F401
 from kikuchipy_amd.detectors import EBSDDetector  # noqa: E402,F401
-from kikuchipy_amd.signals import EBSD, DictionaryXmap, EBSDMasterPattern  # noqa: E402,F401
+from kikuchipy_amd.signals import EBSD, DictionaryXmap, EBSDMasterPattern, VirtualBSEImage  # noqa: E402,F401
 from kikuchipy_amd.simulations import ProjectedDictionary  # noqa: E402,F401
 from kikuchipy_amd.io import load  # noqa: E402,F401
-from kikuchipy_amd import filters  # noqa: E402,F401
+from kikuchipy_amd import filters, imaging  # noqa: E402,F401
 from kikuchipy_amd.sampling import get_sample_fundamental  # noqa: E402,F401
 
 from kikuchipy_amd._lib import clear_engine_cache  # noqa: E402,F401
@@ -37,6 +37,7 @@ __all__ = [
     "EBSDDetector",
     "EBSDMasterPattern",
     "ProjectedDictionary",
+    "VirtualBSEImage",
     "RefinementResult",
     "ResidentDictionary",
     "NormalizedCrossCorrelationMetric",
@@ -46,6 +47,7 @@ __all__ = [
     "dictionary_indexing",
     "filters",
     "get_sample_fundamental",
+    "imaging",
     "load",
     "merge_crystal_maps",
     "orientation_similarity_map",

@@ -132,6 +132,7 @@ SIGNATURES = {
     "kpdi_remove_dynamic_background": (_i, [_vp, _i, _i, C.c_double, C.c_double]),
     "kpdi_get_experimental": (_i, [_vp, _vp]),
     "kpdi_image_quality": (_i, [_vp, _i, _vp, C.c_double, _vp]),
+    "kpdi_region_sums": (_i, [_vp, _vp, _i, _vp]),
     "kpdi_fft_filter": (_i, [_vp, _i, _vp, _i, _i]),
     "kpdi_rescale_intensity": (_i, [_vp, _vp, _vp, C.c_double, C.c_double, _i]),
     "kpdi_normalize_intensity": (_i, [_vp, C.c_double, _i, _i]),
@@ -456,6 +457,19 @@ class Context:
             raise KpdiError(f"frequency vectors of shape {w.shape}, patterns of shape {self._detector}")
         out = np.empty(self._exp_shape[0], dtype=np.float32)
         check(self._f.image_quality(self._h, int(bool(normalize)), _ptr(w), float(inertia_max), _ptr(out)))
+        return out
+
+    def region_sums(self, rects):
+        """np.nansum of every resident pattern (after the recorded background steps) over each rectangle of `rects`,
+        (n_rects, 4) of (row0, row1, col0, col1), half-open and inside the detector: (m_all, n_rects) of uint64 (uint8 /
+        uint16 patterns), int64 (int8 / int16), float32 or float64 (include/kpdi.h, kpdi_region_sums)."""
+        r = np.ascontiguousarray(rects, dtype=np.int32)
+        if r.ndim != 2 or r.shape[1] != 4:
+            raise KpdiError(f"rectangles of shape {r.shape}, not (n_rects, 4)")
+        kind = self._exp_dtype.kind
+        dt = self._exp_dtype if kind == "f" else np.dtype(np.uint64 if kind == "u" else np.int64)
+        out = np.zeros((self._exp_shape[0], len(r)), dtype=dt)
+        check(self._f.region_sums(self._h, _ptr(r), len(r), _ptr(out)))
         return out
 
     def fft_filter(self, function_domain, table):

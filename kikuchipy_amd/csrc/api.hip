@@ -213,7 +213,7 @@ static void write_twiddles(float *tw, int sy, int sx) {
 
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.7.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.8.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 
@@ -571,6 +571,50 @@ int kpdi_image_quality(kpdi_ctx *c, int normalize, const double *weights, double
   a.out = c->iq_out.as<float>();
   HIPCHK(kpdi::launch_image_quality(a, c->stream));
   return results_to_host(c, iq_out, c->iq_out.p, (size_t)c->m_all * sizeof(float));  // (synchronises: `tab` is read)
+}
+
+int kpdi_region_sums(kpdi_ctx *c, const int32_t *rects, int n_rects, void *sums_out) {
+  int rc = check_patterns(c, "region sums");
+  if (rc) return rc;
+  if (n_rects < 0) return fail(KPDI_EINVAL, "n_rects is %d", n_rects);
+  if (n_rects == 0) return KPDI_OK;
+  if (!rects) return fail(KPDI_EINVAL, "rects is NULL");
+  if (!sums_out) return fail(KPDI_EINVAL, "sums_out is NULL");
+  const int sy = c->sy, sx = c->sx;
+  for (int k = 0; k < n_rects; ++k) {
+    const int32_t *r = rects + 4 * (size_t)k;
+    if (r[0] < 0 || r[1] < r[0] || r[1] > sy || r[2] < 0 || r[3] < r[2] || r[3] > sx)
+      return fail(KPDI_EINVAL, "rectangle %d, rows [%d, %d) and columns [%d, %d), is not inside the %d x %d detector", k,
+                  r[0], r[1], r[2], r[3], sy, sx);
+  }
+  const kpdi::RsPlan plan = kpdi::rs_plan(c->exp_dtype, sy, sx, c->m_all, n_rects);
+  if (plan.path < 0)
+    return fail(KPDI_EINVAL, "region sums of %d x %d patterns over %d rectangles: no kernel path takes this shape", sy, sx,
+                n_rects);
+  rc = start_pattern_op(c);
+  if (rc) return rc;
+  const size_t rbytes = (size_t)n_rects * 4 * sizeof(int32_t);
+  const size_t obytes = (size_t)c->m_all * n_rects * (c->exp_dtype == KPDI_F32 ? 4 : 8);
+  HIPCHK(c->op_tab.reserve(rbytes));
+  HIPCHK(hipMemcpyAsync(c->op_tab.p, rects, rbytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c->iq_out.reserve(obytes));
+  if (plan.path == 1) HIPCHK(c->op_ws.reserve(plan.workspace_bytes));
+  kpdi::RsLaunch a{};
+  a.patterns = c->exp_raw.p;
+  a.dtype = c->exp_dtype;
+  a.n = c->m_all;
+  a.sy = sy;
+  a.sx = sx;
+  a.rects = (const int32_t *)c->op_tab.p;
+  a.n_rects = n_rects;
+  a.workspace = c->op_ws.p;
+  a.workspace_bytes = c->op_ws.cap;
+  a.out = c->iq_out.p;
+  hipError_t e = kpdi::launch_region_sums(a, c->stream);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "region-sum kernel: %s (dtype %d, %dx%d, %d rectangles)", hipGetErrorString(e), c->exp_dtype, sy,
+                sx, n_rects);
+  return results_to_host(c, sums_out, c->iq_out.p, obytes);  // (synchronises: `rects` is read)
 }
 
 int kpdi_fft_filter(kpdi_ctx *c, int function_domain, const double *table, int ty, int tx) {

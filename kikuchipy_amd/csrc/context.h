@@ -20,6 +20,7 @@
 #include "intensity_plan.h"
 #include "clahe_plan.h"
 #include "neighbours_plan.h"
+#include "regionsum_plan.h"
 #include "plan.h"
 #include "group_hooks.h"
 

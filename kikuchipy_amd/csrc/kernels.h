@@ -363,6 +363,15 @@ struct IqLaunch {
 };
 hipError_t launch_image_quality(const IqLaunch &a, hipStream_t s);
 
+// ---- sums over detector rectangles (regionsum.hip) ---------------------------------
+struct RsLaunch {
+  const void *patterns; int dtype; int64_t n; int sy, sx;  // n x sy x sx of `dtype`, device
+  const int32_t *rects; int n_rects;  // device, 16-byte aligned: n_rects x (row0, row1, col0, col1), half-open, inside the detector
+  void *workspace; size_t workspace_bytes;  // path 1 of regionsum_plan.h
+  void *out;  // [n][n_rects] uint64 (unsigned patterns) / int64 (signed) / float32 / float64
+};
+hipError_t launch_region_sums(const RsLaunch &a, hipStream_t s);
+
 // ---- FFT filter (fftfilter.hip) ---------------------------------------------------
 struct FfLaunch {
   void *patterns; int dtype; int64_t n; int sy, sx;  // n x sy x sx of `dtype`, device, filtered in place

@@ -175,6 +175,29 @@ def get_image_quality(patterns, normalize=True, frequency_vectors=None, inertia_
     return float(q) if patterns.ndim == 2 else q
 
 
+def region_sums(patterns, rects, *, context=None, device=0, contexts=None):
+    """`np.nansum(patterns[..., row0:row1, col0:col1], axis=(-2, -1))` for every rectangle (row0, row1, col0, col1) of
+    `rects` (n_rects, 4) - half-open, inside the detector, free to overlap or be empty - in one pass over the patterns
+    (csrc/regionsum.hip): an array of shape `patterns.shape[:-2] + (n_rects,)`, uint64 for uint8 / uint16 patterns,
+    int64 for int8 / int16 (both exact), float32 / float64 for patterns of these (summed in float64 in a fixed order
+    and rounded once; NaN counts as 0).  The same bits whichever way `contexts` split the patterns."""
+    patterns = np.asarray(patterns)
+    if patterns.ndim < 2:
+        raise ValueError("patterns need at least the two detector axes")
+    r = np.asarray(rects)
+    if r.size == 0:
+        r = r.reshape(0, 4)
+    if r.ndim != 2 or r.shape[1] != 4 or r.dtype.kind not in "iu":
+        raise ValueError(f"rects must be integers of shape (n_rects, 4): (row0, row1, col0, col1), not {r.dtype} {r.shape}")
+    sy, sx = patterns.shape[-2:]
+    bad = (r[:, 0] < 0) | (r[:, 1] < r[:, 0]) | (r[:, 1] > sy) | (r[:, 2] < 0) | (r[:, 3] < r[:, 2]) | (r[:, 3] > sx)
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"rectangle {k}, {tuple(int(v) for v in r[k])}, is not inside the {sy} x {sx} detector")
+    r = np.ascontiguousarray(r, dtype=np.int32)
+    return _process(patterns, lambda c: None, context, device, contexts, collect=lambda c: c.region_sums(r))
+
+
 _FUNCTION_DOMAINS = ["frequency", "spatial"]
 
 

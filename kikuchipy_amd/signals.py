@@ -81,6 +81,66 @@ class _Axes:
         return f"<axes: navigation {self.navigation_shape} | signal {self.signal_shape}>"
 
 
+class VirtualBSEImage:
+    """Virtual backscatter electron image(s) (signals/virtual_bse_image.py): `data`, the images in the last two axes
+    (an RGB image: (ny, nx, 3), see `rgb_data`), and the three intensity methods of the reference's class, which run
+    the stack functions of `kikuchipy_amd.pattern` with the images as the patterns."""
+
+    def __init__(self, data, *, device=0):
+        self.data = np.asarray(data)
+        self._device = device
+
+    def __repr__(self):
+        return f"<VirtualBSEImage, shape: {self.data.shape}, dtype: {self.data.dtype}>"
+
+    def deepcopy(self):
+        return VirtualBSEImage(np.array(self.data, copy=True), device=self._device)
+
+    @property
+    def rgb_data(self):
+        """An RGB image's `data` (ny, nx, 3) of uint8 / uint16 as HyperSpy's rgb8 / rgb16 dtype: (ny, nx) of fields R, G, B."""
+        d = self.data
+        if d.ndim < 1 or d.shape[-1] != 3 or d.dtype not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+            raise ValueError(f"data of shape {d.shape} and dtype {d.dtype} is not an RGB image")
+        code = f"u{d.dtype.itemsize}"
+        return np.ascontiguousarray(d).view([("R", code), ("G", code), ("B", code)])[..., 0]
+
+    def _done(self, out, inplace):
+        if inplace:
+            self.data = out
+            return None
+        return VirtualBSEImage(out, device=self._device)
+
+    def rescale_intensity(self, relative=False, in_range=None, out_range=None, dtype_out=None, percentiles=None,
+                          show_progressbar=None, inplace=True, lazy_output=None):
+        """signals/_kikuchipy_signal.py:88-243 through `kikuchipy_amd.pattern.rescale_intensity_stack`."""
+        if lazy_output and inplace:
+            raise ValueError("'lazy_output=True' requires 'inplace=False'")
+        if in_range is not None and percentiles is not None:
+            raise ValueError("'percentiles' must be None if 'in_range' is not None")
+        elif relative is True and in_range is not None:
+            raise ValueError("'in_range' must be None if 'relative' is True")
+        out = _pattern.rescale_intensity_stack(self.data, in_range, out_range, dtype_out, percentiles,
+                                               relative=bool(relative), device=self._device)
+        return self._done(out, inplace)
+
+    def normalize_intensity(self, num_std=1, divide_by_square_root=False, dtype_out=None, show_progressbar=None,
+                            inplace=True, lazy_output=None):
+        """signals/_kikuchipy_signal.py:245-338 through `kikuchipy_amd.pattern.normalize_intensity_stack`."""
+        if lazy_output and inplace:
+            raise ValueError("'lazy_output=True' requires 'inplace=False'")
+        out = _pattern.normalize_intensity_stack(self.data, num_std, divide_by_square_root, dtype_out, device=self._device)
+        return self._done(out, inplace)
+
+    def adaptive_histogram_equalization(self, kernel_size=None, clip_limit=0.0, nbins=128, show_progressbar=None,
+                                        inplace=True, lazy_output=None):
+        """signals/_kikuchipy_signal.py:340-470 through `kikuchipy_amd.pattern.adaptive_histogram_equalization_stack`."""
+        if lazy_output and inplace:
+            raise ValueError("'lazy_output=True' requires 'inplace=False'")
+        out = _pattern.adaptive_histogram_equalization_stack(self.data, kernel_size, clip_limit, nbins, device=self._device)
+        return self._done(out, inplace)
+
+
 class EBSD:
     def __init__(self, data, static_background=None, xmap=None, step_sizes=None, scan_unit="px",
                  device=None, devices=None, *, detector=None):
@@ -377,6 +437,34 @@ class EBSD:
         q = _pattern.get_image_quality(data.reshape((-1,) + data.shape[-2:]), normalize,
                                        context=None if contexts else self.context, contexts=contexts)
         return q.reshape(self._navigation_shape_rc)
+
+    def _region_sums(self, rects, devices=None):
+        """`kikuchipy_amd.pattern.region_sums` of this signal's patterns: navigation shape + (n_rects,)."""
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        return _pattern.region_sums(np.asarray(self.data), rects, context=None if contexts else self.context,
+                                    contexts=contexts)
+
+    def get_virtual_bse_intensity(self, roi, out_signal_axes=None, *, devices=None):
+        """signals/ebsd.py:1555-1598: the virtual backscatter electron image formed by the intensity within `roi` on the
+        detector, `np.nansum` of every pattern over it: a `VirtualBSEImage` of the navigation shape, uint64 / int64 for
+        integer patterns as NumPy's sum.  `roi`: anything with `left`, `top`, `right` and `bottom`
+        (`kikuchipy_amd.imaging.RectangularROI`, `roi_to_rect`).  `out_signal_axes`: None, or the first navigation axes
+        in HyperSpy's order in the order the image shall have them: (1, 0) transposes."""
+        from kikuchipy_amd import imaging
+
+        nav = self._navigation_shape_rc
+        if out_signal_axes is None:
+            out_signal_axes = list(range(min(len(nav), 2)))
+        out_signal_axes = list(out_signal_axes)
+        if len(out_signal_axes) > len(nav):
+            raise ValueError("The length of 'out_signal_axes' cannot be longer than the navigation dimension of the signal")
+        if sorted(out_signal_axes) != list(range(len(out_signal_axes))):
+            raise ValueError(f"out_signal_axes {out_signal_axes} is not a permutation of the first navigation axes")
+        rect = imaging.roi_to_rect(roi, self._signal_shape_rc, imaging.signal_axes(self))
+        image = self._region_sums([rect], devices)[..., 0]
+        if out_signal_axes == [1, 0]:
+            image = np.ascontiguousarray(image.T)
+        return VirtualBSEImage(image)
 
     def average_neighbour_patterns(self, window="circular", window_shape=(3, 3), show_progressbar=None, inplace=True,
                                    lazy_output=None, *, devices=None, **kwargs):
