@@ -275,6 +275,44 @@ int kpdi_average_neighbour_patterns(kpdi_ctx *ctx, int ny, int nx, const double 
 int kpdi_neighbour_dot_products(kpdi_ctx *ctx, int ny, int nx, const uint8_t *footprint, int wy, int wx, int zero_mean,
                                 int normalize, int f64, int row0, int row1, void *matrices_out, void *map_out);
 
+/* ---- downsampling (EBSD.downsample, signals/ebsd.py:1113-1219; pattern/_pattern.py:776-807) -----------------------
+ * Replaces every resident pattern (sy x sx, uint8 / int8 / uint16 / int16 / float32 / float64) by its binned and
+ * rescaled image of (sy / factor) x (sx / factor) in `dtype_out` (the same six), AFTER the recorded background steps
+ * (they run first, as in kpdi_rescale_intensity).  The reference's _downsample2d as NumPy 1.26 evaluates it: the
+ * pattern as float32; every binned pixel the float32 sum of its factor x factor pixels added one by one, rows outer and
+ * columns inner; (b - min b) / float32(max b - min b) * (omax - omin) + omin with the range of `dtype_out`, every
+ * operation rounded to float32; then the cast of kpdi_rescale_intensity (a float64 `dtype_out` is the float32 result
+ * widened).  min / max propagate NaN as np.min / np.max do, so a pattern holding a NaN, like a constant binned pattern
+ * (0 / 0), becomes NaN for float `dtype_out` and 0 for integer ones.  Bit-exact with the reference; the result does not
+ * depend on the number of patterns or on the kernel path (csrc/downsample.hip, csrc/downsample_plan.h).
+ * Afterwards the problem's detector shape is (sy / factor, sx / factor) with no signal mask, the patterns' dtype is
+ * `dtype_out` (kpdi_get_experimental returns the new shape and dtype), and prepared rows and the running best-k are
+ * forgotten; metric, arithmetic, keep_n and the navigation mask stay.  The binned patterns can be indexed at once.  To
+ * index them under a signal mask call kpdi_set_problem with the NEW shape and the mask next: kpdi_set_problem keeps the
+ * resident patterns whenever the number of detector pixels is unchanged, so neither that call nor a plain
+ * kpdi_set_problem with the new shape loses them.
+ * KPDI_EINVAL before anything runs (the resident set stays as it was): factor < 2, a factor that does not divide both
+ * sy and sx, a `dtype_out` outside the six, no resident patterns, a signal mask set for the old shape, held dictionary
+ * chunks (their layout depends on the shape), or a shape no kernel path takes. */
+int kpdi_downsample(kpdi_ctx *ctx, int factor, int dtype_out);
+
+/* ---- the dynamic background itself (EBSD.get_dynamic_background, signals/ebsd.py:698-803; pattern/chunk.py:33-72;
+ * pattern/_pattern.py:634-695) ----------------------------------------------------------------------------------------
+ * The Gaussian-blurred image of every resident pattern - what kpdi_remove_dynamic_background subtracts or divides
+ * away - into `out`: m_all * sy * sx values of `dtype_out` (the six dtypes above) in host memory.  The resident patterns
+ * are only read, AFTER the recorded background steps; the navigation mask is ignored; std <= 0 selects sx / 8.  In the
+ * reference's order every pattern is cast to `dtype_out` FIRST (the cast of kpdi_rescale_intensity) and then filtered:
+ * KPDI_DOMAIN_FREQUENCY: the cast pattern as float32, correlated with the normalised Gaussian window of
+ *   int(truncate * std) samples per axis with edge-replicated borders (what the reference's FFT filter computes, here
+ *   as two 1-D passes accumulated in float64), rounded to float32 and cast to `dtype_out` (integers truncate).
+ * KPDI_DOMAIN_SPATIAL: scipy.ndimage.gaussian_filter(sigma=std, truncate=truncate) of the cast pattern: reflect
+ *   boundary, radius int(truncate * std + 0.5), each of the two 1-D passes (rows of the detector last) accumulated in
+ *   float64 and stored in `dtype_out`, integers by truncation toward zero - so the second pass sees the quantised
+ *   first one.  (kpdi_remove_dynamic_background blurs a float32 copy instead.)
+ * KPDI_EINVAL before anything runs: an unknown domain, a window of no samples, a `dtype_out` outside the six, NULL, or a
+ * detector above 256 MB of float64 per pattern (5792 x 5792).  Kernel: csrc/preproc.hip (dynamic_background_kernel). */
+int kpdi_get_dynamic_background(kpdi_ctx *ctx, int filter_domain, double std, double truncate, int dtype_out, void *out);
+
 /* ---- dictionary sweep (_dictionary_indexing loop, indexing/_dictionary_indexing.py:94-128)
  * One call = one loop iteration: prepare_dictionary (cast, mask, normalise) +
  * match + top-k of the chunk + merge into the running best-k, all on the GPU.

@@ -138,6 +138,8 @@ SIGNATURES = {
     "kpdi_normalize_intensity": (_i, [_vp, C.c_double, _i, _i]),
     "kpdi_intensity_range": (_i, [_vp, _vp]),
     "kpdi_adaptive_histogram_equalization": (_i, [_vp, _i, _i, _i, _i]),
+    "kpdi_downsample": (_i, [_vp, _i, _i]),
+    "kpdi_get_dynamic_background": (_i, [_vp, _i, C.c_double, C.c_double, _i, _vp]),
     "kpdi_average_neighbour_patterns": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i]),
     "kpdi_neighbour_dot_products": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "kpdi_push_dictionary_chunk": (_i, [_vp, _vp, _i, _i64, _i64]),
@@ -494,6 +496,27 @@ class Context:
         pc = None if percentiles is None else np.ascontiguousarray(percentiles, dtype=np.float64).reshape(2)
         check(self._f.rescale_intensity(self._h, _ptr(ir), _ptr(pc), float(omin), float(omax), dtype_code(dt)))
         self._exp_dtype = dt
+
+    def downsample(self, factor, dtype_out=None):
+        """Bin every resident pattern (after the recorded background steps) by `factor` and rescale it to the range of
+        `dtype_out` (None: the patterns' dtype); the resident patterns and the problem take the new detector shape and
+        dtype (include/kpdi.h, kpdi_downsample)."""
+        dt = self._exp_dtype if dtype_out is None else np.dtype(dtype_out)
+        check(self._f.downsample(self._h, int(factor), dtype_code(dt)))
+        sy, sx = self._detector
+        self._detector = (sy // int(factor), sx // int(factor))
+        self._exp_shape = (self._exp_shape[0],) + self._detector
+        self._exp_dtype = dt
+
+    def get_dynamic_background(self, filter_domain=DOMAIN_FREQUENCY, std=None, truncate=4.0, dtype_out=None):
+        """The Gaussian-blurred image of every resident pattern (after the recorded background steps) as `dtype_out`
+        (None: the patterns' dtype): (m_all, sy, sx); `std` None: sx / 8 (include/kpdi.h,
+        kpdi_get_dynamic_background).  The resident patterns stay as they are."""
+        dt = self._exp_dtype if dtype_out is None else np.dtype(dtype_out)
+        out = np.empty((self._exp_shape[0],) + self._detector, dtype=dt)
+        check(self._f.get_dynamic_background(self._h, int(filter_domain), 0.0 if std is None else float(std),
+                                             float(truncate), dtype_code(dt), _ptr(out)))
+        return out
 
     def normalize_intensity(self, num_std=1, divide_by_square_root=False, dtype_out=None):
         """(p - mean) / (num_std * std [* sqrt(size)]) of every resident pattern into `dtype_out` (None: the patterns'

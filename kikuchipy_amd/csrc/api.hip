@@ -211,9 +211,83 @@ static void write_twiddles(float *tw, int sy, int sx) {
 
 }  // namespace kpdi
 
+namespace kpdi {
+
+// what of the problem depends on the detector shape and the signal mask (`keep`: the kept pixels, empty without a mask):
+// the pixel counts and the floats per prepared row, for the metric and arithmetic already set in the context.  Shared by
+// kpdi_set_problem and kpdi_downsample, which moves the problem to the binned detector.
+static void set_detector_layout(kpdi_ctx *c, int sy, int sx, bool have_mask, std::vector<int> keep) {
+  c->sy = sy;
+  c->sx = sx;
+  c->npix = sy * sx;
+  c->have_sig_mask = have_mask;
+  if (!have_mask) c->have_quad_desc = false;
+  c->k_kept = have_mask ? (int)keep.size() : c->npix;
+  c->kept_pixels = std::move(keep);
+  // floats per prepared row; the float16 form packs two pixels into one float: steps of 48 pixels
+  // (match16.hip).  `ndp` rows carry one extra column (prep.hip: centred evaluation), except in the float16 form
+  c->kpad = c->compute == KPDI_COMPUTE_F16
+                ? kpdi::round_up(c->k_kept, kpdi::f16_geometry(c->f16_waves).step) / 2
+                : kpdi::round_up(c->k_kept + (c->metric == KPDI_METRIC_NDP ? 1 : 0),
+                                 c->wide32 ? kpdi::F16_STEP / 2 : kpdi::TILE_K);
+  c->cnt.kpad = c->kpad;
+  c->cnt.k_kept = c->k_kept;
+}
+
+// the normalised Gaussian window of the dynamic background in either domain, its length, centre and boundary mode
+static int gaussian_taps(int filter_domain, double std, double truncate, std::vector<double> &taps, int *n_out,
+                         int *centre_out, int *reflect_out) {
+  int n;
+  if (filter_domain == KPDI_DOMAIN_FREQUENCY) {
+    // pattern/_pattern.py:604-613: n = int(truncate*std) samples of
+    // scipy.signal.windows.gaussian, normalised; centre from filters/fft_barnes.py:106-117
+    *n_out = n = (int)(truncate * std);
+    if (n < 1) return fail(KPDI_EINVAL, "Gaussian window of int(truncate*std) = %d samples", n);
+    taps.resize(n);
+    double sum = 0;
+    for (int i = 0; i < n; ++i) {
+      const double x = i - (n - 1) / 2.0;
+      taps[i] = exp(-0.5 * (x / std) * (x / std));
+      sum += taps[i];
+    }
+    for (double &t : taps) t /= sum;
+    *centre_out = n - 1 - (n - 1) / 2;
+    *reflect_out = 0;
+  } else if (filter_domain == KPDI_DOMAIN_SPATIAL) {
+    // scipy.ndimage.gaussian_filter(sigma=std, truncate=truncate), mode='reflect'
+    const int r = (int)(truncate * std + 0.5);
+    *n_out = n = 2 * r + 1;
+    taps.resize(n);
+    double sum = 0;
+    for (int i = 0; i < n; ++i) {
+      const double x = i - r;
+      taps[i] = exp(-0.5 / (std * std) * x * x);
+      sum += taps[i];
+    }
+    for (double &t : taps) t /= sum;
+    *centre_out = r;
+    *reflect_out = 1;
+  } else {
+    return fail(KPDI_EINVAL, "unknown filter domain %d", filter_domain);
+  }
+  return KPDI_OK;
+}
+
+// the kernels read the taps through a window of CONV_R outputs: zero padding on both sides
+static int upload_taps(kpdi_ctx *c, const std::vector<double> &taps) {
+  std::vector<double> padded(taps.size() + 2 * (kpdi::CONV_R - 1), 0.0);
+  std::copy(taps.begin(), taps.end(), padded.begin() + (kpdi::CONV_R - 1));
+  HIPCHK(c->taps.reserve(padded.size() * sizeof(double)));
+  HIPCHK(hipMemcpyAsync(c->taps.p, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // `padded` dies at scope exit
+  return KPDI_OK;
+}
+
+}  // namespace kpdi
+
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.8.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.9.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 
@@ -360,19 +434,9 @@ int kpdi_set_problem(kpdi_ctx *c, int sy, int sx, const uint8_t *signal_mask, in
   c->f16_waves = waves;
   c->wide32 = wide32;
   c->wide_mode = wide_mode;
-  c->kept_pixels = keep;
-  c->sy = sy;
-  c->sx = sx;
-  c->npix = npix;
-  c->have_sig_mask = signal_mask != nullptr;
-  c->k_kept = signal_mask ? (int)keep.size() : npix;
-  // floats per prepared row; the float16 form packs two pixels into one float: steps of 48 pixels
-  // (match16.hip).  `ndp` rows carry one extra column (prep.hip: centred evaluation), except in the float16 form
-  c->kpad = compute_dtype == KPDI_COMPUTE_F16
-                ? kpdi::round_up(c->k_kept, kpdi::f16_geometry(c->f16_waves).step) / 2
-                : kpdi::round_up(c->k_kept + (metric == KPDI_METRIC_NDP ? 1 : 0), wide32 ? kpdi::F16_STEP / 2 : kpdi::TILE_K);
   c->metric = metric;
   c->compute = compute_dtype;
+  kpdi::set_detector_layout(c, sy, sx, signal_mask != nullptr, std::move(keep));
   c->exact64 = exact64;
   c->keep_n = keep_n;
   c->have_problem = true;
@@ -380,8 +444,6 @@ int kpdi_set_problem(kpdi_ctx *c, int sy, int sx, const uint8_t *signal_mask, in
   c->run_valid = false;
   discard_pending(c);
   c->final_valid = false;
-  c->cnt.kpad = c->kpad;
-  c->cnt.k_kept = c->k_kept;
   return KPDI_OK;
 }
 
@@ -452,49 +514,15 @@ int kpdi_remove_dynamic_background(kpdi_ctx *c, int operation, int filter_domain
   if (std <= 0) std = c->sx / 8.0;  // signals/ebsd.py:648-649
   std::vector<double> taps;
   int n, centre, reflect;
-  if (filter_domain == KPDI_DOMAIN_FREQUENCY) {
-    // pattern/_pattern.py:604-613: n = int(truncate*std) samples of
-    // scipy.signal.windows.gaussian, normalised; centre from filters/fft_barnes.py:106-117
-    n = (int)(truncate * std);
-    if (n < 1) return fail(KPDI_EINVAL, "Gaussian window of int(truncate*std) = %d samples", n);
-    taps.resize(n);
-    double sum = 0;
-    for (int i = 0; i < n; ++i) {
-      const double x = i - (n - 1) / 2.0;
-      taps[i] = exp(-0.5 * (x / std) * (x / std));
-      sum += taps[i];
-    }
-    for (double &t : taps) t /= sum;
-    centre = n - 1 - (n - 1) / 2;
-    reflect = 0;
-  } else if (filter_domain == KPDI_DOMAIN_SPATIAL) {
-    // scipy.ndimage.gaussian_filter(sigma=std, truncate=truncate), mode='reflect'
-    const int r = (int)(truncate * std + 0.5);
-    n = 2 * r + 1;
-    taps.resize(n);
-    double sum = 0;
-    for (int i = 0; i < n; ++i) {
-      const double x = i - r;
-      taps[i] = exp(-0.5 / (std * std) * x * x);
-      sum += taps[i];
-    }
-    for (double &t : taps) t /= sum;
-    centre = r;
-    reflect = 1;
-  } else {
-    return fail(KPDI_EINVAL, "unknown filter domain %d", filter_domain);
-  }
+  rc = kpdi::gaussian_taps(filter_domain, std, truncate, taps, &n, &centre, &reflect);
+  if (rc) return rc;
   bool dummy = false;
   if (c->pend.dy) {  // a second dynamic step cannot join the recorded one
     rc = flush_preprocess(c, false, &dummy);
     if (rc) return rc;
   }
-  // the kernels read the taps through a window of CONV_R outputs: zero padding on both sides
-  std::vector<double> padded(taps.size() + 2 * (kpdi::CONV_R - 1), 0.0);
-  std::copy(taps.begin(), taps.end(), padded.begin() + (kpdi::CONV_R - 1));
-  HIPCHK(c->taps.reserve(padded.size() * sizeof(double)));
-  HIPCHK(hipMemcpyAsync(c->taps.p, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));  // `padded` dies at scope exit
+  rc = kpdi::upload_taps(c, taps);
+  if (rc) return rc;
   c->pend.dy = true;
   c->pend.dy_op = operation;
   c->pend.reflect = reflect;
@@ -931,6 +959,95 @@ int kpdi_neighbour_dot_products(kpdi_ctx *c, int ny, int nx, const uint8_t *foot
   }
   if (map_out) return results_to_host(c, map_out, a.map, n_out * esz);
   return KPDI_OK;  // (results_to_host synchronised: `taps` may die)
+}
+
+int kpdi_downsample(kpdi_ctx *c, int factor, int dtype_out) {
+  int rc = kpdi::check_patterns(c, "downsampling");
+  if (rc) return rc;
+  if (!kpdi::intensity_dtype(dtype_out))
+    return fail(KPDI_EINVAL, "dtype_out %d: downsampling writes uint8/int8/uint16/int16/float32/float64", dtype_out);
+  const int sy = c->sy, sx = c->sx;
+  if (factor < 2) return fail(KPDI_EINVAL, "binning factor %d must be an integer > 1", factor);
+  if (sy % factor || sx % factor)
+    return fail(KPDI_EINVAL, "binning factor %d must divide the detector shape (%d, %d)", factor, sy, sx);
+  if (c->have_sig_mask)
+    return fail(KPDI_EINVAL, "a signal mask is set for the %d x %d detector: call kpdi_set_problem without it, downsample, "
+                             "then set the mask of the binned shape", sy, sx);
+  if (!c->held.empty() || c->pending_hold.rows > 0)
+    return fail(KPDI_EINVAL, "dictionary chunks are held for the %d x %d detector: release them before downsampling", sy, sx);
+  const kpdi::DsPlan plan = kpdi::downsample_launch_plan(c->exp_dtype, sy, sx, factor, c->m_all);
+  if (plan.path < 0)
+    return fail(KPDI_EINVAL, "downsampling of %d x %d patterns by %d: no kernel path takes this shape", sy, sx, factor);
+  rc = kpdi::start_pattern_op(c);
+  if (rc) return rc;
+  const int ny = sy / factor, nx = sx / factor;
+  HIPCHK(c->int_out.reserve((size_t)c->m_all * ny * nx * kpdi::dtype_size(dtype_out)));
+  if (plan.path == 1) HIPCHK(c->op_ws.reserve(plan.workspace_bytes));
+  kpdi::DsLaunch a{};
+  a.src = c->exp_raw.p;
+  a.dtype = c->exp_dtype;
+  a.dst = c->int_out.p;
+  a.dtype_out = dtype_out;
+  a.n = c->m_all;
+  a.sy = sy;
+  a.sx = sx;
+  a.factor = factor;
+  kpdi::dtype_range(dtype_out, &a.omin, &a.omax);
+  a.workspace = c->op_ws.p;
+  a.workspace_bytes = c->op_ws.cap;
+  hipError_t e = kpdi::launch_downsample(a, c->stream);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "downsampling kernel: %s (dtype %d -> %d, %dx%d by %d)", hipGetErrorString(e), c->exp_dtype,
+                dtype_out, sy, sx, factor);
+  std::swap(c->exp_raw, c->int_out);
+  c->exp_dtype = dtype_out;
+  // the problem follows the patterns: the binned detector without a signal mask; metric, arithmetic and keep_n stay
+  // (there are no held chunks to release)
+  kpdi::set_detector_layout(c, ny, nx, false, {});
+  kpdi::patterns_changed(c);
+  return KPDI_OK;
+}
+
+int kpdi_get_dynamic_background(kpdi_ctx *c, int filter_domain, double std, double truncate, int dtype_out, void *out) {
+  int rc = kpdi::check_patterns(c, "the dynamic background");
+  if (rc) return rc;
+  if (!out) return fail(KPDI_EINVAL, "out is NULL");
+  if (!kpdi::intensity_dtype(dtype_out))
+    return fail(KPDI_EINVAL, "dtype_out %d: the dynamic background is written as uint8/int8/uint16/int16/float32/float64", dtype_out);
+  if (std <= 0) std = c->sx / 8.0;  // signals/ebsd.py:741-742
+  std::vector<double> taps;
+  int n, centre, reflect;
+  rc = kpdi::gaussian_taps(filter_domain, std, truncate, taps, &n, &centre, &reflect);
+  if (rc) return rc;
+  const size_t sbytes = kpdi::dynamic_background_scratch_bytes(c->sy, c->sx, c->m_all, nullptr);
+  if (sbytes == 0)
+    return fail(KPDI_EINVAL, "the dynamic background of %d x %d patterns: no kernel path takes this shape", c->sy, c->sx);
+  rc = kpdi::start_pattern_op(c);
+  if (rc) return rc;
+  rc = kpdi::upload_taps(c, taps);
+  if (rc) return rc;
+  const size_t obytes = (size_t)c->m_all * c->npix * kpdi::dtype_size(dtype_out);
+  HIPCHK(c->int_out.reserve(obytes));
+  HIPCHK(c->op_ws.reserve(sbytes));
+  kpdi::DbLaunch a{};
+  a.src = c->exp_raw.p;
+  a.dtype = c->exp_dtype;
+  a.dst = c->int_out.p;
+  a.dtype_out = dtype_out;
+  a.n = c->m_all;
+  a.sy = c->sy;
+  a.sx = c->sx;
+  a.taps_padded = c->taps.as<double>();
+  a.ntaps = n;
+  a.centre = centre;
+  a.spatial = reflect;
+  a.scratch = (double *)c->op_ws.p;
+  a.scratch_bytes = c->op_ws.cap;
+  hipError_t e = kpdi::launch_dynamic_background(a, c->stream);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "dynamic background kernel: %s (dtype %d -> %d, %dx%d)", hipGetErrorString(e), c->exp_dtype,
+                dtype_out, c->sy, c->sx);
+  return kpdi::results_to_host(c, out, c->int_out.p, obytes);
 }
 
 size_t kpdi_dtype_size(int dtype) { return kpdi::dtype_size(dtype); }

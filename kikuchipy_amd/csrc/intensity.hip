@@ -142,17 +142,6 @@ __device__ __forceinline__ int int_load4(const T *p, int npix, int q, bool vec, 
   return m;
 }
 
-// ndarray.astype(TO) of the arithmetic's result
-template <typename TO, typename V>
-__device__ __forceinline__ TO int_cast(V y) {
-  if constexpr (std::is_floating_point<TO>::value) {
-    return (TO)y;
-  } else {
-    const int32_t i = (y >= (V)-2147483648.0 && y < (V)2147483648.0) ? (int32_t)y : INT32_MIN;  // NaN: INT32_MIN
-    return (TO)(uint32_t)i;  // the low bits
-  }
-}
-
 // np.maximum / np.minimum (NaN-propagating), as np.clip = minimum(maximum(p, lo), hi)
 template <typename V>
 __device__ __forceinline__ V int_clip(V x, V lo, V hi) {
@@ -180,7 +169,7 @@ __device__ __forceinline__ void int_store(const T *p, TO *__restrict__ o, int np
     const int c = int_load4(p, npix, q, vec, v);
     Quad<TO> u;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) u.v[e] = int_cast<TO>(m((V)v[e]));
+    for (int e = 0; e < 4; ++e) u.v[e] = astype_cast<TO>(m((V)v[e]));
     if (vec) {
       *reinterpret_cast<Quad<TO> *>(o + 4 * q) = u;
     } else {

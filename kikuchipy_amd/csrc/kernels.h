@@ -7,6 +7,7 @@
 
 #include "clahe_plan.h"
 #include "neighbours_plan.h"
+#include "downsample_plan.h"
 
 namespace kpdi {
 
@@ -438,5 +439,31 @@ struct NbDotLaunch {
   void *map;                              // [(row1 - row0) * nx] or NULL
 };
 hipError_t launch_neighbour_dot(const NbDotLaunch &a, hipStream_t s);
+
+// ---- downsampling (downsample.hip) ---------------------------------------------------
+struct DsLaunch {
+  const void *src; int dtype;      // n x sy x sx of `dtype`, device
+  void *dst; int dtype_out;        // n x (sy / factor) x (sx / factor) of `dtype_out`, device; not `src`
+  int64_t n; int sy, sx, factor;   // factor >= 2 divides sy and sx
+  float omin, omax;                // dtype range of `dtype_out`
+  void *workspace; size_t workspace_bytes;  // path 1 of downsample_plan.h
+};
+// the plan launch_downsample follows (KPDI_DOWNSAMPLE_PATH=1, read at each call, forces path 1)
+DsPlan downsample_launch_plan(int dtype, int sy, int sx, int factor, int64_t n);
+hipError_t launch_downsample(const DsLaunch &a, hipStream_t s);
+
+// ---- the dynamic background itself (preproc.hip) ---------------------------------------
+struct DbLaunch {
+  const void *src; int dtype;      // n x sy x sx of `dtype`, device, only read
+  void *dst; int dtype_out;        // n x sy x sx of `dtype_out`, device
+  int64_t n; int sy, sx;
+  const double *taps_padded;       // as PreLaunch::taps_padded
+  int ntaps, centre;
+  int spatial;                     // 0: the FFT filter's correlation (edge replicate, float32 in and out),
+                                   // 1: scipy.ndimage.gaussian_filter (reflect, every pass stored in `dtype_out`)
+  double *scratch; size_t scratch_bytes;  // dynamic_background_scratch_bytes
+};
+size_t dynamic_background_scratch_bytes(int sy, int sx, int64_t n, int *grid_out);
+hipError_t launch_dynamic_background(const DbLaunch &a, hipStream_t s);
 
 }  // namespace kpdi

@@ -5,6 +5,9 @@
 #include "kernels.h"
 #include "../../include/kpdi.h"
 
+#include <cstdint>
+#include <type_traits>
+
 namespace kpdi {
 
 constexpr int NORM_NDP_CENTRED = 2;  // internal value of the `metric` argument: `ndp` in its centred form (prep.hip)
@@ -85,6 +88,25 @@ template <typename T>
 struct alignas(sizeof(T) * 4) Quad {
   T v[4];
 };
+
+// (pattern - imin) / float(imax - imin) * (omax - omin) + omin, float32: the reference's _rescale_with_min_max
+// (pattern/_pattern.py:96-111), every operation rounded on its own (the library builds with -ffp-contract=off) and an
+// IEEE division.  Shared by the background-removal kernels (preproc.hip) and downsampling (downsample.hip).
+__device__ __forceinline__ float rescale(float v, float imin, float irange, float orange, float omin) {
+  return ((v - imin) / irange) * orange + omin;
+}
+
+// ndarray.astype(TO) of a floating-point value on x86-64: to an integer dtype truncate to int32 (NaN and values outside
+// int32 give INT32_MIN), then keep the low 8 or 16 bits; to a float dtype round to nearest
+template <typename TO, typename V>
+__device__ __forceinline__ TO astype_cast(V y) {
+  if constexpr (std::is_floating_point<TO>::value) {
+    return (TO)y;
+  } else {
+    const int32_t i = (y >= (V)-2147483648.0 && y < (V)2147483648.0) ? (int32_t)y : INT32_MIN;  // NaN: INT32_MIN
+    return (TO)(uint32_t)i;  // the low bits
+  }
+}
 
 // Four consecutive values of a raw pattern.  Raw patterns are read exactly once per preparation: the load is marked
 // non-temporal (KPDI_PREP_NT, default on) so that the stream does not push the prepared matrices the match kernel is

@@ -76,12 +76,7 @@ __device__ __forceinline__ void block_minmax(float &mn, float &mx, float *red) {
   }
 }
 
-// (pattern - imin) / float(imax - imin) * (omax - omin) + omin, float32 (pattern/_pattern.py:110-111)
-__device__ __forceinline__ float rescale(float v, float imin, float irange, float orange, float omin) {
-  return ((v - imin) / irange) * orange + omin;
-}
-
-// The same with the division by a WORKGROUP-UNIFORM divisor taken apart: an IEEE float32 division is, on this chip, a
+// rescale() of prep_device.h with the division by a WORKGROUP-UNIFORM divisor taken apart: an IEEE float32 division is, on this chip, a
 // reciprocal refined once, a quotient estimate and two residual corrections (what the compiler emits around
 // v_div_scale / v_div_fixup, which only matter for operands near the ends of the exponent range).  The refined reciprocal
 // depends on the divisor alone, so it is computed once per pass and each pixel pays five instructions instead of eleven;
@@ -157,7 +152,8 @@ __device__ __forceinline__ int wrap_index(int i, int n) {
 // changes nothing), so the results are bit-identical to it.
 constexpr int CONV_CHUNK = 30;
 constexpr int CONV_RU = 16;  // outputs per job of the unrolled form
-template <int NT, bool REFLECT, int THREADS, typename Load, typename Store>
+// OutT: what an accumulated output is rounded to before `store` sees it (float: the reference's float32 intermediates)
+template <int NT, bool REFLECT, int THREADS, typename OutT = float, typename Load, typename Store>
 __device__ __forceinline__ void correlate_slow_axis(int len, int other, int ld, const double *__restrict__ tp, int n,
                                                     int centre, Load load, Store store) {
   if (NT > 0) {
@@ -205,7 +201,7 @@ __device__ __forceinline__ void correlate_slow_axis(int len, int other, int ld, 
     }
 #pragma unroll
     for (int i = 0; i < CONV_R; ++i)
-      if (a0 + i < len) store(a0 + i, o, (float)acc[i]);
+      if (a0 + i < len) store(a0 + i, o, (OutT)acc[i]);
   }
 }
 
@@ -458,6 +454,97 @@ __global__ __launch_bounds__(PP_THREADS) void dynamic_stream_kernel(PreArgs a, c
     for (int i = tid; i < npix; i += PP_THREADS) p[i] = cast_out<T>(rescale(yb[i], mn, irange, orange, a.omin));
     __syncthreads();  // the scratch is reused by the next pattern
   }
+}
+
+// ---- the dynamic background itself (kpdi_get_dynamic_background): the filtering stage above with an epilogue that
+// writes the blurred pattern instead of removing it and rescaling.  In the reference's order (signals/ebsd.py:767-779)
+// the pattern is cast to the output dtype TO first, then filtered:
+//   frequency (SPATIAL = false): _fft_filter pads the cast pattern into float32 and returns float32, stored into TO by
+//     astype - as above, the edge-replicating correlation with the normalised window, two 1-D passes accumulated in
+//     float64; the intermediate stays float64 here (the FFT has none), the result is rounded to float32 and cast.
+//   spatial (SPATIAL = true): scipy.ndimage.gaussian_filter on an array of dtype TO: correlate1d along the detector's
+//     rows axis first, then along the columns axis, each accumulated in float64 in SciPy's order and STORED IN TO -
+//     integers by the C conversion, truncation toward zero - so the second pass reads the quantised first one.
+// Persistent workgroups; the pattern is read from memory (L2 after its first touch), the transposed intermediate lives
+// in a global scratch of npix doubles per workgroup.
+// scipy.ndimage.correlate1d for a symmetric kernel of 2 r + 1 weights (taps[r] the centre) along the slow axis of a
+// [len][other] array, 'reflect' boundary, in SciPy's order of operations - it decides the last bit and with it the side
+// of an integer the truncating store falls on: t = in[l] w[r]; for d = r ... 1: t += (in[l - d] + in[l + d]) w[r - d],
+// multiply and add rounded separately (-ffp-contract=off).  One output per thread, consecutive threads consecutive `o`.
+template <int THREADS, typename Load, typename Store>
+__device__ __forceinline__ void correlate_symmetric_slow_axis(int len, int other, int ld, const double *__restrict__ taps,
+                                                              int r, Load load, Store store) {
+  for (int job = threadIdx.x; job < len * other; job += THREADS) {
+    const int l = job / other, o = job - l * other;
+    double t = load(l * ld + o) * taps[r];
+    for (int d = r; d >= 1; --d)
+      t += (load(wrap_index<true>(l - d, len) * ld + o) + load(wrap_index<true>(l + d, len) * ld + o)) * taps[r - d];
+    store(l, o, t);
+  }
+}
+
+template <typename T, typename TO, bool SPATIAL>
+__global__ __launch_bounds__(PP_THREADS) void dynamic_background_kernel(DbLaunch a, const double *__restrict__ tp) {
+  const int sy = a.sy, sx = a.sx, npix = sy * sx;
+  double *tt = a.scratch + (size_t)blockIdx.x * npix;
+  for (int64_t pat = blockIdx.x; pat < a.n; pat += gridDim.x) {
+    const T *p = (const T *)a.src + (size_t)pat * npix;
+    TO *o = (TO *)a.dst + (size_t)pat * npix;
+    auto in = [&](int i) {
+      const TO v = astype_cast<TO>((double)p[i]);  // get_dask_array(self, dtype=dtype_out)
+      if constexpr (SPATIAL) return (double)v;
+      else return (double)(float)v;
+    };
+    // axis 0 (detector rows) first, as scipy.ndimage.gaussian_filter does; out(r, c) -> tt[c * sy + r]
+    if constexpr (SPATIAL) {
+      const double *taps = tp + (CONV_R - 1);
+      correlate_symmetric_slow_axis<PP_THREADS>(sy, sx, sx, taps, a.centre, in,
+                                                [&](int r, int c, double v) { tt[c * sy + r] = (double)astype_cast<TO>(v); });
+      __syncthreads();
+      correlate_symmetric_slow_axis<PP_THREADS>(sx, sy, sy, taps, a.centre, [&](int i) { return tt[i]; },
+                                                [&](int c, int r, double v) { o[r * sx + c] = astype_cast<TO>(v); });
+    } else {
+      correlate_slow_axis<0, false, PP_THREADS, double>(sy, sx, sx, tp, a.ntaps, a.centre, in,
+                                                        [&](int r, int c, double v) { tt[c * sy + r] = v; });
+      __syncthreads();
+      correlate_slow_axis<0, false, PP_THREADS, double>(
+          sx, sy, sy, tp, a.ntaps, a.centre, [&](int i) { return tt[i]; },
+          [&](int c, int r, double v) { o[r * sx + c] = astype_cast<TO>((float)v); });
+    }
+    __syncthreads();  // the scratch is reused by the next pattern
+  }
+}
+
+// one slot of npix doubles per persistent workgroup, at most 1024 of them and PATTERN_WORKSPACE_CAP (256 MB) in all;
+// 0: a single pattern's intermediate does not fit (above 5792 x 5792), no path takes the shape
+size_t dynamic_background_scratch_bytes(int sy, int sx, int64_t n, int *grid_out) {
+  const size_t per = (size_t)sy * sx * sizeof(double);
+  if (grid_out) *grid_out = 0;
+  if (sy < 1 || sx < 1 || n < 1 || per > PATTERN_WORKSPACE_CAP) return 0;
+  const int64_t grid = std::min<int64_t>(std::min<int64_t>(n, 1024), (int64_t)(PATTERN_WORKSPACE_CAP / per));
+  if (grid_out) *grid_out = (int)grid;
+  return (size_t)grid * per;
+}
+
+template <typename T, typename TO>
+static hipError_t launch_db_tt(const DbLaunch &a, int grid, hipStream_t s) {
+  if (a.spatial)
+    hipLaunchKernelGGL((dynamic_background_kernel<T, TO, true>), dim3((unsigned)grid), dim3(PP_THREADS), 0, s, a, a.taps_padded);
+  else
+    hipLaunchKernelGGL((dynamic_background_kernel<T, TO, false>), dim3((unsigned)grid), dim3(PP_THREADS), 0, s, a, a.taps_padded);
+  return hipGetLastError();
+}
+
+hipError_t launch_dynamic_background(const DbLaunch &a, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  int grid = 0;
+  const size_t need = dynamic_background_scratch_bytes(a.sy, a.sx, a.n, &grid);
+  if (need == 0 || !a.src || !a.dst || !a.taps_padded || a.ntaps < 1 || !a.scratch || a.scratch_bytes < need ||
+      (int64_t)a.sy * a.sx >= ((int64_t)1 << 30))
+    return hipErrorInvalidValue;
+  return with_pattern_type(a.dtype, [&](auto t) {
+    return with_pattern_type(a.dtype_out, [&](auto to) { return launch_db_tt<decltype(t), decltype(to)>(a, grid, s); });
+  });
 }
 
 size_t preprocess_scratch_floats(int sy, int sx, int64_t n, int *grid_out) {

@@ -1,8 +1,11 @@
 from kikuchipy_amd.pattern._pattern import (  # noqa: F401
     adaptive_histogram_equalization,
     adaptive_histogram_equalization_stack,
+    downsample_stack,
     fft_filter_stack,
     fft_frequency_vectors,
+    get_dynamic_background,
+    get_dynamic_background_stack,
     get_image_quality,
     normalize_intensity,
     normalize_intensity_stack,

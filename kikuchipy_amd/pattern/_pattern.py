@@ -14,6 +14,9 @@ one HIP workgroup per pattern (csrc/preproc.hip).  `get_image_quality`
 pattern in one HIP workgroup (csrc/intensity.hip).  `adaptive_histogram_equalization` (pattern/_pattern.py:810-840)
 and `adaptive_histogram_equalization_stack`, which `EBSD.adaptive_histogram_equalization`
 (signals/_kikuchipy_signal.py:340-470) runs, equalize every pattern in one HIP workgroup (csrc/clahe.hip).
+`downsample_stack` (signals/ebsd.py:1113-1219) bins every pattern and changes the detector shape
+(csrc/downsample.hip); `get_dynamic_background` / `get_dynamic_background_stack` (pattern/_pattern.py:634-695,
+signals/ebsd.py:698-803) return the blur that `remove_dynamic_background` removes (csrc/preproc.hip).
 """
 
 import numbers
@@ -374,6 +377,66 @@ def normalize_intensity_stack(patterns, num_std=1, divide_by_square_root=False, 
     dt = intensity_dtype_out(dtype_out, patterns.dtype)
     return _process(patterns, lambda c: c.normalize_intensity(num_std, divide_by_square_root, dt), context, device,
                     contexts)
+
+
+def check_binning_factor(factor, sig_shape):
+    """The checks of `EBSD.downsample` (signals/ebsd.py:1167-1179) for patterns of `sig_shape` (sy, sx), with its
+    messages: shape and remainder in HyperSpy's (x, y) order."""
+    if not isinstance(factor, int) or factor <= 1:
+        raise ValueError(f"Binning factor {factor} must be an integer > 1")
+    sig_shape_old = tuple(int(v) for v in sig_shape[::-1])
+    rest = np.mod(sig_shape_old, factor)
+    if not all(rest == 0):
+        raise ValueError(
+            f"Binning factor {factor} must be a divisor of the initial pattern "
+            f"shape {sig_shape_old}, but {tuple(int(r) for r in rest)} pixels remain.\n"
+            "You might try to crop away these pixels first using EBSD.crop()."
+        )
+    return int(factor)
+
+
+def downsample_stack(patterns, factor, dtype_out=None, *, context=None, device=0, contexts=None):
+    """`EBSD.downsample` on an array (..., sy, sx): every pattern binned by the integer `factor`, which must divide sy
+    and sx, and rescaled to the range of `dtype_out` (default: the patterns' dtype; `DTYPE_RANGE`): a new array
+    (..., sy / factor, sx / factor) of `dtype_out`.  The reference's `_downsample2d` (pattern/_pattern.py:776-807) bit
+    for bit: float32 sums in its order, float32 rescaling, `astype`.  A pattern holding a NaN, or whose binned image is
+    constant (the reference's 0 / 0), becomes NaN for float `dtype_out` and 0 for integer ones (csrc/downsample.hip)."""
+    patterns = np.asarray(patterns)
+    if patterns.ndim < 2:
+        raise ValueError("patterns need at least the two detector axes")
+    factor = check_binning_factor(factor, patterns.shape[-2:])
+    dt = intensity_dtype_out(dtype_out, patterns.dtype)
+    return _process(patterns, lambda c: c.downsample(factor, dt), context, device, contexts)
+
+
+def get_dynamic_background_stack(patterns, filter_domain="frequency", std=None, truncate=4.0, dtype_out=None, *,
+                                 context=None, device=0, contexts=None):
+    """`EBSD.get_dynamic_background` on an array (..., sy, sx): the Gaussian-blurred image of every pattern - what
+    `remove_dynamic_background` subtracts or divides away - as `dtype_out` (default: the patterns' dtype).  As in the
+    reference (signals/ebsd.py:767-779) the patterns are cast to `dtype_out` first.  "frequency": the cast pattern as
+    float32 through the FFT filter's correlation with a Gaussian window of int(truncate * std) samples, stored into
+    `dtype_out` (integers truncate); within the FFT's float32 round-off of the reference.  "spatial":
+    `scipy.ndimage.gaussian_filter(sigma=std, truncate=truncate)` on the cast pattern, whose two passes are each stored
+    in `dtype_out`.  `std` defaults to an eighth of the pattern width."""
+    if filter_domain not in _DOMAINS:
+        raise ValueError(f"{filter_domain} must be either of {list(_DOMAINS)}")
+    patterns = np.asarray(patterns)
+    if patterns.ndim < 2:
+        raise ValueError("patterns need at least the two detector axes")
+    dt = intensity_dtype_out(dtype_out, patterns.dtype)
+    if std is None:
+        std = patterns.shape[-1] / 8
+    return _process(patterns, lambda c: None, context, device, contexts,
+                    collect=lambda c: c.get_dynamic_background(_DOMAINS[filter_domain], std, truncate, dt))
+
+
+def get_dynamic_background(pattern, filter_domain="frequency", std=None, truncate=4.0, *, context=None, device=0):
+    """pattern/_pattern.py:634-695 on one 2-D pattern: its dynamic background in the pattern's data type; `std`
+    defaults to `pattern.shape[1] / 8`."""
+    pattern = np.asarray(pattern)
+    if pattern.ndim != 2:
+        raise ValueError(f"one 2-D pattern is filtered, not an array of shape {pattern.shape}")
+    return get_dynamic_background_stack(pattern, filter_domain, std, truncate, context=context, device=device)
 
 
 CLAHE_MAX_NBINS = 16384  # csrc/clahe_plan.h: 2**14 grey levels

@@ -428,6 +428,58 @@ class EBSD:
             return None
         return self._like(out)
 
+    def get_dynamic_background(self, filter_domain="frequency", std=None, truncate=4.0, dtype_out=None,
+                               show_progressbar=None, lazy_output=None, *, devices=None, **kwargs):
+        """signals/ebsd.py:698-803: the dynamic background of every pattern - the Gaussian blur that
+        `remove_dynamic_background` removes - in a new signal of `dtype_out` (default: the data's dtype) with this
+        one's custom attributes (`kikuchipy_amd.pattern.get_dynamic_background_stack`).  The reference hands `**kwargs`
+        to its SciPy filter function; this engine has none, so any is refused.  `show_progressbar` / `lazy_output` as in
+        `remove_static_background` (`lazy_output=True` returns an ordinary signal)."""
+        if filter_domain not in ("frequency", "spatial"):
+            raise ValueError(f"{filter_domain} must be either of ['frequency', 'spatial']")
+        if kwargs:
+            raise TypeError(f"get_dynamic_background() got keyword arguments {sorted(kwargs)} for the reference's SciPy "
+                            "filter function, which this GPU engine does not call")
+        _pattern.intensity_dtype_out(dtype_out, self.data.dtype)  # before any GPU work
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        out = _pattern.get_dynamic_background_stack(np.asarray(self.data), filter_domain, std, truncate, dtype_out,
+                                                    context=None if contexts else self.context, contexts=contexts)
+        return self._like(out)
+
+    def downsample(self, factor, dtype_out=None, show_progressbar=None, inplace=True, lazy_output=None, *,
+                   devices=None):
+        """signals/ebsd.py:1113-1219: bin every pattern by the integer `factor`, a divisor of both detector axes, and
+        rescale it to the range of `dtype_out` (default: the data's dtype; `kikuchipy_amd.pattern.downsample_stack`).
+        As in the reference the static background, if any, is binned and rescaled the same way into `dtype_out` (on
+        the GPU, as a stack of one pattern), the detector becomes a copy with the new shape and `binning * factor`, and
+        `xmap` carries over; with `inplace=False` this signal, its detector and its background stay untouched.
+        `show_progressbar` / `lazy_output` as in `remove_static_background`."""
+        if lazy_output and inplace:
+            raise ValueError("'lazy_output=True' requires 'inplace=False'")
+        factor = _pattern.check_binning_factor(factor, self._signal_shape_rc)
+        dt = _pattern.intensity_dtype_out(dtype_out, self.data.dtype)  # before any GPU work
+        static_bg = self.static_background
+        if static_bg is not None:
+            if hasattr(static_bg, "compute"):
+                static_bg = static_bg.compute()
+            static_bg = _pattern.downsample_stack(np.asarray(static_bg), factor, dt, context=self.context)
+        detector = self.detector.deepcopy()  # (the default detector when none was set: the reference always has one)
+        detector.shape = tuple(n // factor for n in self._signal_shape_rc)
+        detector.binning = detector.binning * factor
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        data = _pattern.downsample_stack(np.asarray(self.data), factor, dt, context=None if contexts else self.context,
+                                         contexts=contexts)
+        out = self if inplace else EBSD(data, None, self.xmap, self.step_sizes, self.scan_unit, self._device,
+                                        self._devices)
+        out.data = data
+        out._static_background = static_bg
+        out._detector = detector
+        if not inplace:
+            if hasattr(self, "original_metadata"):
+                out.original_metadata = self.original_metadata
+            return out
+        return None
+
     def get_image_quality(self, normalize=True, show_progressbar=None, *, devices=None):
         """signals/ebsd.py:1312-1375: Q of every pattern (`kikuchipy_amd.pattern.get_image_quality` with the default
         frequency vectors), float32 of the navigation shape (0-d without navigation axes).  `show_progressbar` is
