@@ -169,24 +169,220 @@ __device__ __forceinline__ void scan16(f32x16 (&acc)[4], float (&best)[KMAX], in
 constexpr int CAND_CAP = KPDI16_CAP;  // a multiple of 16
 constexpr int CAND_CAP_PLAIN = 8;
 
+// ---- a list in its scratch home (`hs` / `hi`: wave-uniform, entry j at [j * 64 + lane]), N entries in chunks of 16
+// (chunk_base above)
+template <int N>
+__device__ __forceinline__ void list_load(float *hs, int *hi, unsigned ulane, float (&best)[N], int (&bidx)[N]) {
+#pragma unroll
+  for (int q = 0; q < (N + 15) / 16; ++q) {
+    const float *ps = chunk_base(hs, q);
+    const int *pi = chunk_base(hi, q);
+#pragma unroll
+    for (int j = 16 * q; j < N && j < 16 * q + 16; ++j) {
+      best[j] = ps[(j - 16 * q) * 64 + ulane];
+      bidx[j] = pi[(j - 16 * q) * 64 + ulane];
+    }
+  }
+}
+template <int N>
+__device__ __forceinline__ void list_store(float *hs, int *hi, unsigned ulane, const float (&best)[N], const int (&bidx)[N]) {
+#pragma unroll
+  for (int q = 0; q < (N + 15) / 16; ++q) {
+    float *ps = chunk_base(hs, q);
+    int *pi = chunk_base(hi, q);
+#pragma unroll
+    for (int j = 16 * q; j < N && j < 16 * q + 16; ++j) {
+      ps[(j - 16 * q) * 64 + ulane] = best[j];
+      pi[(j - 16 * q) * 64 + ulane] = bidx[j];
+    }
+  }
+}
+// N entries of "no entry" into a home (all lists of a lane at once)
+template <int N>
+__device__ __forceinline__ void list_clear(float *hs, int *hi, unsigned ulane) {
+#pragma unroll
+  for (int c = 0; c < (N + 15) / 16; ++c) {
+    float *ps = chunk_base(hs, c);
+    int *pi = chunk_base(hi, c);
+#pragma unroll
+    for (int j = 16 * c; j < N && j < 16 * c + 16; ++j) {
+      ps[(j - 16 * c) * 64 + ulane] = -INFINITY;
+      pi[(j - 16 * c) * 64 + ulane] = INT_MAX;
+    }
+  }
+}
+// ---- developer builds (tools/build_variant.sh): cycle counters and statistics of ONE kernel, printed from it.  The
+// kernel and its stages call the probe's methods at fixed points; in the shipped build the four flags are false and every method folds to nothing.
+//   KPDI16_TIME_PHASES  cycles of a launch's phases (tools/probes/share_step.py; profiles/r06_launch_phases.txt)
+//   KPDI16_TIME_EPI     where the cycles between tiles go (tools/probes/one_step.py)
+//   KPDI16_EPI_STATS    per tile, what the epilogue of ONE wave did (tools/probes/one_step.py; profiles/r05_f32_tile_time.txt)
+//   KPDI16_EPI_FINE     cycles of the three parts of a block's epilogue (same tools, same record)
+#ifdef KPDI16_TIME_PHASES
+constexpr bool PROBE_PHASES = true;
+#else
+constexpr bool PROBE_PHASES = false;
+#endif
+#ifdef KPDI16_TIME_EPI
+constexpr bool PROBE_EPI = true;
+#else
+constexpr bool PROBE_EPI = false;
+#endif
+#ifdef KPDI16_EPI_STATS
+constexpr bool PROBE_STATS = true;
+#else
+constexpr bool PROBE_STATS = false;
+#endif
+#ifdef KPDI16_EPI_FINE
+constexpr bool PROBE_FINE = true;
+#else
+constexpr bool PROBE_FINE = false;
+#endif
+struct Probe16 {
+  typedef unsigned long long u64;
+  u64 ph_t0, ph_prologue = 0, ph_first_loop = 0, ph_first_epi = 0, ph_loop_end = 0, ph_epi_t0 = 0;
+  u64 ph_fs_bound = 0, ph_fs_loop = 0, fs0 = 0, fs2 = 0;
+  int ph_fs_iters = 0, ph_fs_inserts = 0;
+  int st_hot = 0, st_iter = 0, st_cand = 0;
+  u64 st_t0 = 0;
+  u64 fine_screen = 0, fine_pm = 0, fine_loop = 0, f0 = 0, f1 = 0, f2 = 0;
+  int fine_blocks = 0;
+  u64 epi_cycles = 0, epi_drain = 0, epi_t0 = 0, kern_t0 = 0;
+  static __device__ __forceinline__ u64 now() { return __builtin_readcyclecounter(); }
+  __device__ __forceinline__ Probe16() : ph_t0(PROBE_PHASES ? now() : 0) {}
+  __device__ __forceinline__ void mark_prologue() {
+    if (PROBE_PHASES) ph_prologue = now() - ph_t0;
+  }
+  __device__ __forceinline__ void loop_begin() {
+    if (PROBE_EPI) kern_t0 = now();
+  }
+  // behind a tile's last step
+  __device__ __forceinline__ void tile_begin(int tiles_done) {
+    if (PROBE_EPI) epi_t0 = now();
+    if (PROBE_PHASES) {
+      ph_epi_t0 = now();
+      if (tiles_done == 0) ph_first_loop = ph_epi_t0 - ph_t0 - ph_prologue;
+    }
+  }
+  __device__ __forceinline__ void drain_done() {
+    if (PROBE_EPI) epi_drain += now() - epi_t0;
+    if (PROBE_STATS) {
+      st_hot = st_iter = st_cand = 0;
+      st_t0 = now();
+    }
+  }
+  // a block of 16 accumulator registers: its screen, the mask of a hot block, the append loop
+  __device__ __forceinline__ void block_begin() {
+    if (PROBE_FINE) f0 = now();
+  }
+  __device__ __forceinline__ void hot_block() {
+    if (PROBE_FINE) f1 = now();
+    if (PROBE_STATS) ++st_hot;
+  }
+  __device__ __forceinline__ void mask_done(unsigned &pm) {
+    if (PROBE_FINE) {
+      asm volatile("" : "+v"(pm));
+      f2 = now();
+    }
+  }
+  __device__ __forceinline__ void append_iteration(unsigned pm) {
+    if (PROBE_STATS) {
+      ++st_iter;
+      st_cand += __builtin_popcountll(__builtin_amdgcn_ballot_w64(pm != 0));
+    }
+  }
+  __device__ __forceinline__ void hot_block_end() {
+    if (PROBE_FINE) {
+      const u64 f3 = now();
+      fine_screen += f1 - f0;
+      fine_pm += f2 - f1;
+      fine_loop += f3 - f2;
+      ++fine_blocks;
+    }
+  }
+  __device__ __forceinline__ void tile_end(int tiles_done, bool first_fast, int wv, int lane) {
+    if (PROBE_EPI) epi_cycles += now() - epi_t0;
+    if (PROBE_STATS) {
+      const u64 dt = now() - st_t0;
+      if (blockIdx.x == 100 && lane == 0 && wv == 0)
+        printf("tile %d: %llu cycles, %d hot blocks of 16, %d loop iterations, %d candidates of the wave, first_fast %d\n", tiles_done, dt,
+               st_hot, st_iter, st_cand, (int)first_fast);
+    }
+    if (PROBE_PHASES) {
+      if (tiles_done == 0) ph_first_epi = now() - ph_epi_t0;
+      ph_loop_end = now() - ph_t0;
+    }
+  }
+  __device__ __forceinline__ void loop_report(int tiles_done, int wv, int lane) {
+    if (PROBE_FINE && blockIdx.x == 100 && lane == 0)
+      printf("wave %d: %d hot blocks: screen %llu, mask %llu, loop %llu cycles per hot block\n", wv, fine_blocks, fine_screen / fine_blocks,
+             fine_pm / fine_blocks, fine_loop / fine_blocks);
+    if (PROBE_EPI && (blockIdx.x == 0 || blockIdx.x == 100) && lane == 0)
+      printf("block %d wave %d: %d tiles, %llu cycles between tiles (%llu of them waiting for the last MFMAs) of %llu in the tile loop "
+             "(%.2f %%)\n", (int)blockIdx.x, wv, tiles_done, epi_cycles, epi_drain, now() - kern_t0,
+             100.0 * epi_cycles / (double)(now() - kern_t0));
+  }
+  // the final stage: its bound, a batch of 16 buffered candidates (direct path: stores; sorted path: insertions)
+  __device__ __forceinline__ void final_begin() {
+    if (PROBE_PHASES) fs0 = now();
+  }
+  __device__ __forceinline__ void final_bound(float &tf) {
+    if (PROBE_PHASES) {
+      asm volatile("" : "+v"(tf));
+      ph_fs_bound += now() - fs0;
+    }
+  }
+  __device__ __forceinline__ void final_direct_begin() {
+    if (PROBE_PHASES) fs2 = now();
+  }
+  __device__ __forceinline__ void final_batch_begin(unsigned &pm) {
+    if (PROBE_PHASES) {
+      asm volatile("" : "+v"(pm));
+      fs2 = now();
+    }
+  }
+  __device__ __forceinline__ void final_insert() {
+    if (PROBE_PHASES) ++ph_fs_inserts;
+  }
+  __device__ __forceinline__ void final_batch_end() {
+    if (PROBE_PHASES) {
+      ph_fs_loop += now() - fs2;
+      ++ph_fs_iters;
+    }
+  }
+  __device__ __forceinline__ void report(int wv, int lane) {
+    if (PROBE_PHASES) {
+      const u64 end = now() - ph_t0;
+      if ((blockIdx.x == 0 || blockIdx.x == 100 || blockIdx.x == 255) && lane == 0 && wv == 0)
+        printf("block %d: prologue %llu, first tile's steps %llu, first epilogue %llu, tile loop ends at %llu, final stage %llu, kernel %llu cycles "
+               "(shader cycles); final stage: bound loads %llu, insert loops %llu (%d batches, %d insertions)\n", (int)blockIdx.x, ph_prologue,
+               ph_first_loop, ph_first_epi, ph_loop_end, end - ph_loop_end, end, ph_fs_bound, ph_fs_loop, ph_fs_iters, ph_fs_inserts);
+    }
+  }
+};
+
+// ---- a candidate that passed the screen into the lane's candidate buffer (`c` entries so far, `cap` at most; `mx`:
+// the best score appended from this tile; a full buffer: `overflow`) - shared by the two append forms of the epilogue
+__device__ __forceinline__ void append16(float *bs, int *bi, unsigned ulane, int cap, int &c, float &mx, bool &overflow, float v,
+                                         int idx) {
+  if (c < cap) {
+    bs[c * 64 + ulane] = v;
+    bi[c * 64 + ulane] = idx;
+    ++c;
+    mx = fmaxf(mx, v);
+  } else {
+    overflow = true;
+  }
+}
+
 template <int KMAX, bool BOUNDED, int WAVES, bool F32 = false>
 __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArgs a, float *ls_scores, int *ls_idx) {
   static_assert(!F32 || WAVES == 4, "the float32 form runs one wave per SIMD");
   typedef Geo<WAVES> G;
   constexpr int NCG = G::NCG;
-#ifdef KPDI16_NO_LEX  // (developer build: round 5's order and tie handling in every instantiation)
-  constexpr bool LEX = false;
-#else
   constexpr bool LEX = !(KMAX == 32 && WAVES == 8);  // (scan16 above)
-#endif
   constexpr int BLOCK16 = G::DBLOCK, STAGE16 = G::STAGE, NSTAGE16 = G::NSTAGE, KSTEPS16 = G::KS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef KPDI16_TIME_PHASES  // developer build: cycles of a launch's phases (tools/probes/one_step.py; profiles/r06_launch_phases.txt)
-  const unsigned long long ph_t0 = __builtin_readcyclecounter();
-  unsigned long long ph_prologue = 0, ph_first_loop = 0, ph_first_epi = 0, ph_loop_end = 0, ph_epi_t0 = 0;
-  unsigned long long ph_fs_bound = 0, ph_fs_loop = 0;
-  int ph_fs_iters = 0, ph_fs_inserts = 0;
-#endif
+  Probe16 probe;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0 .. WAVES - 1
@@ -213,6 +409,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
 #define KPDI_FA(base, rt, ks) (*(const f32x4 *)((base) + fa_off + (rt) * 1024 + (ks) * (G::DT * 32)))
 #define KPDI_FB(base, cg, ks) (*(const f32x4 *)((base) + fb_off + (cg) * 1024 + (ks) * (F16_TILE * 32)))
 
+  // ==== STAGE: set-up - this lane's list and candidate-buffer homes, the bound line and slot.  (Inline: as a function
+  // returning a struct, <20, false, 8> gained an SGPR and an instruction in its MFMA loop.)
   // ---- this lane's NCG lists (column group cg: pattern m_lane + 32 cg; it sees the rows
   // 4 (lane >> 5) + {0..3} + 8 j of every 32-row group of its wave's 128 rows).  Their home is the
   // scratch: entry j of list (workgroup, wave, cg) at [((wg * WAVES + wave) * NCG + cg) * KMAX + j][lane].
@@ -229,18 +427,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
   // (the 32-entry lists of the 8-wave form - !LEX - keep the initialised homes: that instantiation has no register to
   // spare, tools/check_mfma_loops.py)
   unsigned built = LEX ? 0u : ~0u;
-  if (!LEX) {
-#pragma unroll
-    for (int c = 0; c < (NCG * KMAX + 15) / 16; ++c) {
-      float *ps = chunk_base(home_s, c);
-      int *pi = chunk_base(home_i, c);
-#pragma unroll
-      for (int j = 16 * c; j < NCG * KMAX && j < 16 * c + 16; ++j) {
-        ps[(j - 16 * c) * 64 + ulane] = -INFINITY;
-        pi[(j - 16 * c) * 64 + ulane] = INT_MAX;
-      }
-    }
-  }
+  if (!LEX) list_clear<NCG * KMAX>(home_s, home_i, ulane);
   // candidate buffers behind the lists: [((wg * WAVES + wave) * NCG + cg) * CAND_CAP + slot][lane]
   const size_t n_list_entries = (size_t)gridDim.x * WAVES * NCG * KMAX * 64;
   float *buf_s = ls_scores + n_list_entries + (((size_t)blockIdx.x * WAVES + wv) * NCG) * CAND_CAP * 64;
@@ -261,6 +448,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
   const bool bound_grouped = a.bound_grouped != 0;
   const int cap = bound_rank == 1 ? CAND_CAP : CAND_CAP_PLAIN;
 
+  // ==== STAGE: the unit and tile cursor.  (t0 / t1 / t2 must stay plain locals: as members of a struct selected by ld_pos
+  // they are addressed through scratch, inside the MFMA loop.)
   // ---- dictionary tiles: t0 = tile being computed, t1 / t2 the next two (loads run two steps ahead).
   // STATIC hand-out: split sp takes the tiles sp, sp + nsplit, sp + 2 nsplit ...  Block b runs on XCD
   // b % 8 and nsplit is a multiple of 8 whenever the chip is full, so the workgroups of ALL row blocks
@@ -268,16 +457,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
   // block crosses the fabric once and is served to the other row blocks by that XCD's L2 (with the
   // dynamic hand-out of match.hip every row block re-fetched it: 16 x the dictionary per launch, which
   // the f32 kernel's 1.2 TB/s tolerates and this kernel's 6+ TB/s did not).
-  // timing-only ablations: the same block every step (always an L2 hit)
-#if defined(KPDI16_E_FIXED) && defined(KPDI16_D_FIXED)
-#define KPDI16_ABLATE_ADDR ge = exp_base; gd = dict_base;
-#elif defined(KPDI16_E_FIXED)
-#define KPDI16_ABLATE_ADDR ge = exp_base;
-#elif defined(KPDI16_D_FIXED)
-#define KPDI16_ABLATE_ADDR gd = dict_base;
-#else
-#define KPDI16_ABLATE_ADDR
-#endif
   // Units of work.  Whole tiles everywhere except in the float32 form's tail: the tiles from a.tail_first on are cut
   // into units of 256 >> tail_shift dictionary rows (unit u >= tail_first: tile tail_first + ((u - tail_first) >>
   // tail_shift), rows from ((u - tail_first) & (2^tail_shift - 1)) * (256 >> tail_shift)), in which a wave runs
@@ -320,7 +499,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
     t_ = t_ < last_tile ? t_ : last_tile; /* past the end: harmless re-load */       \
     gd = dict_base + (size_t)t_ * tile_bytes + (size_t)ld_step * G::DBLOCK;          \
     ge = exp_base + (size_t)ld_step * G::EBLOCK;                                     \
-    KPDI16_ABLATE_ADDR                                                               \
   }
 #define KPDI16_CURSOR_ADVANCE()                                \
   {                                                            \
@@ -341,9 +519,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
     KPDI16_CURSOR_ADVANCE();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-#ifdef KPDI16_TIME_PHASES
-    ph_prologue = __builtin_readcyclecounter() - ph_t0;
-#endif
+    probe.mark_prologue();
 
     // rows of this wave in a unit: 32 * rt_n consecutive rows from unit row + wr * 32 * rt_n
     auto fa_base = [&](int u) { return (unsigned)((KPDI16_UNIT_ROW(u) + wr * 32 * KPDI16_UNIT_RT(u)) * 32) + fa_lane; };
@@ -357,18 +533,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
 
     int stage = 0;
     int tiles_done = 0, refresh_at = 0;
-#ifdef KPDI16_EPI_STATS  // developer build: per tile, what the epilogue of ONE wave did (tools/probes/one_step.py; profiles/r05_f32_tile_time.txt)
-    int st_hot = 0, st_iter = 0, st_cand = 0;
-    unsigned long long st_t0 = 0;
-#endif
-#ifdef KPDI16_EPI_FINE  // developer build: cycles of the three parts of a block's epilogue (same tools, same record)
-    unsigned long long fine_screen = 0, fine_pm = 0, fine_loop = 0;
-    int fine_blocks = 0;
-#endif
-#ifdef KPDI16_TIME_EPI  // developer build (tools/build_variant.sh + tools/probes/one_step.py): where the cycles between tiles go
-    unsigned long long epi_cycles = 0, epi_drain = 0;
-    const unsigned long long kern_t0 = __builtin_readcyclecounter();
-#endif
+    probe.loop_begin();
 #pragma clang loop unroll(disable)
     for (;;) {  // dictionary tiles (units)
       const int rt_n = F32 ? KPDI16_UNIT_RT(t0) : 4;                        // row groups of this wave in this unit
@@ -379,6 +544,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
         for (int rt = 0; rt < 4; ++rt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[cg][rt][r] = 0.f;
+      // ==== STAGE: the MFMA loop - per step: fragment reads, MFMAs, DMA issue, one barrier
 #pragma clang loop unroll(disable)
       for (int step = 0; step < nsteps; ++step) {
         const char *ls = smem + stage * STAGE16;
@@ -466,13 +632,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
         KPDI16_CURSOR_ADVANCE();
         stage = nstage;
       }  // steps
-#ifdef KPDI16_TIME_EPI
-      const unsigned long long epi_t0 = __builtin_readcyclecounter();
-#endif
-#ifdef KPDI16_TIME_PHASES
-      ph_epi_t0 = __builtin_readcyclecounter();
-      if (tiles_done == 0) ph_first_loop = ph_epi_t0 - ph_t0 - ph_prologue;
-#endif
+      probe.tile_begin(tiles_done);
+      // ==== STAGE: the accumulator drain.  (Inline: as a function, <8, false, 4> spills 8 and <8, false, 4, F32> 14 more VGPRs.)
       // the last MFMAs (8 passes) must have written the accumulators before they are read
       // (the pipe retires MFMAs in order: ONE wait covers all of them; the empty statements only tie every accumulator to
       // this point - 16 x 24 wait states per tile were spent here before)
@@ -492,13 +653,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
               asm volatile("" : "+v"(acc[cg][rt]));
           }
         }
-#ifdef KPDI16_TIME_EPI
-      epi_drain += __builtin_readcyclecounter() - epi_t0;
-#endif
-#ifdef KPDI16_EPI_STATS
-      st_hot = st_iter = st_cand = 0;
-      st_t0 = __builtin_readcyclecounter();
-#endif
+      probe.drain_done();
       {
         // ---- epilogue of the tile.  Steady state (per column group): the 64 accumulator registers are
         // compared with the pre-scaled threshold (a v_max3 tree per 16 registers first) and the few
@@ -508,6 +663,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
         // step), so every cycle spent here is lost on the matrix pipe: a list update per tile cost 23 %.
         const int row0 = F32 ? KPDI16_UNIT_TILE(t0) * G::DT + KPDI16_UNIT_ROW(t0) + wr * 32 * rt_n + 4 * (lane >> 5)
                              : t0 * G::DT + wr * 128 + 4 * (lane >> 5);
+        // ==== STAGE: first-tile fast path - publish the maxima, poll the bound -> first_fast.  (Inline: as a function, eight
+        // instantiations grew, e.g. <8, false, 4, F32>: 43 more spilled VGPRs.)
         // ---- the FIRST tile of a launch has no bound to screen with.  Building every lane's list from all 64 candidates
         // of each column group (scan16 below) is what a launch of this kernel costs beyond its tiles: ~360 000 cycles =
         // 0.15 ms (profiles/r04_epilogue_ab.txt).  A bound needs no list, though - only every list's BEST entry (grouped
@@ -516,7 +673,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
         // 3 % quantile: ~2 of the 64 candidates pass and take the steady-state append path.  If the bound is not
         // complete after the poll (a workgroup of the row block lags, or is not resident) the list is built directly, as before.
         bool first_fast = false;
-#ifndef KPDI16_FIRST_TILE_DIRECT  // (developer build: rounds 3's first tile)
         if (tiles_done == 0 && !BOUNDED && bound_rank == 1 && bound_grouped &&
             (F32 ? KPDI16_UNIT_TILE(t0) : t0) * G::DT + G::DT <= n_valid) {
 #pragma unroll
@@ -550,7 +706,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
             if (!first_fast) __builtin_amdgcn_s_sleep(24);
           }
         }
-#endif
+        // ==== STAGE: screen-and-append, per column group (the two append forms share append16)
         // index of a built list's last entry (a candidate that TIES with it passes only with a lower index: tiles
         // arrive in a permuted order); lists are rarely built before the end - then nothing is loaded
         int lidx[NCG];
@@ -562,10 +718,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
 #pragma unroll
         for (int cg = 0; cg < NCG; ++cg) {
 #ifdef KPDI16_NO_EPILOGUE  // (the MFMAs are asm volatile: they stay)
-          continue;
-#endif
-#ifdef KPDI16_SCREEN_NONE  // the bound is loaded and reduced, nothing is screened
-          if (g[cg] == 12345.f) cnt[cg] = 1;
           continue;
 #endif
           constexpr float unscale = F32 ? 1.f : 0x1p-24f;
@@ -588,35 +740,22 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
           // launch of the float32 form cost beyond its tiles (tools/tile_ramp_probe.py on the ablation builds).  It goes
           // the way of a full buffer instead: the list is built from the accumulators directly (scan16: 20 entries stay,
           // 40 stores), and its last entry screens the lane's next tiles beside the shared bound.
-#ifdef KPDI16_FIRST_TILE_APPENDS  // (developer build: round 2's behaviour)
-          const bool first_tile = false;
-#else
           const bool first_tile = tiles_done == 0 && !first_fast;
-#endif
           bool overflow = first_tile;
           float mx = -INFINITY;
 #pragma unroll
           for (int rt = 0; rt < 4; ++rt) {
             if (first_tile) continue;
             if (F32 && rt >= rt_n) continue;
-#ifdef KPDI16_EPI_FINE
-            const unsigned long long f0 = __builtin_readcyclecounter();
-#endif
+            probe.block_begin();
             float m = acc[cg][rt][0];
 #pragma unroll
             for (int r = 1; r < 16; ++r) m = fmaxf(m, acc[cg][rt][r]);
-#ifdef KPDI16_SCAN_NEVER  // timing-only ablation: the screen (maxima + ballot) runs, no candidate is ever taken
-            if (__builtin_amdgcn_ballot_w64(m >= thr_raw) != 0xdeadbeefull) continue;
-#endif
             if (__builtin_amdgcn_ballot_w64(m >= thr_raw) == 0) continue;  // wave-uniform
             // (the bounded 32-entry instantiation of the 8-wave form has no register to spare for the mask form below - it
             // would reload a fragment from scratch inside the MFMA loop, tools/check_mfma_loops.py - and keeps round 3's
-            // form: one exec-masked block per accumulator register; KPDI16_APPEND_PER_REGISTER forces it everywhere, A/B)
-#ifdef KPDI16_APPEND_PER_REGISTER
-            constexpr bool PER_REGISTER = true;
-#else
+            // form: one exec-masked block per accumulator register)
             constexpr bool PER_REGISTER = BOUNDED && KMAX == 32 && WAVES == 8;
-#endif
             if (PER_REGISTER) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -625,16 +764,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
               const int idx = idx_base + lrow;
               bool ok = acc[cg][rt][r] >= thr_raw && lrow < n_valid && (!LEX || v > last[cg] || idx < lidx[cg]);
               if (BOUNDED) ok = ok && (v < ub_cg || (v == ub_cg && idx > ubi_cg));
-              if (ok) {
-                if (c < cap) {
-                  bs[c * 64 + ulane] = v;
-                  bi[c * 64 + ulane] = idx;
-                  ++c;
-                  mx = fmaxf(mx, v);
-                } else {
-                  overflow = true;
-                }
-              }
+              if (ok) append16(bs, bi, ulane, cap, c, mx, overflow, v, idx);
             }
             } else {
             // ---- some lane of this block of 16 registers holds a candidate (typically ONE lane, one register).  Which of
@@ -643,25 +773,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
             // cycles of scalar dependency stalls each, 16 x 16 times per tile: 2 % of the kernel, profiles/r03_epilogue_cycles.txt);
             // then ONE loop, as long as any lane has a bit left: lowest bit -> register (a 16-way select) -> append.  Bits
             // are taken in ascending register order = ascending dictionary index, like the per-register form.
-#ifdef KPDI16_EPI_FINE
-            const unsigned long long f1 = __builtin_readcyclecounter();
-#endif
+            probe.hot_block();
             unsigned pm = 0;
 #pragma unroll
             for (int r = 0; r < 16; ++r) pm |= acc[cg][rt][r] >= thr_raw ? (1u << r) : 0u;
-#ifdef KPDI16_EPI_FINE
-            asm volatile("" : "+v"(pm));
-            const unsigned long long f2 = __builtin_readcyclecounter();
-#endif
-#ifdef KPDI16_EPI_STATS
-            ++st_hot;
-#endif
+            probe.mask_done(pm);
 #pragma unroll 1
             while (__builtin_amdgcn_ballot_w64(pm != 0) != 0) {
-#ifdef KPDI16_EPI_STATS
-              ++st_iter;
-              st_cand += __builtin_popcountll(__builtin_amdgcn_ballot_w64(pm != 0));
-#endif
+              probe.append_iteration(pm);
               if (pm != 0) {
                 const int r = __builtin_ctz(pm);
                 pm &= pm - 1;
@@ -673,29 +792,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
                 const int idx = idx_base + lrow;
                 bool ok = lrow < n_valid && (!LEX || v > last[cg] || idx < lidx[cg]);
                 if (BOUNDED) ok = ok && (v < ub_cg || (v == ub_cg && idx > ubi_cg));
-                if (ok) {
-                  if (c < cap) {
-#ifndef KPDI16_NO_APPEND_STORES
-                    bs[c * 64 + ulane] = v;
-                    bi[c * 64 + ulane] = idx;
-#endif
-                    ++c;
-                    mx = fmaxf(mx, v);
-                  } else {
-                    overflow = true;
-                  }
-                }
+                if (ok) append16(bs, bi, ulane, cap, c, mx, overflow, v, idx);
               }
             }
-#ifdef KPDI16_EPI_FINE
-            {
-              const unsigned long long f3 = __builtin_readcyclecounter();
-              fine_screen += f1 - f0;
-              fine_pm += f2 - f1;
-              fine_loop += f3 - f2;
-              ++fine_blocks;
-            }
-#endif
+            probe.hot_block_end();
             }
           }
           if (__builtin_amdgcn_ballot_w64(overflow) == 0) {
@@ -707,6 +807,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
               __hip_atomic_fetch_max(line + my_slot, score_key(mx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
           } else {
+            // ==== STAGE: the overflow rebuild - load or empty the list, replay the buffer, scan16, store, publish.  (Inline: as
+            // a function it spills far less but lengthens the MFMA loop of six instantiations, <32, true, 8>: 73 -> 90.)
             // ---- a buffer is full: list <- buffered candidates of the earlier tiles (in arrival order), then
             // this tile's accumulators the direct way (what was appended from this tile above is dropped)
             float best[KMAX];
@@ -714,16 +816,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
             float *hs = home_s + cg * KMAX * 64;
             int *hi = home_i + cg * KMAX * 64;
             if (!LEX || ((built >> cg) & 1)) {
-#pragma unroll
-              for (int q = 0; q < (KMAX + 15) / 16; ++q) {
-                const float *ps = chunk_base(hs, q);
-                const int *pi = chunk_base(hi, q);
-#pragma unroll
-                for (int j = 16 * q; j < KMAX && j < 16 * q + 16; ++j) {
-                  best[j] = ps[(j - 16 * q) * 64 + ulane];
-                  bidx[j] = pi[(j - 16 * q) * 64 + ulane];
-                }
-              }
+              list_load<KMAX>(hs, hi, ulane, best, bidx);
             } else {  // (never built: the empty list)
 #pragma unroll
               for (int j = 0; j < KMAX; ++j) {
@@ -753,16 +846,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
             }
             cnt[cg] = 0;
             scan16<KMAX, BOUNDED, F32, LEX>(acc[cg], best, bidx, g[cg], ub_cg, ubi_cg, row0, n_valid, idx_base, rt_n);
-#pragma unroll
-            for (int q = 0; q < (KMAX + 15) / 16; ++q) {
-              float *ps = chunk_base(hs, q);
-              int *pi = chunk_base(hi, q);
-#pragma unroll
-              for (int j = 16 * q; j < KMAX && j < 16 * q + 16; ++j) {
-                ps[(j - 16 * q) * 64 + ulane] = best[j];
-                pi[(j - 16 * q) * 64 + ulane] = bidx[j];
-              }
-            }
+            list_store<KMAX>(hs, hi, ulane, best, bidx);
             last[cg] = best[KMAX - 1];
             float now = best[0];  // the entry the shared bound is built from
 #pragma unroll
@@ -773,21 +857,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
             }
           }
         }
-#ifdef KPDI16_TIME_EPI
-        epi_cycles += __builtin_readcyclecounter() - epi_t0;
-#endif
-#ifdef KPDI16_EPI_STATS
-        {
-          const unsigned long long dt = __builtin_readcyclecounter() - st_t0;
-          if (blockIdx.x == 100 && lane == 0 && wv == 0)
-            printf("tile %d: %llu cycles, %d hot blocks of 16, %d loop iterations, %d candidates of the wave, first_fast %d\n", tiles_done, dt,
-                   st_hot, st_iter, st_cand, (int)first_fast);
-        }
-#endif
-#ifdef KPDI16_TIME_PHASES
-        if (tiles_done == 0) ph_first_epi = __builtin_readcyclecounter() - ph_epi_t0;
-        ph_loop_end = __builtin_readcyclecounter() - ph_t0;
-#endif
+        probe.tile_end(tiles_done, first_fast, wv, lane);
         ++tiles_done;
         t0 = t1;
         t1 = t2;
@@ -796,19 +866,11 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
         if (t0 >= n_units) break;
       }
     }
-#ifdef KPDI16_EPI_FINE
-    if (blockIdx.x == 100 && lane == 0)
-      printf("wave %d: %d hot blocks: screen %llu, mask %llu, loop %llu cycles per hot block\n", wv, fine_blocks, fine_screen / fine_blocks,
-             fine_pm / fine_blocks, fine_loop / fine_blocks);
-#endif
-#ifdef KPDI16_TIME_EPI
-    if ((blockIdx.x == 0 || blockIdx.x == 100) && lane == 0)
-      printf("block %d wave %d: %d tiles, %llu cycles between tiles (%llu of them waiting for the last MFMAs) of %llu in the tile loop "
-             "(%.2f %%)\n", (int)blockIdx.x, wv, tiles_done, epi_cycles, epi_drain, __builtin_readcyclecounter() - kern_t0,
-             100.0 * epi_cycles / (double)(__builtin_readcyclecounter() - kern_t0));
-#endif
+    probe.loop_report(tiles_done, wv, lane);
   }
 
+  // ==== STAGE: the final stage.  (Inline, its list load written out: as a function, <32, false, 8>'s MFMA loop grew 73 -> 83;
+  // with list_load here, 14 instantiations grew.)
   // ---- the buffered candidates that pass the FINAL shared bound join their lists (in arrival order = by
   // increasing dictionary index), then lists -> [m_pad][lists][KMAX] for the merge kernel
   {
@@ -816,16 +878,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
 #pragma unroll
     for (int cg = 0; cg < NCG; ++cg) {
       const size_t ol = (size_t)(m_lane + 32 * cg) * lists + (size_t)list_id, o = ol * KMAX;
-#ifdef KPDI16_SKIP_FINAL  // (developer build, TIMING ONLY - results are wrong: what a launch costs without its final stage)
-      if (LEX) {
-        a.part_cnt[ol] = 0;
-        continue;
-      }
-#endif
       // a candidate below the bound has KMAX better ones somewhere among the pattern's lists
-#ifdef KPDI16_TIME_PHASES
-      const unsigned long long fs0 = __builtin_readcyclecounter();
-#endif
+      probe.final_begin();
       // (any bound that ever stood is valid; the one this wave refreshed last - during its last tiles - is nearly the
       // final one and costs nothing: four dependent loads from memory here were 10 us of every launch)
       float tf = g[cg];
@@ -833,11 +887,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
       tf = -INFINITY;
 #endif
       if (__builtin_amdgcn_ballot_w64(!(tf > -INFINITY)) != 0) tf = shared_bound<KMAX>(line0 + 32 * cg * BOUND_SLOTS, bound_grouped);
-#ifdef KPDI16_TIME_PHASES
-      asm volatile("" : "+v"(tf));
-      const unsigned long long fs1 = __builtin_readcyclecounter();
-      ph_fs_bound += fs1 - fs0;
-#endif
+      probe.final_bound(tf);
 #ifdef KPDI16_NO_DIRECT  // (developer build: every list through the sorted path)
       constexpr bool DIRECT = false;
 #else
@@ -846,11 +896,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
       // cycles and its hot loop is instruction for instruction the same (A/B of developer builds on one box, alternating:
       // profiles/r06_f16_ab.txt; why is not established - not the scratch size, which is the same either way).  Its final
       // stage is 20 k cycles of 5 M: there is nothing to gain there for it anyway.)
-#ifdef KPDI16_DIRECT_ALL  // (developer build: the A/B of profiles/r06_f16_ab.txt)
-      constexpr bool DIRECT = LEX;
-#else
       constexpr bool DIRECT = LEX && WAVES == 4;
-#endif
 #endif
       if (DIRECT && !((built >> cg) & 1)) {
         // ---- the usual case: this list was never built.  The merge kernel takes a partial list as a SET of candidates
@@ -859,9 +905,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
         // them: 16 predicated stores per batch instead of one 20-entry sorted insertion per survivor (those insertions, 6
         // per column group at ~2500 cycles each, were most of what a launch spent behind its last tile:
         // profiles/r06_launch_phases.txt).  A lane with more than KMAX survivors (adversarial data): the sorted path below.
-#ifdef KPDI16_TIME_PHASES
-        const unsigned long long fs2 = __builtin_readcyclecounter();
-#endif
+        probe.final_direct_begin();
         int n = 0;
 #pragma unroll 1
         for (int base = 0; __builtin_amdgcn_ballot_w64(base < cnt[cg]) != 0; base += 16) {
@@ -886,10 +930,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
             }
           }
         }
-#ifdef KPDI16_TIME_PHASES
-        ph_fs_loop += __builtin_readcyclecounter() - fs2;
-        ++ph_fs_iters;
-#endif
+        probe.final_batch_end();
         if (__builtin_amdgcn_ballot_w64(n > KMAX) == 0) {
           a.part_cnt[ol] = n;  // (the merge takes the first n entries of this list: nothing is stored behind them)
           if (a.epi_stats) {
@@ -944,16 +985,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
 #pragma unroll
         for (int e = 0; e < 16; ++e)
           pm |= (vs[e] >= tf && (LEX ? ranks_before(vs[e], ids[e], best[KMAX - 1], bidx[KMAX - 1]) : vs[e] > best[KMAX - 1])) ? (1u << e) : 0u;
-#ifdef KPDI16_TIME_PHASES
-        asm volatile("" : "+v"(pm));
-        const unsigned long long fs2 = __builtin_readcyclecounter();
-        ++ph_fs_iters;
-#endif
+        probe.final_batch_begin(pm);
 #pragma unroll 1
         while (__builtin_amdgcn_ballot_w64(pm != 0) != 0) {
-#ifdef KPDI16_TIME_PHASES
-          ++ph_fs_inserts;
-#endif
+          probe.final_insert();
           if (pm != 0) {
             const int e = __builtin_ctz(pm);
             pm &= pm - 1;
@@ -971,9 +1006,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
             }
           }
         }
-#ifdef KPDI16_TIME_PHASES
-        ph_fs_loop += __builtin_readcyclecounter() - fs2;
-#endif
+        probe.final_batch_end();
       }
       if (LEX && a.epi_stats) {
         const unsigned app = wave_sum_u32((unsigned)cnt[cg]);
@@ -990,15 +1023,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void match16_kernel(MatchArg
       }
     }
   }
-#ifdef KPDI16_TIME_PHASES
-  {
-    const unsigned long long end = __builtin_readcyclecounter() - ph_t0;
-    if ((blockIdx.x == 0 || blockIdx.x == 100 || blockIdx.x == 255) && lane == 0 && wv == 0)
-      printf("block %d: prologue %llu, first tile's steps %llu, first epilogue %llu, tile loop ends at %llu, final stage %llu, kernel %llu cycles "
-             "(shader cycles); final stage: bound loads %llu, insert loops %llu (%d batches, %d insertions)\n", (int)blockIdx.x, ph_prologue,
-             ph_first_loop, ph_first_epi, ph_loop_end, end - ph_loop_end, end, ph_fs_bound, ph_fs_loop, ph_fs_iters, ph_fs_inserts);
-  }
-#endif
+  probe.report(wv, lane);
 }
 
 // floats (and as many ints) the kernel keeps per launch: the lists and the candidate buffers behind them
@@ -1025,9 +1050,6 @@ static hipError_t launch16_t(const MatchArgs &args_in, int grid, void *scratch, 
   }
   MatchArgs args = args_in;
   if (KMAX == 32 && WAVES == 8) args.perm_rounds = 0;  // (!LEX instantiations: natural order, match16_kernel)
-#ifdef KPDI16_NO_LEX
-  args.perm_rounds = 0;
-#endif
   // scratch: scores of all lists, then their indices
   float *ls = (float *)scratch;
   int *li = (int *)(ls + scratch16_entries(grid, WAVES, KMAX));
