@@ -8,6 +8,7 @@
 #include "clahe_plan.h"
 #include "neighbours_plan.h"
 #include "downsample_plan.h"
+#include "prep_plan.h"
 
 namespace kpdi {
 
@@ -153,11 +154,7 @@ struct PrepLaunch {
   int f16_rows = F16_TILE, f16_step = F16_STEP;  // float16 form: patterns per tile / pixels per step of the layout
 };
 hipError_t launch_prep(const PrepLaunch &a, hipStream_t s);
-// host: the signal mask's pixel map as one descriptor per 4 kept pixels for the gather kernels of prep.hip - the quad's
-// pixels as (up to) two runs of consecutive detector pixels: bits 0-11 = detector pixel of element 0, bits 12-23 =
-// detector pixel of element j MINUS j (so that element e >= j is the e-th float behind it), bits 24-26 = j (4: one run).
-// Returns false when some quad needs more than two runs or npix > 4096 (descriptors unusable).
-bool gather_descriptors(const int *pix_map, int k, int npix, std::vector<unsigned> *out);
+// (gather_descriptors(), the host side of quad_desc, and the kernel choice: prep_plan.h)
 // in place: prepared f32 rows [0, n_rows_pad) x kpad -> split-f16 form (KPDI_COMPUTE_F16X2): every
 // 128-byte row-slab (32 pixels) becomes 4 slots of high halves + 4 slots of low halves of
 // 2^12 * value, eight f16 pixels per 16-byte slot; n_rows_pad multiple of 128
@@ -282,7 +279,7 @@ struct PreLaunch {
 hipError_t launch_preprocess(const PreLaunch &a, bool *prep_done, hipStream_t s);
 bool preprocess_fits_fused(int sy, int sx, int prepared_cols);
 size_t preprocess_scratch_floats(int sy, int sx, int64_t n, int *grid_out);
-size_t dtype_size(int dtype);
+// (dtype_size: prep_plan.h)
 
 // ---- master-pattern projection (project.hip) --------------------------------
 struct ProjectLaunch {

@@ -41,16 +41,6 @@
 
 namespace kpdi {
 
-size_t dtype_size(int dtype) {
-  switch (dtype) {
-    case KPDI_U8: case KPDI_I8: return 1;
-    case KPDI_U16: case KPDI_I16: case KPDI_F16: return 2;
-    case KPDI_F32: case KPDI_I32: case KPDI_U32: return 4;
-    case KPDI_F64: return 8;
-  }
-  return 0;
-}
-
 // ---- large detectors: one workgroup per pattern ----------------------------------------
 template <typename T>
 __global__ __launch_bounds__(PREP_THREADS) void prep_kernel(const T *raw, int npix, const int *row_map,
@@ -236,7 +226,6 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_block_kernel(const T *raw, 
 // 28.8 GB dictionary of configs[4].  Here every 256-thread group normalises one of four consecutive patterns
 // in registers (as prep_block_kernel), the float16 rows are staged in LDS, and the workgroup writes them out
 // as whole lines.  LDS: 4 x (2 * kpad + 8) float16.
-constexpr int PREP16_THREADS = 1024;
 // NP = patterns per workgroup.  4 (1024 threads): whole 128-byte lines, but 64 values per thread x 1024 threads is all of
 // a CU's registers - ONE workgroup per CU, whose load, reduce and store phases nothing overlaps (3.7 TB/s on configs[4]).
 // 2 (512 threads): two workgroups per CU in different phases; a plane's 64 bytes of the two rows are one aligned half
@@ -661,26 +650,7 @@ __global__ __launch_bounds__(PREP_THREADS) void prep_wave_masked_dma_kernel(cons
 // of a staged copy of the whole row in LDS: no LDS for the input, no barrier, no wait for the acknowledgement of the
 // previous row's stores, and the workgroup's LDS budget goes to writing whole 128-byte lines (write_lines4).
 // Reads past the row's end return zero (the buffer descriptor is sized to the row); they are never selected.
-bool gather_descriptors(const int *pix_map, int k, int npix, std::vector<unsigned> *out) {
-  out->clear();
-  if (npix > 4096 || k <= 0) return false;
-  for (int q = 0; 4 * q < k; ++q) {
-    const int n = std::min(4, k - 4 * q);
-    const int *p = pix_map + 4 * q;
-    int j = n;  // first element that does not continue the run of element 0
-    for (int e = 1; e < n; ++e)
-      if (p[e] != p[0] + e) {
-        j = e;
-        break;
-      }
-    for (int e = j + 1; e < n; ++e)
-      if (p[e] != p[j] + (e - j)) return false;  // a third run
-    const int off2 = j < n ? p[j] - j : p[0];      // >= 0: pix_map ascends, so p[j] > p[j - 1] >= j - 1
-    if (off2 < 0) return false;
-    out->push_back((unsigned)p[0] | ((unsigned)off2 << 12) | ((unsigned)(j < n ? j : 4) << 24));
-  }
-  return true;
-}
+// (gather_descriptors: prep_plan.h)
 
 template <bool LINES>
 __global__ __launch_bounds__(PREP_THREADS) void prep_wave_gather_kernel(const float *raw, int npix, const int *row_map,
@@ -778,127 +748,107 @@ hipError_t launch_split_f16(float *prepared, int n_rows_pad, int kpad, hipStream
   return hipGetLastError();
 }
 
-hipError_t launch_prep(const PrepLaunch &a, hipStream_t s) {
-  if (a.n_out <= 0) return hipSuccess;
-  const int cols = a.k + (a.metric == NORM_NDP_CENTRED ? 1 : 0);  // columns of a row that are not padding
-  // columns a row-owning wave / workgroup has to write: everything up to the padded row length
-  const int span = std::max(cols, a.operand_form == 2 ? 2 * a.kpad : a.kpad);
-  const bool wave_path = span <= 64 * WAVE_VALUES;
-  // what the kernels are told: the float16 form carries its block geometry
-  const int form = a.operand_form == 2 ? f16_form(a.f16_rows, a.f16_step) : (a.operand_form == 3 ? wide32_form() : a.operand_form);
-  const bool vec_ok = (a.npix % 4) == 0 && ((uintptr_t)a.raw % (4 * dtype_size(a.dtype))) == 0;
-  const bool vec4 = wave_path && a.pix_map == nullptr && (a.k % 4) == 0 && vec_ok;
-  const bool staged = wave_path && a.pix_map != nullptr && vec_ok && a.npix <= 64 * WAVE_VALUES && !getenv("KPDI_PREP_NO_STAGED");
-  // larger detectors, still register-resident: one workgroup per pattern
-  const bool block_path = !wave_path && span <= PREP_THREADS * WAVE_VALUES;
-  const bool block_vec = block_path && a.pix_map == nullptr && (a.k % 4) == 0 && vec_ok;
-  const bool block_masked = block_path && a.pix_map != nullptr;
-  const size_t staged_lds = (size_t)(((a.k + 3) & ~3) + 4 * a.npix) * 4;
-  const size_t lines_lds = (size_t)4 * a.kpad * 4 * (getenv("KPDI_PREP_NO_LINES") ? 1000 : 1);  // prep_wave_lines_kernel
-  // float32 rows (dictionaries): LDS-DMA, double-buffered (prep_wave_masked_dma_kernel)
-  const size_t dma_lds = (size_t)(((a.k + 3) & ~3) + 8 * ((a.npix + 255) & ~255)) * 4;
-  const bool staged_dma = staged && a.dtype == KPDI_F32 && dma_lds <= 160 * 1024 && !getenv("KPDI_PREP_NO_DMA");
-  // float32 rows whose mask is a set of runs: gathered straight from global memory (prep_wave_gather_kernel); the
-  // plane-major forms (2: float16, 3: wide float32) are written as whole lines through LDS, forms 0 / 1 as 16-byte slots
-  const bool gather = wave_path && a.pix_map != nullptr && a.quad_desc != nullptr && a.dtype == KPDI_F32 &&
-                      ((uintptr_t)a.raw % 4) == 0 && (a.operand_form < 2 || lines_lds <= 64 * 1024) &&
-                      !getenv("KPDI_PREP_NO_GATHER");
-  static const bool prep16_affine = getenv("KPDI_PREP16") && !strcmp(getenv("KPDI_PREP16"), "block");
-  static const int prep16_np = getenv("KPDI_PREP16") && !strcmp(getenv("KPDI_PREP16"), "block4") ? 4 : 2;
-  dim3 block(PREP_THREADS);
-  dim3 grid(wave_path ? (a.n_out + 3) / 4 : a.n_out);
-  if (staged && !gather) grid = dim3(std::min((a.n_out + 3) / 4, 2048));
-#define KPDI_PREP_H(T, H)                                                                                \
-  if (H && vec4 && lines_lds <= 64 * 1024)                                                               \
-    hipLaunchKernelGGL((prep_wave_lines_kernel<T>), grid, block, lines_lds, s, (const T *)a.raw, a.npix, a.row_map, a.k, \
-                       a.kpad, a.metric, a.n_out, a.out, form);                                          \
-  else if (vec4)                                                                                       \
-    hipLaunchKernelGGL((prep_wave_kernel<T, 4, H>), grid, block, 0, s, (const T *)a.raw, a.npix,        \
-                       a.row_map, a.pix_map, a.k, a.kpad, a.metric, a.n_out, a.out, form);               \
-  else if (staged_dma) {                                                                                 \
-    auto kd = prep_wave_masked_dma_kernel<H>;                                                            \
-    if (dma_lds > 64 * 1024) {                                                                           \
-      hipError_t e = hipFuncSetAttribute((const void *)kd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dma_lds); \
-      if (e != hipSuccess) return e;                                                                     \
-    }                                                                                                    \
-    hipLaunchKernelGGL(kd, dim3(std::min((a.n_out + 3) / 4, 1024)), block, dma_lds, s, (const float *)a.raw, a.npix, \
-                       a.row_map, a.pix_map, a.k, a.kpad, a.metric, a.n_out, a.out, form);               \
-  } else if (staged) {                                                                                   \
-    if (staged_lds > 64 * 1024) {                                                                        \
-      hipError_t e = hipFuncSetAttribute((const void *)prep_wave_masked_kernel<T, H>,                    \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)staged_lds);   \
-      if (e != hipSuccess) return e;                                                                     \
-    }                                                                                                    \
-    hipLaunchKernelGGL((prep_wave_masked_kernel<T, H>), grid, block, staged_lds, s, (const T *)a.raw,   \
-                       a.npix, a.row_map, a.pix_map, a.k, a.kpad, a.metric, a.n_out, a.out, form);       \
-  } else if (wave_path)                                                                                  \
-    hipLaunchKernelGGL((prep_wave_kernel<T, 1, H>), grid, block, 0, s, (const T *)a.raw, a.npix,        \
-                       a.row_map, a.pix_map, a.k, a.kpad, a.metric, a.n_out, a.out, H ? form : 0);       \
-  else if (block_vec)                                                                                    \
-    hipLaunchKernelGGL((prep_block_kernel<T, false, H>), H ? dim3(round_up(a.n_out, 32)) : grid, block, 0, s,            \
-                       (const T *)a.raw, a.npix, a.row_map, a.pix_map, a.k, a.kpad, a.metric, a.out, form, H ? a.n_out : 0); \
-  else if (block_masked)                                                                                 \
-    hipLaunchKernelGGL((prep_block_kernel<T, true, H>), H ? dim3(round_up(a.n_out, 32)) : grid, block, 0, s,             \
-                       (const T *)a.raw, a.npix, a.row_map, a.pix_map, a.k, a.kpad, a.metric, a.out, form, H ? a.n_out : 0); \
-  else                                                                                                   \
-    hipLaunchKernelGGL((prep_kernel<T>), grid, block, 0, s, (const T *)a.raw, a.npix, a.row_map,        \
-                       a.pix_map, a.k, a.kpad, a.metric, a.out, H ? form : 0);
-#define KPDI_PREP(T)                  \
-  if (gather) {                                                                                           \
-    if (a.operand_form >= 2)                                                                              \
-      hipLaunchKernelGGL((prep_wave_gather_kernel<true>), grid, block, lines_lds, s, (const float *)a.raw, a.npix,       \
-                         a.row_map, a.quad_desc, a.k, a.kpad, a.metric, a.n_out, a.out, form);            \
-    else                                                                                                  \
-      hipLaunchKernelGGL((prep_wave_gather_kernel<false>), grid, block, 0, s, (const float *)a.raw, a.npix,              \
-                         a.row_map, a.quad_desc, a.k, a.kpad, a.metric, a.n_out, a.out, form);            \
-  } else if (a.operand_form == 3 && (block_vec || block_masked)) {                                              \
-    const size_t lds32 = (size_t)4 * (8 * ((a.kpad / 8 + 1) / 2) + 4) * 4;                               \
-    auto k32 = block_masked ? prep32_block4_kernel<T, true> : prep32_block4_kernel<T, false>;            \
-    if (lds32 > 64 * 1024) {                                                                             \
-      hipError_t e = hipFuncSetAttribute((const void *)k32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32); \
-      if (e != hipSuccess) return e;                                                                     \
-    }                                                                                                    \
-    hipLaunchKernelGGL(k32, dim3((a.n_out + 3) / 4), dim3(PREP16_THREADS), lds32, s, (const T *)a.raw, a.npix, \
-                       a.row_map, a.pix_map, a.k, a.kpad, a.metric, a.n_out, a.out, form);               \
-  } else if (a.operand_form == 2 && (block_vec || block_masked) && !prep16_affine) {                     \
-    const int np = prep16_np;                                                                            \
-    const size_t lds16 = (size_t)np * (2 * a.kpad + 8) * 2;                                              \
-    auto k16 = np == 2 ? (block_masked ? prep16_block4_kernel<T, true, 2> : prep16_block4_kernel<T, false, 2>)           \
-                       : (block_masked ? prep16_block4_kernel<T, true, 4> : prep16_block4_kernel<T, false, 4>);          \
-    if (lds16 > 64 * 1024) {                                                                             \
-      hipError_t e = hipFuncSetAttribute((const void *)k16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16); \
-      if (e != hipSuccess) return e;                                                                     \
-    }                                                                                                    \
-    /* NP = 2: the affine mapping walks row groups of 4 in blocks of 16 units */                         \
-    hipLaunchKernelGGL(k16, dim3(np == 2 ? round_up((a.n_out + 1) / 2, 16) : (a.n_out + 3) / 4), dim3(256 * np), lds16, s, \
-                       (const T *)a.raw, a.npix, a.row_map, a.pix_map, a.k, a.kpad, a.metric, a.n_out, a.out, form);     \
-  } else if (a.operand_form >= 2) {   \
-    KPDI_PREP_H(T, true)              \
-  } else {                            \
-    KPDI_PREP_H(T, false)             \
-  }                                   \
-  break;
-  switch (a.dtype) {
-    case KPDI_U8: KPDI_PREP(uint8_t)
-    case KPDI_I8: KPDI_PREP(int8_t)
-    case KPDI_U16: KPDI_PREP(uint16_t)
-    case KPDI_I16: KPDI_PREP(int16_t)
-    case KPDI_I32: KPDI_PREP(int32_t)
-    case KPDI_U32: KPDI_PREP(uint32_t)
-    case KPDI_F32: KPDI_PREP(float)
-    case KPDI_F64: KPDI_PREP(double)
-    case KPDI_F16: KPDI_PREP(_Float16)
+// one launch with the plan's geometry
+template <typename K, typename... A>
+static hipError_t launch_planned(K kernel, const PrepPlan &p, hipStream_t s, A... args) {
+  if (p.lds_bytes > PREP_LDS_DEFAULT) {
+    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.threads), p.lds_bytes, s, args...);
+  return hipSuccess;
+}
+
+// the families that carry the plane-major flag H as a template argument
+template <typename T, bool H>
+static hipError_t launch_family(const PrepLaunch &a, const PrepPlan &p, int form, hipStream_t s) {
+  const T *raw = (const T *)a.raw;
+  switch (p.kernel) {
+    case PREP_WAVE_LINES:
+      return launch_planned(prep_wave_lines_kernel<T>, p, s, raw, a.npix, a.row_map, a.k, a.kpad, a.metric, a.n_out, a.out,
+                            form);
+    case PREP_WAVE4:
+      return launch_planned(prep_wave_kernel<T, 4, H>, p, s, raw, a.npix, a.row_map, a.pix_map, a.k, a.kpad, a.metric,
+                            a.n_out, a.out, form);
+    case PREP_WAVE_MASKED_DMA:
+      return launch_planned(prep_wave_masked_dma_kernel<H>, p, s, (const float *)a.raw, a.npix, a.row_map, a.pix_map, a.k,
+                            a.kpad, a.metric, a.n_out, a.out, form);
+    case PREP_WAVE_MASKED:
+      return launch_planned(prep_wave_masked_kernel<T, H>, p, s, raw, a.npix, a.row_map, a.pix_map, a.k, a.kpad, a.metric,
+                            a.n_out, a.out, form);
+    case PREP_WAVE1:
+      return launch_planned(prep_wave_kernel<T, 1, H>, p, s, raw, a.npix, a.row_map, a.pix_map, a.k, a.kpad, a.metric,
+                            a.n_out, a.out, form);
+    case PREP_BLOCK:
+      return launch_planned(prep_block_kernel<T, false, H>, p, s, raw, a.npix, a.row_map, a.pix_map, a.k, a.kpad, a.metric,
+                            a.out, form, H ? a.n_out : 0);
+    case PREP_BLOCK_MASKED:
+      return launch_planned(prep_block_kernel<T, true, H>, p, s, raw, a.npix, a.row_map, a.pix_map, a.k, a.kpad, a.metric,
+                            a.out, form, H ? a.n_out : 0);
+    case PREP_GENERIC:
+      return launch_planned(prep_kernel<T>, p, s, raw, a.npix, a.row_map, a.pix_map, a.k, a.kpad, a.metric, a.out, form);
     default: return hipErrorInvalidValue;
   }
-#undef KPDI_PREP
-#undef KPDI_PREP_H
-  hipError_t e = hipGetLastError();
+}
+
+template <typename T>
+static hipError_t launch_typed(const PrepLaunch &a, const PrepPlan &p, int form, hipStream_t s) {
+  const T *raw = (const T *)a.raw;
+  switch (p.kernel) {
+    case PREP_WAVE_GATHER:
+      if (p.lines)
+        return launch_planned(prep_wave_gather_kernel<true>, p, s, (const float *)a.raw, a.npix, a.row_map, a.quad_desc, a.k,
+                              a.kpad, a.metric, a.n_out, a.out, form);
+      return launch_planned(prep_wave_gather_kernel<false>, p, s, (const float *)a.raw, a.npix, a.row_map, a.quad_desc, a.k,
+                            a.kpad, a.metric, a.n_out, a.out, form);
+    case PREP32_BLOCK4:
+      return launch_planned(p.masked ? prep32_block4_kernel<T, true> : prep32_block4_kernel<T, false>, p, s, raw, a.npix,
+                            a.row_map, a.pix_map, a.k, a.kpad, a.metric, a.n_out, a.out, form);
+    case PREP16_BLOCK4:
+      return launch_planned(p.np == 2 ? (p.masked ? prep16_block4_kernel<T, true, 2> : prep16_block4_kernel<T, false, 2>)
+                                      : (p.masked ? prep16_block4_kernel<T, true, 4> : prep16_block4_kernel<T, false, 4>),
+                            p, s, raw, a.npix, a.row_map, a.pix_map, a.k, a.kpad, a.metric, a.n_out, a.out, form);
+    default:
+      return p.h16 ? launch_family<T, true>(a, p, form, s) : launch_family<T, false>(a, p, form, s);
+  }
+}
+
+// the KPDI_PREP_* switches, read at every launch
+static PrepSwitches prep_switches() {
+  PrepSwitches sw;
+  sw.no_staged = getenv("KPDI_PREP_NO_STAGED") != nullptr;
+  sw.no_lines = getenv("KPDI_PREP_NO_LINES") != nullptr;
+  sw.no_dma = getenv("KPDI_PREP_NO_DMA") != nullptr;
+  sw.no_gather = getenv("KPDI_PREP_NO_GATHER") != nullptr;
+  if (const char *e = getenv("KPDI_PREP16")) sw.prep16 = !strcmp(e, "block") ? 1 : (!strcmp(e, "block4") ? 2 : 0);
+  return sw;
+}
+
+// which kernel and geometry: prep_plan.h
+hipError_t launch_prep(const PrepLaunch &a, hipStream_t s) {
+  if (a.n_out <= 0) return hipSuccess;
+  const PrepPlan p = prep_plan(a.dtype, a.npix, a.k, a.kpad, a.metric, a.operand_form, a.pix_map != nullptr,
+                               a.quad_desc != nullptr, (uint64_t)(uintptr_t)a.raw, a.n_out, prep_switches());
+  // what the kernels are told: the float16 form carries its block geometry
+  const int full = a.operand_form == 2 ? f16_form(a.f16_rows, a.f16_step) : (a.operand_form == 3 ? wide32_form() : a.operand_form);
+  const int form = p.pass_form ? full : 0;
+  hipError_t e;
+  switch (a.dtype) {
+    case KPDI_U8: e = launch_typed<uint8_t>(a, p, form, s); break;
+    case KPDI_I8: e = launch_typed<int8_t>(a, p, form, s); break;
+    case KPDI_U16: e = launch_typed<uint16_t>(a, p, form, s); break;
+    case KPDI_I16: e = launch_typed<int16_t>(a, p, form, s); break;
+    case KPDI_I32: e = launch_typed<int32_t>(a, p, form, s); break;
+    case KPDI_U32: e = launch_typed<uint32_t>(a, p, form, s); break;
+    case KPDI_F32: e = launch_typed<float>(a, p, form, s); break;
+    case KPDI_F64: e = launch_typed<double>(a, p, form, s); break;
+    case KPDI_F16: e = launch_typed<_Float16>(a, p, form, s); break;
+    default: return hipErrorInvalidValue;
+  }
   if (e != hipSuccess) return e;
-  // paths that store whole float4 slots write the split-f16 form themselves; the others are
-  // converted in place afterwards (rows beyond n_out are zero in either form).  The float16
-  // form is written directly by every path.
-  if (a.operand_form == 1 && !(vec4 || staged || gather || block_vec || block_masked))
-    return launch_split_f16(a.out, round_up(a.n_out, TILE_DICT), a.kpad, s);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (p.split_after) return launch_split_f16(a.out, round_up(a.n_out, TILE_DICT), a.kpad, s);
   return hipSuccess;
 }
 

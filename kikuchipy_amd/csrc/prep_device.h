@@ -10,8 +10,6 @@
 
 namespace kpdi {
 
-constexpr int NORM_NDP_CENTRED = 2;  // internal value of the `metric` argument: `ndp` in its centred form (prep.hip)
-
 // ---- degenerate patterns (include/kpdi.h, "Degenerate patterns") ---------------------------------------------------
 // A pattern whose normalisation is undefined is DEGENERATE: `ncc` - a CONSTANT pattern (dead or saturated detector
 // frame): all kept pixels equal, tested EXACTLY (minimum == maximum of the pixels as read - no tolerance: one pixel
@@ -27,8 +25,7 @@ template <typename F>
 __host__ __device__ inline bool degenerate_pattern(F norm2, F lo, F hi, bool ncc) {
   return !(norm2 > (F)0 && norm2 < (F)__builtin_inff()) || (ncc && lo == hi);  // (NaN fails both comparisons)
 }
-constexpr int PREP_THREADS = 256;
-constexpr int WAVE_VALUES = 64;  // values per lane of the wave-per-pattern kernels (K <= 4096)
+// (PREP_THREADS, WAVE_VALUES, NORM_NDP_CENTRED: prep_plan.h)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

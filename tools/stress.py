@@ -33,10 +33,15 @@ for case in range(n_cases):
     k = int(min(n, rng.choice([1, 2, 8, 20, 21, 33, 64])))
     metric = str(rng.choice(["ncc", "ndp"]))
     mode = int(rng.choice([_lib.COMPUTE_F32, _lib.COMPUTE_F16X2, _lib.COMPUTE_F16, _lib.COMPUTE_F64]))
-    dt_e = rng.choice([np.uint8, np.uint16, np.float32, np.float64])
-    dt_d = rng.choice([np.float32, np.uint8, np.float64])
-    exp = (rng.random((m, sy, sx)) * 250 + 1).astype(dt_e)
-    dic = (rng.random((n, sy, sx)) * 250 + 1).astype(dt_d)
+    all_dtypes = [np.uint8, np.int8, np.uint16, np.int16, np.int32, np.uint32, np.float16, np.float32, np.float64]
+    dt_e, dt_d = rng.choice(all_dtypes), rng.choice(all_dtypes)
+    exp = (rng.random((m, sy, sx)) * 120 + 1).astype(dt_e)  # (int8 holds up to 127)
+    dic = (rng.random((n, sy, sx)) * 120 + 1).astype(dt_d)
+    # the f32 kernel form: mostly the planner's choice, sometimes forced either way (read by set_problem)
+    wide = str(rng.choice(["", "", "0", "1"]))
+    os.environ.pop("KPDI_F32_WIDE", None)
+    if wide:
+        os.environ["KPDI_F32_WIDE"] = wide
     degenerate = ""
     if rng.random() < 0.3 and sy * sx >= 4:
         # patterns whose normalisation is undefined (include/kpdi.h "Degenerate patterns"): all-zero rows, score 0
@@ -65,7 +70,7 @@ for case in range(n_cases):
     ctx.set_experimental(exp, nav)
     ctx.set_dictionary_size(n if rng.random() < 0.6 else 0)  # (a group plans its chunk assignment with it; 0 = unknown)
     pre = ""
-    if rng.random() < 0.25 and dt_e in (np.uint8, np.uint16) and sy >= 4 and sx >= 4:
+    if rng.random() < 0.25 and dt_e in (np.uint8, np.uint16) and sy >= 4 and sx >= 4:  # (dt_e: a numpy scalar type)
         # recorded background removal, fused with the preparation at the first chunk; the oracle is then fed
         # the engine's own pre-processed patterns (the pre-processing itself: tests/test_gpu_config3.py)
         if rng.random() < 0.7:
@@ -137,6 +142,6 @@ for case in range(n_cases):
               f"sig={sig is not None} nav={nav is not None} chunk={chunk}: {err}")
         sys.exit(1)
     assert np.isfinite(s).all()
-    print(f"ok {case}: {sy}x{sx} m={m} n={n} k={k} {metric} mode={mode} chunk={chunk} pre={pre or '-'} members={members} "
+    print(f"ok {case}: {sy}x{sx} m={m} n={n} k={k} {metric} mode={mode} chunk={chunk} pre={pre or '-'} members={members} wide={wide or '-'} {dt_e.__name__}/{dt_d.__name__} "
           f"degenerate={degenerate or '-'} max|d|={np.abs(s - rs).max():.1e}", flush=True)
 print("STRESS_OK")
