@@ -484,6 +484,40 @@ int kpdi_nelder_mead_selftest(kpdi_ctx *ctx, int kind, int nvar, const double *x
                               const double *lower, const double *upper, double xatol,
                               double fatol, int maxiter, int maxfev, double *result);
 
+/* The top-k merge kernels alone, on lists the caller makes (tests/test_gpu_merge.py): everything is host memory.
+ * kpdi_merge_selftest: n_src <= 3 sources; src_scores / src_idx / src_cnt are arrays of n_src host pointers
+ * (src_cnt[j] NULL: no counts, else m x src_lists[j]), src_elems[j] the elements of source j's two buffers, so that
+ * padded (list_stride > len, row_stride > lists * len) and gathered (row_stride < list_stride) layouts can be given.
+ * seg_n segments (row0 / delta) translate the sources whose bit is set in seg_sources.  out_scores / out_idx:
+ * m x out_stride, prefilled by the caller, uploaded, merged into (columns out_offset .. out_offset + k) and read back
+ * whole.  force: -1 = the kernel the candidate count selects, 0..6 = merge_cached_kernel<4 | 12 | 24 | 48>,
+ * merge_block_kernel<24 | 64>, merge_kernel (csrc/merge_plan.h).  *launch_error: the HIP error of the launch (1,
+ * invalid value, when the forced kernel cannot hold the candidates - nothing is launched); *plan_ran: the kernel. */
+int kpdi_merge_selftest(kpdi_ctx *ctx, int n_src, const float *const *src_scores,
+                        const int32_t *const *src_idx, const int32_t *const *src_cnt,
+                        const int64_t *src_elems, const int32_t *src_lists, const int32_t *src_len,
+                        const int32_t *src_row_stride, const int32_t *src_list_stride, int m, int k,
+                        int out_stride, int out_offset, int seg_n, const int32_t *seg_row0,
+                        const int32_t *seg_delta, uint32_t seg_sources, float *out_scores,
+                        int32_t *out_idx, int force, int32_t *launch_error, int32_t *plan_ran);
+/* The float64 merge: run_s / run_i m x k or both NULL; in_place: the result replaces the running list (as the sweep
+ * does), else it goes to a buffer of its own, prefilled from out_s / out_i.  Candidates: `lists` lists of `len` per
+ * pattern in buffers of cand_elems elements.  cand_s32 (m x s32_stride) and uncertified both non-NULL: certification
+ * with max_diff, eps_floor and enumerated_all; *uncertified = patterns that failed it.  *launch_error as above (a
+ * pattern's entries beyond 150 KB of LDS are refused). */
+int kpdi_merge64_selftest(kpdi_ctx *ctx, int m, int k, const double *run_s, const int32_t *run_i,
+                          int in_place, const double *cand_s64, const int32_t *cand_i,
+                          int64_t cand_elems, int lists, int len, int64_t row_stride,
+                          int64_t list_stride, const float *cand_s32, int s32_stride, int s32_col,
+                          int enumerated_all, float max_diff, float eps_floor, double *out_s,
+                          int32_t *out_i, int32_t *uncertified, int32_t *launch_error);
+/* The queued initialisations' one launch: n <= 8 ranges of words[i] 32-bit words at byte_offset[i] (a multiple of 4)
+ * of one device buffer of buffer_words words, uploaded from and read back into `buffer`; value[i], or the shared
+ * bound's pattern when bound_used[i] >= 0. */
+int kpdi_fill_selftest(kpdi_ctx *ctx, int n, const int64_t *words, const uint32_t *value,
+                       const int32_t *bound_used, const int64_t *byte_offset, uint32_t *buffer,
+                       int64_t buffer_words);
+
 /* ---- orientation similarity map ---------------------------------
  * kikuchipy.indexing.orientation_similarity_map
  * (indexing/_orientation_similarity_map.py:30-152).  simulation_indices: ny*nx x keep_n

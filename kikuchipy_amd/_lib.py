@@ -163,6 +163,11 @@ SIGNATURES = {
     "kpdi_refine_objective": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp]),
     "kpdi_refine_solve": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i, _i, _vp]),
     "kpdi_nelder_mead_selftest": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _i, _i, _vp]),
+    "kpdi_merge_selftest": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.c_uint32,
+                                 _vp, _vp, _i, _vp, _vp]),
+    "kpdi_merge64_selftest": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _i, _i, _i64, _i64, _vp, _i, _i, _i,
+                                   C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
+    "kpdi_fill_selftest": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i64]),
     "kpdi_orientation_similarity_map": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "kpdi_dtype_size": (_sz, [_i]),
     "kpdi_plan_describe": (_i, [_i64, _i64, _i, _i, _i, _i, C.POINTER(Plan)]),
@@ -738,6 +743,92 @@ class Context:
                                                float(xatol), float(fatol), int(maxiter or 0), int(maxfev or 0),
                                                _ptr(res)))
         return res
+
+    def merge_selftest(self, sources, m, k, out_scores, out_idx, out_offset=0, segments=None, seg_sources=0, force=-1):
+        """merge.hip alone (kpdi_merge_selftest).  sources: up to three dicts of scores (float32), idx (int32), cnt
+        (int32 (m, lists) or None), lists, len, row_stride, list_stride; out_scores / out_idx: (m, out_stride), prefilled.
+        segments: (row0, delta).  Returns (scores, idx, launch error, kernel that ran)."""
+        n = len(sources)
+        keep = []
+
+        def table(key, dtype):
+            ptrs = (C.c_void_p * 3)()
+            for j, src in enumerate(sources):
+                if src.get(key) is not None:
+                    a = np.ascontiguousarray(src[key], dtype=dtype)
+                    keep.append(a)
+                    ptrs[j] = a.ctypes.data
+            return ptrs
+
+        ps, pi, pc = table("scores", np.float32), table("idx", np.int32), table("cnt", np.int32)
+        for j, src in enumerate(sources):
+            if src.get("cnt") is not None and np.asarray(src["cnt"]).size != m * src["lists"]:
+                raise KpdiError(f"source {j}: counts must have shape (m, lists)")
+            if np.asarray(src["scores"]).size != np.asarray(src["idx"]).size:
+                raise KpdiError(f"source {j}: scores and idx differ in size")
+        ints = {key: np.array([src[key] for src in sources], dtype=np.int32)
+                for key in ("lists", "len", "row_stride", "list_stride")}
+        elems = np.array([np.asarray(src["scores"]).size for src in sources], dtype=np.int64)
+        out_s = np.array(out_scores, dtype=np.float32, order="C")
+        out_i = np.array(out_idx, dtype=np.int32, order="C")
+        if out_s.shape != out_i.shape or out_s.ndim != 2 or out_s.shape[0] != m:
+            raise KpdiError("out_scores / out_idx must have shape (m, out_stride)")
+        row0 = delta = None
+        if segments is not None:
+            row0 = np.ascontiguousarray(segments[0], dtype=np.int32)
+            delta = np.ascontiguousarray(segments[1], dtype=np.int32)
+        err, ran = C.c_int32(0), C.c_int32(-1)
+        check(self._f.merge_selftest(self._h, n, C.addressof(ps), C.addressof(pi), C.addressof(pc), _ptr(elems),
+                                     _ptr(ints["lists"]), _ptr(ints["len"]), _ptr(ints["row_stride"]),
+                                     _ptr(ints["list_stride"]), int(m), int(k), out_s.shape[1], int(out_offset),
+                                     0 if row0 is None else row0.size, _ptr(row0), _ptr(delta), int(seg_sources),
+                                     _ptr(out_s), _ptr(out_i), int(force), C.addressof(err), C.addressof(ran)))
+        return out_s, out_i, err.value, ran.value
+
+    def merge64_selftest(self, k, cand_s64, cand_i, lists, length, row_stride, list_stride, out_s, out_i, run=None,
+                         in_place=False, cert=None):
+        """rescore.hip's merge64_kernel alone (kpdi_merge64_selftest).  run: (scores, idx) (m, k) or None; cert: dict of
+        cand_s32 (m, s32_stride), s32_col, max_diff, eps_floor, enumerated_all, or None.  Returns (scores, idx,
+        uncertified or None, launch error)."""
+        out_s = np.array(out_s, dtype=np.float64, order="C")
+        out_i = np.array(out_i, dtype=np.int32, order="C")
+        m = out_s.shape[0]
+        cs = np.ascontiguousarray(cand_s64, dtype=np.float64)
+        ci = np.ascontiguousarray(cand_i, dtype=np.int32)
+        rs = ri = s32 = None
+        if run is not None:
+            rs = np.ascontiguousarray(run[0], dtype=np.float64)
+            ri = np.ascontiguousarray(run[1], dtype=np.int32)
+            if rs.shape != (m, k) or ri.shape != (m, k):
+                raise KpdiError("the running list must have shape (m, k)")
+        if out_s.shape != (m, k) or out_i.shape != (m, k) or cs.size != ci.size:
+            raise KpdiError("out must have shape (m, k); candidate scores and indices the same size")
+        unc, err = C.c_int32(0), C.c_int32(0)
+        stride = col = 0
+        if cert is not None:
+            s32 = np.ascontiguousarray(cert["cand_s32"], dtype=np.float32)
+            if s32.ndim != 2 or s32.shape[0] != m:
+                raise KpdiError("cand_s32 must have shape (m, s32_stride)")
+            stride, col = s32.shape[1], int(cert["s32_col"])
+        check(self._f.merge64_selftest(self._h, m, int(k), _ptr(rs), _ptr(ri), int(bool(in_place)), _ptr(cs), _ptr(ci),
+                                       cs.size, int(lists), int(length), int(row_stride), int(list_stride), _ptr(s32),
+                                       stride, col, int(bool(cert and cert.get("enumerated_all"))),
+                                       float(cert["max_diff"]) if cert else 0.0, float(cert["eps_floor"]) if cert else 0.0,
+                                       _ptr(out_s), _ptr(out_i), C.addressof(unc) if cert is not None else None,
+                                       C.addressof(err)))
+        return out_s, out_i, (unc.value if cert is not None else None), err.value
+
+    def fill_selftest(self, buffer, ranges):
+        """merge.hip's fill_segments_kernel alone (kpdi_fill_selftest).  buffer: uint32 words; ranges: up to eight
+        (byte_offset, words, value, bound_used).  Returns the buffer after the launch."""
+        buf = np.array(buffer, dtype=np.uint32, order="C").ravel()
+        off = np.array([r[0] for r in ranges], dtype=np.int64)
+        words = np.array([r[1] for r in ranges], dtype=np.int64)
+        value = np.array([r[2] for r in ranges], dtype=np.uint32)
+        used = np.array([r[3] for r in ranges], dtype=np.int32)
+        check(self._f.fill_selftest(self._h, len(ranges), _ptr(words), _ptr(value), _ptr(used), _ptr(off), _ptr(buf),
+                                    buf.size))
+        return buf
 
     # -- result consumers
     def orientation_similarity_map(self, simulation_indices, shape, keep_n, n_best, from_n_best, offsets,

@@ -422,6 +422,170 @@ int kpdi_nelder_mead_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0,
   return KPDI_OK;
 }
 
+// ---- the merge and fill kernels on caller-made lists (tests/test_gpu_merge.py) ------------------------------------
+// Host arrays in, the whole output buffer out: a test decides every byte the kernels see, what lies behind a list's
+// count included.  Every extent is checked against the buffer sizes given before anything is launched.
+namespace {
+struct Upload {
+  DevBuf d;
+  hipError_t put(const void *host, size_t bytes, hipStream_t s) {
+    hipError_t e = d.reserve(bytes ? bytes : 4);
+    if (e != hipSuccess || !bytes) return e;
+    return hipMemcpyAsync(d.p, host, bytes, hipMemcpyHostToDevice, s);
+  }
+};
+}  // namespace
+
+int kpdi_merge_selftest(kpdi_ctx *c, int n_src, const float *const *src_scores, const int32_t *const *src_idx,
+                        const int32_t *const *src_cnt, const int64_t *src_elems, const int32_t *src_lists,
+                        const int32_t *src_len, const int32_t *src_row_stride, const int32_t *src_list_stride, int m,
+                        int k, int out_stride, int out_offset, int seg_n, const int32_t *seg_row0,
+                        const int32_t *seg_delta, uint32_t seg_sources, float *out_scores, int32_t *out_idx, int force,
+                        int32_t *launch_error, int32_t *plan_ran) {
+  if (!c || !src_scores || !src_idx || !src_cnt || !src_elems || !src_lists || !src_len || !src_row_stride ||
+      !src_list_stride || !out_scores || !out_idx || !launch_error || !plan_ran)
+    return fail(KPDI_EINVAL, "NULL argument");
+  if (n_src < 1 || n_src > 3) return fail(KPDI_EINVAL, "between 1 and 3 sources");
+  if (m < 1 || k < 1 || out_offset < 0 || (int64_t)out_offset + k > out_stride)
+    return fail(KPDI_EINVAL, "need m, k >= 1 and out_offset + k <= out_stride");
+  if (seg_n < 0 || seg_n > kpdi::INDEX_SEGMENTS || (seg_n > 0 && (!seg_row0 || !seg_delta)))
+    return fail(KPDI_EINVAL, "between 0 and %d segments", kpdi::INDEX_SEGMENTS);
+  int64_t candidates = 0;
+  for (int j = 0; j < n_src; ++j) {
+    if (!src_scores[j] || !src_idx[j]) return fail(KPDI_EINVAL, "source %d: NULL lists", j);
+    if (src_lists[j] < 1 || src_len[j] < 1 || src_row_stride[j] < 0 || src_list_stride[j] < 0)
+      return fail(KPDI_EINVAL, "source %d: bad shape", j);
+    const int64_t last = (int64_t)(m - 1) * src_row_stride[j] + (int64_t)(src_lists[j] - 1) * src_list_stride[j] + src_len[j];
+    if (last > src_elems[j]) return fail(KPDI_EINVAL, "source %d: its lists end at element %lld of %lld", j, (long long)last, (long long)src_elems[j]);
+    candidates += (int64_t)src_lists[j] * src_len[j];
+  }
+  if (candidates > (1 << 22)) return fail(KPDI_EINVAL, "too many candidates for a self-test");
+  int rc = use_device(c);
+  if (rc) return rc;
+  Upload us[3], ui[3], uc[3], uos, uoi;
+  kpdi::MergeLaunch l{};
+  l.m = m;
+  l.k = k;
+  l.n_src = n_src;
+  for (int j = 0; j < n_src; ++j) {
+    HIPCHK(us[j].put(src_scores[j], (size_t)src_elems[j] * sizeof(float), c->stream));
+    HIPCHK(ui[j].put(src_idx[j], (size_t)src_elems[j] * sizeof(int), c->stream));
+    if (src_cnt[j]) HIPCHK(uc[j].put(src_cnt[j], (size_t)m * src_lists[j] * sizeof(int), c->stream));
+    l.src_scores[j] = us[j].d.as<float>();
+    l.src_idx[j] = ui[j].d.as<int>();
+    l.src_cnt[j] = src_cnt[j] ? uc[j].d.as<int>() : nullptr;
+    l.src_lists[j] = src_lists[j];
+    l.src_len[j] = src_len[j];
+    l.src_row_stride[j] = src_row_stride[j];
+    l.src_list_stride[j] = src_list_stride[j];
+  }
+  const size_t n_out = (size_t)m * out_stride;
+  HIPCHK(uos.put(out_scores, n_out * sizeof(float), c->stream));
+  HIPCHK(uoi.put(out_idx, n_out * sizeof(int), c->stream));
+  l.out_scores = uos.d.as<float>();
+  l.out_idx = uoi.d.as<int>();
+  l.out_stride = out_stride;
+  l.out_offset = out_offset;
+  l.seg.n = seg_n;
+  for (int t = 0; t < kpdi::INDEX_SEGMENTS; ++t) {
+    l.seg.row0[t] = t < seg_n ? seg_row0[t] : INT_MAX;
+    l.seg.delta[t] = t < seg_n ? seg_delta[t] : 0;
+  }
+  l.seg_sources = seg_sources;
+  int ran = -1;
+  const hipError_t e = kpdi::launch_merge(l, c->stream, force, &ran);
+  *launch_error = (int32_t)e;
+  *plan_ran = ran;
+  HIPCHK(hipMemcpyAsync(out_scores, uos.d.p, n_out * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(out_idx, uoi.d.p, n_out * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return KPDI_OK;
+}
+
+int kpdi_merge64_selftest(kpdi_ctx *c, int m, int k, const double *run_s, const int32_t *run_i, int in_place,
+                          const double *cand_s64, const int32_t *cand_i, int64_t cand_elems, int lists, int len,
+                          int64_t row_stride, int64_t list_stride, const float *cand_s32, int s32_stride, int s32_col,
+                          int enumerated_all, float max_diff, float eps_floor, double *out_s, int32_t *out_i,
+                          int32_t *uncertified, int32_t *launch_error) {
+  if (!c || !cand_s64 || !cand_i || !out_s || !out_i || !launch_error) return fail(KPDI_EINVAL, "NULL argument");
+  if ((run_s == nullptr) != (run_i == nullptr)) return fail(KPDI_EINVAL, "give both halves of the running list or neither");
+  if (in_place && !run_s) return fail(KPDI_EINVAL, "in place needs a running list");
+  if ((cand_s32 == nullptr) != (uncertified == nullptr)) return fail(KPDI_EINVAL, "certification needs cand_s32 and uncertified");
+  if (m < 1 || k < 1 || lists < 1 || len < 1 || row_stride < 0 || list_stride < 0) return fail(KPDI_EINVAL, "bad shape");
+  if ((int64_t)(m - 1) * row_stride + (int64_t)(lists - 1) * list_stride + len > cand_elems)
+    return fail(KPDI_EINVAL, "the candidate lists end behind their buffer");
+  if (cand_s32 && (s32_col < 0 || s32_col >= s32_stride)) return fail(KPDI_EINVAL, "s32_col outside a row");
+  int rc = use_device(c);
+  if (rc) return rc;
+  Upload urs, uri, ucs, uci, us32, uos, uoi, ucert;
+  const size_t n_out = (size_t)m * k;
+  if (run_s) {
+    HIPCHK(urs.put(run_s, n_out * sizeof(double), c->stream));
+    HIPCHK(uri.put(run_i, n_out * sizeof(int), c->stream));
+  }
+  HIPCHK(ucs.put(cand_s64, (size_t)cand_elems * sizeof(double), c->stream));
+  HIPCHK(uci.put(cand_i, (size_t)cand_elems * sizeof(int), c->stream));
+  HIPCHK(uos.put(out_s, n_out * sizeof(double), c->stream));
+  HIPCHK(uoi.put(out_i, n_out * sizeof(int), c->stream));
+  const unsigned cert[2] = {0u, 0u};  // (max_diff's bits, the counter)
+  HIPCHK(ucert.put(cert, sizeof(cert), c->stream));
+  HIPCHK(hipMemcpyAsync(ucert.d.p, &max_diff, sizeof(float), hipMemcpyHostToDevice, c->stream));
+  if (cand_s32) HIPCHK(us32.put(cand_s32, (size_t)m * s32_stride * sizeof(float), c->stream));
+  kpdi::Merge64Launch g{};
+  g.m = m;
+  g.k = k;
+  g.run_s = run_s ? urs.d.as<double>() : nullptr;
+  g.run_i = run_s ? uri.d.as<int>() : nullptr;
+  g.cand_s64 = ucs.d.as<double>();
+  g.cand_i = uci.d.as<int>();
+  g.lists = lists;
+  g.len = len;
+  g.row_stride = row_stride;
+  g.list_stride = list_stride;
+  g.out_s = in_place ? urs.d.as<double>() : uos.d.as<double>();
+  g.out_i = in_place ? uri.d.as<int>() : uoi.d.as<int>();
+  g.cand_s32 = cand_s32 ? us32.d.as<float>() : nullptr;
+  g.s32_stride = s32_stride;
+  g.s32_col = s32_col;
+  g.enumerated_all = enumerated_all;
+  g.max_diff = ucert.d.as<unsigned>();
+  g.eps_floor = eps_floor;
+  g.uncertified = cand_s32 ? (int *)(ucert.d.as<unsigned>() + 1) : nullptr;
+  *launch_error = (int32_t)kpdi::launch_merge64(g, c->stream);
+  HIPCHK(hipMemcpyAsync(out_s, g.out_s, n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(out_i, g.out_i, n_out * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (uncertified) HIPCHK(hipMemcpyAsync(uncertified, ucert.d.as<unsigned>() + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return KPDI_OK;
+}
+
+int kpdi_fill_selftest(kpdi_ctx *c, int n, const int64_t *words, const uint32_t *value, const int32_t *bound_used,
+                       const int64_t *byte_offset, uint32_t *buffer, int64_t buffer_words) {
+  if (!c || !words || !value || !bound_used || !byte_offset || !buffer) return fail(KPDI_EINVAL, "NULL argument");
+  if (n < 0 || n > kpdi::FILL_SEGMENTS) return fail(KPDI_EINVAL, "between 0 and %d ranges", kpdi::FILL_SEGMENTS);
+  if (buffer_words < 1 || buffer_words > (1 << 24)) return fail(KPDI_EINVAL, "bad buffer size");
+  for (int i = 0; i < n; ++i)
+    if (words[i] < 0 || byte_offset[i] < 0 || (byte_offset[i] & 3) || byte_offset[i] / 4 + words[i] > buffer_words ||
+        bound_used[i] > kpdi::BOUND_SLOTS)
+      return fail(KPDI_EINVAL, "range %d: outside the buffer, off a word boundary or bound_used > %d", i, kpdi::BOUND_SLOTS);
+  int rc = use_device(c);
+  if (rc) return rc;
+  Upload u;
+  HIPCHK(u.put(buffer, (size_t)buffer_words * 4, c->stream));
+  kpdi::FillSegments f{};
+  f.n = n;
+  for (int i = 0; i < n; ++i) {
+    f.p[i] = (unsigned *)((char *)u.d.p + byte_offset[i]);
+    f.words[i] = (unsigned long long)words[i];
+    f.value[i] = value[i];
+    f.bound_used[i] = bound_used[i];
+  }
+  HIPCHK(kpdi::launch_fill_segments(f, c->stream));
+  HIPCHK(hipMemcpyAsync(buffer, u.d.p, (size_t)buffer_words * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return KPDI_OK;
+}
+
 // ---- orientation similarity map ---------------------------------------------------
 int kpdi_orientation_similarity_map(kpdi_ctx *c, const int64_t *simulation_indices, int ny, int nx, int keep_n,
                                     int n_best, int from_n_best, const int32_t *footprint_offsets, int n_fp,

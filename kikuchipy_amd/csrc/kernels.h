@@ -191,7 +191,9 @@ struct MergeLaunch {
   IndexSegments seg;    // seg.n > 0: the sources in `seg_sources` (bit j = source j) hold ROWS of a coalesced matrix
   unsigned seg_sources = 0;
 };
-hipError_t launch_merge(const MergeLaunch &a, hipStream_t s);
+// `force` (merge_plan.h: MergePlanId, -1 = by candidate count): run that kernel, hipErrorInvalidValue when it cannot hold
+// the candidates - only kpdi_merge_selftest passes it; `ran`: the kernel that was launched
+hipError_t launch_merge(const MergeLaunch &a, hipStream_t s, int force = -1, int *ran = nullptr);
 hipError_t launch_fill_topk(float *scores, int *idx, int64_t n, hipStream_t s);
 hipError_t launch_fill_u32(unsigned *p, unsigned value, int64_t n, hipStream_t s);
 // ONE launch for all the small initialisations in front of a sweep (running lists, shared bound, tile counters, the zero

@@ -17,6 +17,7 @@
 // Latency-bound and tiny next to the match kernel.
 #include <algorithm>
 #include "kernels.h"
+#include "merge_plan.h"
 #include <limits.h>
 #include <math.h>
 
@@ -138,9 +139,8 @@ __device__ __forceinline__ unsigned long long candidate_key(const MergeArgs &a, 
   const int stride = in0 ? a.stride[0] : (in1 ? a.stride[1] : a.stride[2]);
   const int list_stride = in0 ? a.list_stride[0] : (in1 ? a.list_stride[1] : a.list_stride[2]);
   const int local = c - (in0 ? 0 : (in1 ? end0 : end1));
-  // local / len without an integer division: local < 16384, len <= 32, so the float quotient of
-  // local + 0.5 is at least 1/64 away from an integer (and float holds it to 2^-9)
-  const int l = (int)(((float)local + 0.5f) / (float)len);
+  // local / len without an integer division (merge_plan.h: exact for local < 16384 and every len a caller passes)
+  const int l = merge_list_index(local, len);
   const size_t e = (size_t)m * stride + (size_t)l * list_stride + (local - l * len);
   // a source with counts: only the first cnt[m][l] entries of a list were written - what lies behind them is stale memory
   const int *pc = in0 ? a.cnt[0] : (in1 ? a.cnt[1] : a.cnt[2]);
@@ -292,7 +292,8 @@ __global__ __launch_bounds__(256) void merge_block_kernel(MergeArgs a) {
   }
 }
 
-hipError_t launch_merge(const MergeLaunch &l, hipStream_t s) {
+hipError_t launch_merge(const MergeLaunch &l, hipStream_t s, int force, int *ran) {
+  if (ran) *ran = MERGE_PLAN_AUTO;
   if (l.m <= 0 || l.k <= 0) return hipSuccess;
   MergeArgs a;
   a.m = l.m;
@@ -319,21 +320,23 @@ hipError_t launch_merge(const MergeLaunch &l, hipStream_t s) {
   }
   int candidates = 0;
   for (int j = 0; j < l.n_src; ++j) candidates += l.src_lists[j] * l.src_len[j];
-  const dim3 grid((l.m + 3) / 4), block(256);
-  if (candidates <= 4 * 64)
-    hipLaunchKernelGGL(merge_cached_kernel<4>, grid, block, 0, s, a);
-  else if (candidates <= 12 * 64)
-    hipLaunchKernelGGL(merge_cached_kernel<12>, grid, block, 0, s, a);
-  else if (candidates <= 24 * 64)
-    hipLaunchKernelGGL(merge_cached_kernel<24>, grid, block, 0, s, a);
-  else if (candidates <= 48 * 64)
-    hipLaunchKernelGGL(merge_cached_kernel<48>, grid, block, 0, s, a);
-  else if (candidates <= 24 * 256)
-    hipLaunchKernelGGL(merge_block_kernel<24>, dim3(l.m), block, 0, s, a);
-  else if (candidates <= 64 * 256)
-    hipLaunchKernelGGL(merge_block_kernel<64>, dim3(l.m), block, 0, s, a);
-  else
-    hipLaunchKernelGGL(merge_kernel, grid, block, 0, s, a);
+  // (merge_plan.h) `force`: a named kernel instead, if it holds the candidates - the self-test's way to every kernel
+  MergePlan plan = merge_plan(candidates);
+  if (force != MERGE_PLAN_AUTO) {
+    plan = merge_plan_of(force);
+    if (plan.id != force || candidates > plan.capacity) return hipErrorInvalidValue;
+  }
+  if (ran) *ran = plan.id;
+  const dim3 grid((l.m + 3) / 4), block(MERGE_BLOCK_THREADS);
+  switch (plan.id) {
+    case MERGE_PLAN_CACHED4: hipLaunchKernelGGL(merge_cached_kernel<4>, grid, block, 0, s, a); break;
+    case MERGE_PLAN_CACHED12: hipLaunchKernelGGL(merge_cached_kernel<12>, grid, block, 0, s, a); break;
+    case MERGE_PLAN_CACHED24: hipLaunchKernelGGL(merge_cached_kernel<24>, grid, block, 0, s, a); break;
+    case MERGE_PLAN_CACHED48: hipLaunchKernelGGL(merge_cached_kernel<48>, grid, block, 0, s, a); break;
+    case MERGE_PLAN_BLOCK24: hipLaunchKernelGGL(merge_block_kernel<24>, dim3(l.m), block, 0, s, a); break;
+    case MERGE_PLAN_BLOCK64: hipLaunchKernelGGL(merge_block_kernel<64>, dim3(l.m), block, 0, s, a); break;
+    default: hipLaunchKernelGGL(merge_kernel, grid, block, 0, s, a); break;
+  }
   return hipGetLastError();
 }
 
