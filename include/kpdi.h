@@ -313,6 +313,44 @@ int kpdi_downsample(kpdi_ctx *ctx, int factor, int dtype_out);
  * detector above 256 MB of float64 per pattern (5792 x 5792).  Kernel: csrc/preproc.hip (dynamic_background_kernel). */
 int kpdi_get_dynamic_background(kpdi_ctx *ctx, int filter_domain, double std, double truncate, int dtype_out, void *out);
 
+/* ---- PCA decomposition and its model (EBSD.decomposition as the reference's multivariate-analysis workflow uses it;
+ * EBSD.get_decomposition_model, signals/ebsd.py:2665-2723, signals/util/_dask.py:283-332) --------------------------------
+ * All four calls work on the resident patterns (the six dtypes of kpdi_rescale_intensity) AFTER the recorded background
+ * steps and ignore the navigation mask.  M is the number of resident patterns, K = sy * sx, X the M x K matrix of the
+ * patterns with row-major pixels, every value widened exactly to float64.
+ * `centre`: KPDI_CENTRE_NONE; KPDI_CENTRE_NAVIGATION subtracts from every pixel its mean over all patterns (the mean
+ * pattern); KPDI_CENTRE_SIGNAL subtracts from every pattern its mean over its pixels.  Means are float64 sums in a fixed
+ * order without atomics, divided once (csrc/decomp.hip states the order); xc = double(x) - mean is rounded once, when a
+ * tile is staged: the centred matrix Xc is never stored.
+ * The products are float64 MFMA tile kernels with one fixed summation order per output: results do not depend on the
+ * launch, bit for bit (csrc/decomp.hip, csrc/decomp_plan.h).  The eigen-solve between kpdi_decomposition_gram and
+ * kpdi_decomposition_apply is the caller's (kikuchipy_amd/pattern/_decomposition.py: numpy.linalg.eigh).
+ *
+ * kpdi_decomposition_gram: the Gram matrix of Xc over its shorter side into `gram_out` (host, side * side float64, both
+ *   triangles, symmetric bit for bit): K <= M gives Xc^T Xc with *side = K, *transposed = 0; K > M gives Xc Xc^T with
+ *   *side = M, *transposed = 1.  `mean_out` (host; may be NULL) receives the M ("signal") or K ("navigation") means.
+ *   KPDI_EINVAL: an unknown `centre`, NULL, side = min(M, K) above 8192 (bin the patterns first: kpdi_downsample) - all
+ *   before any launch - and patterns that hold non-finite values (the trace is not finite; the outputs are written).
+ * kpdi_decomposition_apply: transposed_op 0: out (M x c) = Xc basis (K x c); transposed_op 1: out (K x c) = Xc^T basis
+ *   (M x c); host float64, row-major, 1 <= c <= min(M, K).
+ * kpdi_decomposition_model: every resident pattern becomes sum_j loadings[m, j] factors[k, j] + mean, accumulated in
+ *   float64 and rounded once to `dtype_out` (KPDI_F32 or KPDI_F64 only).  `loadings` (M x c) and `factors` (K x c) are
+ *   host arrays of `dtype_out`; `mean` is NULL or host float64: K means per pixel (mean_kind KPDI_CENTRE_NAVIGATION) or M
+ *   means per pattern (KPDI_CENTRE_SIGNAL).  As in kpdi_rescale_intensity the patterns take the new dtype and prepared
+ *   rows are forgotten.
+ * kpdi_change_dtype: ndarray.astype(dtype_out) of the resident patterns with the casts of kpdi_rescale_intensity
+ *   (to integers: truncate to int32, NaN and out-of-range values give INT32_MIN, keep the low bits; to float32: round
+ *   to nearest); `dtype_out` is one of the six. */
+#define KPDI_CENTRE_NONE 0
+#define KPDI_CENTRE_NAVIGATION 1
+#define KPDI_CENTRE_SIGNAL 2
+int kpdi_decomposition_gram(kpdi_ctx *ctx, int centre, double *gram_out, double *mean_out, int64_t *side, int *transposed);
+int kpdi_decomposition_apply(kpdi_ctx *ctx, int centre, int transposed_op, const double *basis, int n_components,
+                             double *out);
+int kpdi_decomposition_model(kpdi_ctx *ctx, const void *loadings, const void *factors, int n_components, const double *mean,
+                             int mean_kind, int dtype_out);
+int kpdi_change_dtype(kpdi_ctx *ctx, int dtype_out);
+
 /* ---- dictionary sweep (_dictionary_indexing loop, indexing/_dictionary_indexing.py:94-128)
  * One call = one loop iteration: prepare_dictionary (cast, mask, normalise) +
  * match + top-k of the chunk + merge into the running best-k, all on the GPU.

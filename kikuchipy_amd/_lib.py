@@ -23,6 +23,8 @@ GATHER_NAMES = {GATHER_RCCL: "rccl", GATHER_P2P: "p2p", GATHER_NONE: "none"}
 F64_CERTIFICATES = {0: None, 1: "statistical", 2: "worstcase"}
 OP_SUBTRACT, OP_DIVIDE = 0, 1
 DOMAIN_FREQUENCY, DOMAIN_SPATIAL = 0, 1
+CENTRE_NONE, CENTRE_NAVIGATION, CENTRE_SIGNAL = 0, 1, 2  # kpdi_decomposition_*: what centring subtracts
+DECOMPOSITION_MAX_SIDE = 8192  # csrc/decomp_plan.h, DEC_MAX_SIDE
 UNIQUE_ID_BYTES = 128
 REFINE_ORI, REFINE_PC, REFINE_ORI_PC = 0, 1, 2
 REFINE_SIZES = {REFINE_ORI: (3, 3), REFINE_PC: (3, 4), REFINE_ORI_PC: (6, 0)}  # (control variables, fixed values)
@@ -140,6 +142,10 @@ SIGNATURES = {
     "kpdi_adaptive_histogram_equalization": (_i, [_vp, _i, _i, _i, _i]),
     "kpdi_downsample": (_i, [_vp, _i, _i]),
     "kpdi_get_dynamic_background": (_i, [_vp, _i, C.c_double, C.c_double, _i, _vp]),
+    "kpdi_decomposition_gram": (_i, [_vp, _i, _vp, _vp, C.POINTER(_i64), C.POINTER(_i)]),
+    "kpdi_decomposition_apply": (_i, [_vp, _i, _i, _vp, _i, _vp]),
+    "kpdi_decomposition_model": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i]),
+    "kpdi_change_dtype": (_i, [_vp, _i]),
     "kpdi_average_neighbour_patterns": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i]),
     "kpdi_neighbour_dot_products": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "kpdi_push_dictionary_chunk": (_i, [_vp, _vp, _i, _i64, _i64]),
@@ -522,6 +528,63 @@ class Context:
         check(self._f.get_dynamic_background(self._h, int(filter_domain), 0.0 if std is None else float(std),
                                              float(truncate), dtype_code(dt), _ptr(out)))
         return out
+
+    def change_dtype(self, dtype_out):
+        """`ndarray.astype(dtype_out)` of the resident patterns (after the recorded background steps), which take the
+        new dtype (include/kpdi.h, kpdi_change_dtype)."""
+        dt = np.dtype(dtype_out)
+        check(self._f.change_dtype(self._h, dtype_code(dt)))
+        self._exp_dtype = dt
+
+    def decomposition_gram(self, centre=CENTRE_NONE):
+        """The float64 Gram matrix of the centred resident patterns over their shorter side: (gram (side, side), the
+        means that `centre` removed or None, transposed) - `transposed` False: Xc^T Xc over the pixels, True: Xc Xc^T
+        over the patterns (include/kpdi.h, kpdi_decomposition_gram).  The resident patterns stay as they are."""
+        m, k = int(self._exp_shape[0]), int(np.prod(self._detector))
+        side = min(m, k)
+        if side > DECOMPOSITION_MAX_SIDE:  # (the library's refusal, before a side x side array is asked for)
+            raise KpdiError(f"decomposition of {m} patterns of {k} pixels: the Gram matrix would have {side} rows, above "
+                            f"the limit of {DECOMPOSITION_MAX_SIDE} (it is solved on the host); bin the patterns first "
+                            "(downsample)")
+        gram = np.empty((side, side), dtype=np.float64)
+        mean = None if centre == CENTRE_NONE else np.empty(m if centre == CENTRE_SIGNAL else k, dtype=np.float64)
+        n, t = C.c_int64(0), C.c_int(0)
+        check(self._f.decomposition_gram(self._h, int(centre), _ptr(gram), _ptr(mean), C.byref(n), C.byref(t)))
+        return gram, mean, bool(t.value)
+
+    def decomposition_apply(self, basis, centre=CENTRE_NONE, transposed_op=False):
+        """Xc basis ((pixels, c) -> (patterns, c)) or, `transposed_op`, Xc^T basis ((patterns, c) -> (pixels, c)) in
+        float64, Xc the resident patterns centred as in `decomposition_gram` (include/kpdi.h,
+        kpdi_decomposition_apply)."""
+        m, k = int(self._exp_shape[0]), int(np.prod(self._detector))
+        b = np.ascontiguousarray(basis, dtype=np.float64)
+        rows_in, rows_out = (m, k) if transposed_op else (k, m)
+        if b.ndim != 2 or b.shape[0] != rows_in:
+            raise KpdiError(f"basis of shape {b.shape}: ({rows_in}, c) expected")
+        out = np.empty((rows_out, b.shape[1]), dtype=np.float64)
+        check(self._f.decomposition_apply(self._h, int(centre), int(bool(transposed_op)), _ptr(b), int(b.shape[1]), _ptr(out)))
+        return out
+
+    def decomposition_model(self, loadings, factors, mean=None, mean_kind=CENTRE_NONE, dtype_out=np.float32):
+        """Every resident pattern becomes loadings[m] . factors[k] + mean, summed in float64 and rounded once to
+        `dtype_out` (float32 / float64), the resident patterns' new dtype; `mean`: None, or the float64 means per pixel
+        (`mean_kind` CENTRE_NAVIGATION) or per pattern (CENTRE_SIGNAL) (include/kpdi.h, kpdi_decomposition_model)."""
+        dt = np.dtype(dtype_out)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise KpdiError(f"dtype_out {dt}: the decomposition model is written as float32 or float64")
+        m, k = int(self._exp_shape[0]), int(np.prod(self._detector))
+        lo, fa = np.ascontiguousarray(loadings, dtype=dt), np.ascontiguousarray(factors, dtype=dt)
+        if lo.ndim != 2 or fa.ndim != 2 or lo.shape[0] != m or fa.shape[0] != k or lo.shape[1] != fa.shape[1]:
+            raise KpdiError(f"loadings {lo.shape} and factors {fa.shape}: ({m}, c) and ({k}, c) expected")
+        mu = None
+        if mean is not None:
+            mu = np.ascontiguousarray(mean, dtype=np.float64).ravel()
+            want = {CENTRE_NAVIGATION: k, CENTRE_SIGNAL: m}.get(mean_kind)
+            if want is None or mu.size != want:
+                raise KpdiError(f"mean of {mu.size} values with mean_kind {mean_kind}")
+        check(self._f.decomposition_model(self._h, _ptr(lo), _ptr(fa), int(lo.shape[1]), _ptr(mu), int(mean_kind),
+                                          dtype_code(dt)))
+        self._exp_dtype = dt
 
     def normalize_intensity(self, num_std=1, divide_by_square_root=False, dtype_out=None):
         """(p - mean) / (num_std * std [* sqrt(size)]) of every resident pattern into `dtype_out` (None: the patterns'

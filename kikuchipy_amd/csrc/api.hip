@@ -287,7 +287,7 @@ static int upload_taps(kpdi_ctx *c, const std::vector<double> &taps) {
 
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.9.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.10.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 
@@ -1048,6 +1048,162 @@ int kpdi_get_dynamic_background(kpdi_ctx *c, int filter_domain, double std, doub
     return fail(KPDI_EHIP, "dynamic background kernel: %s (dtype %d -> %d, %dx%d)", hipGetErrorString(e), c->exp_dtype,
                 dtype_out, c->sy, c->sx);
   return kpdi::results_to_host(c, out, c->int_out.p, obytes);
+}
+
+}  // extern "C"
+
+namespace kpdi {
+
+// what the decomposition calls share once their own arguments are checked: the plan of the resident set (refused above
+// DEC_MAX_SIDE), the recorded background steps, and the means that `centre` removes, left in c->dec_mean
+static int start_decomposition(kpdi_ctx *c, int centre, DecPlan *plan, DecLaunch *a) {
+  if (centre != DEC_CENTRE_NONE && centre != DEC_CENTRE_NAVIGATION && centre != DEC_CENTRE_SIGNAL)
+    return fail(KPDI_EINVAL, "centre %d: 0 (none), 1 (\"navigation\") or 2 (\"signal\")", centre);
+  *plan = dec_plan(c->m_all, c->npix);
+  if (plan->too_large)
+    return fail(KPDI_EINVAL, "decomposition of %lld patterns of %d pixels: the Gram matrix would have %lld rows, above the "
+                             "limit of %lld (it is solved on the host); bin the patterns first (downsample)",
+                (long long)c->m_all, c->npix, (long long)plan->side, (long long)DEC_MAX_SIDE);
+  if (!plan->ok) return fail(KPDI_EINVAL, "decomposition of %lld patterns of %d pixels: no kernel takes this shape",
+                             (long long)c->m_all, c->npix);
+  int rc = start_pattern_op(c);
+  if (rc) return rc;
+  *a = DecLaunch{};
+  a->patterns = c->exp_raw.p;
+  a->dtype = c->exp_dtype;
+  a->m = c->m_all;
+  a->k = c->npix;
+  a->centre = centre;
+  if (centre == DEC_CENTRE_NONE) return KPDI_OK;
+  const size_t n_mean = centre == DEC_CENTRE_SIGNAL ? (size_t)a->m : (size_t)a->k;
+  const size_t n_part = centre == DEC_CENTRE_NAVIGATION ? (size_t)dec_mean_chunks(a->m) * (size_t)a->k : 0;
+  HIPCHK(c->dec_mean.reserve((n_mean + n_part) * sizeof(double)));
+  a->mean = c->dec_mean.as<double>();
+  a->mean_partial = n_part ? a->mean + n_mean : nullptr;
+  hipError_t e = launch_decomposition_means(*a, c->stream);
+  if (e != hipSuccess) return fail(KPDI_EHIP, "decomposition means kernel: %s", hipGetErrorString(e));
+  return KPDI_OK;
+}
+
+}  // namespace kpdi
+
+extern "C" {
+
+int kpdi_decomposition_gram(kpdi_ctx *c, int centre, double *gram_out, double *mean_out, int64_t *side, int *transposed) {
+  int rc = kpdi::check_patterns(c, "decomposition");
+  if (rc) return rc;
+  if (!gram_out || !side || !transposed) return fail(KPDI_EINVAL, "gram_out, side or transposed is NULL");
+  kpdi::DecPlan plan;
+  kpdi::DecLaunch a;
+  rc = kpdi::start_decomposition(c, centre, &plan, &a);
+  if (rc) return rc;
+  const size_t n = (size_t)plan.side;
+  HIPCHK(c->dec_out.reserve(n * n * sizeof(double)));
+  hipError_t e = kpdi::launch_decomposition_gram(a, plan.transposed, c->dec_out.as<double>(), c->stream);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "decomposition Gram kernel: %s (dtype %d, %lld x %d)", hipGetErrorString(e), c->exp_dtype,
+                (long long)c->m_all, c->npix);
+  rc = kpdi::results_to_host(c, gram_out, c->dec_out.p, n * n * sizeof(double));
+  if (rc) return rc;
+  if (mean_out && centre != kpdi::DEC_CENTRE_NONE) {
+    rc = kpdi::results_to_host(c, mean_out, a.mean, (size_t)(centre == kpdi::DEC_CENTRE_SIGNAL ? a.m : a.k) * sizeof(double));
+    if (rc) return rc;
+  }
+  *side = plan.side;
+  *transposed = plan.transposed;
+  double trace = 0;
+  for (size_t i = 0; i < n; ++i) trace += gram_out[i * n + i];
+  if (!std::isfinite(trace)) return fail(KPDI_EINVAL, "patterns hold non-finite values: the trace of the Gram matrix is not finite");
+  return KPDI_OK;
+}
+
+int kpdi_decomposition_apply(kpdi_ctx *c, int centre, int transposed_op, const double *basis, int n_components, double *out) {
+  int rc = kpdi::check_patterns(c, "decomposition");
+  if (rc) return rc;
+  if (!basis || !out) return fail(KPDI_EINVAL, "basis or out is NULL");
+  if (transposed_op != 0 && transposed_op != 1) return fail(KPDI_EINVAL, "transposed_op %d: 0 (Xc basis) or 1 (Xc^T basis)", transposed_op);
+  const int64_t side = c->m_all < c->npix ? c->m_all : c->npix;
+  if (n_components < 1 || n_components > side)
+    return fail(KPDI_EINVAL, "%d components: between 1 and min(patterns, pixels) = %lld", n_components, (long long)side);
+  kpdi::DecPlan plan;
+  kpdi::DecLaunch a;
+  rc = kpdi::start_decomposition(c, centre, &plan, &a);
+  if (rc) return rc;
+  const size_t in_rows = transposed_op ? (size_t)a.m : (size_t)a.k, out_rows = transposed_op ? (size_t)a.k : (size_t)a.m;
+  const size_t in_bytes = in_rows * n_components * sizeof(double), out_bytes = out_rows * n_components * sizeof(double);
+  HIPCHK(c->dec_in.reserve(in_bytes));
+  HIPCHK(c->dec_out.reserve(out_bytes));
+  HIPCHK(hipMemcpyAsync(c->dec_in.p, basis, in_bytes, hipMemcpyHostToDevice, c->stream));
+  hipError_t e = kpdi::launch_decomposition_apply(a, transposed_op, c->dec_in.as<double>(), n_components, c->dec_out.as<double>(),
+                                                  c->stream);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "decomposition apply kernel: %s (dtype %d, %lld x %d, %d components)", hipGetErrorString(e),
+                c->exp_dtype, (long long)c->m_all, c->npix, n_components);
+  return kpdi::results_to_host(c, out, c->dec_out.p, out_bytes);  // (synchronises: `basis` is read)
+}
+
+int kpdi_decomposition_model(kpdi_ctx *c, const void *loadings, const void *factors, int n_components, const double *mean,
+                             int mean_kind, int dtype_out) {
+  int rc = kpdi::check_patterns(c, "the decomposition model");
+  if (rc) return rc;
+  if (!loadings || !factors) return fail(KPDI_EINVAL, "loadings or factors is NULL");
+  if (dtype_out != KPDI_F32 && dtype_out != KPDI_F64)
+    return fail(KPDI_EINVAL, "dtype_out %d: the decomposition model is written as float32 or float64", dtype_out);
+  if (mean && mean_kind != kpdi::DEC_CENTRE_NAVIGATION && mean_kind != kpdi::DEC_CENTRE_SIGNAL)
+    return fail(KPDI_EINVAL, "mean_kind %d: 1 (a mean per pixel) or 2 (a mean per pattern)", mean_kind);
+  const int64_t side = c->m_all < c->npix ? c->m_all : c->npix;
+  if (n_components < 1 || n_components > side)
+    return fail(KPDI_EINVAL, "%d components: between 1 and min(patterns, pixels) = %lld", n_components, (long long)side);
+  rc = kpdi::start_pattern_op(c);
+  if (rc) return rc;
+  const size_t es = kpdi::dtype_size(dtype_out), m = (size_t)c->m_all, k = (size_t)c->npix;
+  const size_t n_mean = !mean ? 0 : mean_kind == kpdi::DEC_CENTRE_SIGNAL ? m : k;
+  HIPCHK(c->dec_in.reserve(m * n_components * es));
+  HIPCHK(c->dec_in2.reserve(k * n_components * es));
+  HIPCHK(c->int_out.reserve(m * k * es));
+  HIPCHK(hipMemcpyAsync(c->dec_in.p, loadings, m * n_components * es, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->dec_in2.p, factors, k * n_components * es, hipMemcpyHostToDevice, c->stream));
+  if (n_mean) {
+    HIPCHK(c->dec_mean.reserve(n_mean * sizeof(double)));
+    HIPCHK(hipMemcpyAsync(c->dec_mean.p, mean, n_mean * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  kpdi::DecModelLaunch a{};
+  a.loadings = c->dec_in.p;
+  a.factors = c->dec_in2.p;
+  a.m = c->m_all;
+  a.k = c->npix;
+  a.c = n_components;
+  a.mean = n_mean ? c->dec_mean.as<double>() : nullptr;
+  a.mean_kind = mean_kind;
+  a.dst = c->int_out.p;
+  a.dtype_out = dtype_out;
+  hipError_t e = kpdi::launch_decomposition_model(a, c->stream);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "decomposition model kernel: %s (%lld x %d, %d components)", hipGetErrorString(e), (long long)c->m_all,
+                c->npix, n_components);
+  HIPCHK(hipStreamSynchronize(c->stream));  // the caller's arrays are read
+  std::swap(c->exp_raw, c->int_out);
+  c->exp_dtype = dtype_out;
+  kpdi::patterns_changed(c);
+  return KPDI_OK;
+}
+
+int kpdi_change_dtype(kpdi_ctx *c, int dtype_out) {
+  int rc = kpdi::check_patterns(c, "a dtype change");
+  if (rc) return rc;
+  if (!kpdi::intensity_dtype(dtype_out))
+    return fail(KPDI_EINVAL, "dtype_out %d: patterns are cast to uint8/int8/uint16/int16/float32/float64", dtype_out);
+  rc = kpdi::start_pattern_op(c);
+  if (rc) return rc;
+  if (dtype_out == c->exp_dtype) return KPDI_OK;
+  const int64_t count = c->m_all * (int64_t)c->npix;
+  HIPCHK(c->int_out.reserve((size_t)count * kpdi::dtype_size(dtype_out)));
+  hipError_t e = kpdi::launch_change_dtype(c->exp_raw.p, c->exp_dtype, c->int_out.p, dtype_out, count, c->stream);
+  if (e != hipSuccess) return fail(KPDI_EHIP, "dtype change kernel: %s (dtype %d -> %d)", hipGetErrorString(e), c->exp_dtype, dtype_out);
+  std::swap(c->exp_raw, c->int_out);
+  c->exp_dtype = dtype_out;
+  kpdi::patterns_changed(c);
+  return KPDI_OK;
 }
 
 size_t kpdi_dtype_size(int dtype) { return kpdi::dtype_size(dtype); }

@@ -219,6 +219,9 @@ struct kpdi_ctx {
   // kpdi_*_intensity: the patterns in a new dtype, kpdi_average_neighbour_patterns: the averaged patterns (swapped with
   // exp_raw); range partials
   kpdi::DevBuf int_out, int_ws;
+  // kpdi_decomposition_*: the Gram matrix or a product, the means (and the partial sums of the mean pattern), and the
+  // caller's basis / loadings / factors
+  kpdi::DevBuf dec_out, dec_mean, dec_in, dec_in2;
 
   // dictionary chunk
   kpdi::DevBuf dict_raw, dict_y;

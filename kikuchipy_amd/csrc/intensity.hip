@@ -458,6 +458,27 @@ hipError_t launch_range_t(const void *src, int64_t count, double *partial, doubl
   return hipGetLastError();
 }
 
+// kpdi_change_dtype: ndarray.astype, value by value (integers widen exactly to float64 first, so an integer-to-integer
+// cast keeps the low bits as NumPy does)
+template <typename T, typename TO>
+__global__ __launch_bounds__(INT_THREADS) void change_dtype_kernel(const T *__restrict__ src, TO *__restrict__ dst,
+                                                                   int64_t count) {
+  using V = typename std::conditional<std::is_floating_point<T>::value, T, double>::type;
+  for (int64_t i = (int64_t)blockIdx.x * INT_THREADS + threadIdx.x; i < count; i += (int64_t)gridDim.x * INT_THREADS)
+    dst[i] = astype_cast<TO>((V)src[i]);
+}
+
+template <typename T>
+hipError_t launch_change_dtype_t(const void *src, void *dst, int dtype_out, int64_t count, hipStream_t s) {
+  const int64_t want = (count + INT_THREADS * 8 - 1) / (INT_THREADS * 8);
+  const unsigned nb = (unsigned)(want < 65536 ? want : 65536);
+  return with_pattern_type(dtype_out, [&](auto o) {
+    using TO = decltype(o);
+    hipLaunchKernelGGL((change_dtype_kernel<T, TO>), dim3(nb), dim3(INT_THREADS), 0, s, (const T *)src, (TO *)dst, count);
+    return hipGetLastError();
+  });
+}
+
 }  // namespace
 
 hipError_t launch_intensity(const IntLaunch &a, hipStream_t s) {
@@ -474,6 +495,11 @@ hipError_t launch_intensity_range(const void *src, int dtype, int64_t count, dou
                                   hipStream_t s) {
   if (count <= 0 || !src || !partial || !out) return hipErrorInvalidValue;
   return with_pattern_type(dtype, [&](auto t) { return launch_range_t<decltype(t)>(src, count, partial, out, s); });
+}
+
+hipError_t launch_change_dtype(const void *src, int dtype, void *dst, int dtype_out, int64_t count, hipStream_t s) {
+  if (count <= 0 || !src || !dst || src == dst) return hipErrorInvalidValue;
+  return with_pattern_type(dtype, [&](auto t) { return launch_change_dtype_t<decltype(t)>(src, dst, dtype_out, count, s); });
 }
 
 }  // namespace kpdi

@@ -8,6 +8,7 @@
 #include "clahe_plan.h"
 #include "neighbours_plan.h"
 #include "downsample_plan.h"
+#include "decomp_plan.h"
 #include "prep_plan.h"
 
 namespace kpdi {
@@ -464,5 +465,30 @@ struct DbLaunch {
 };
 size_t dynamic_background_scratch_bytes(int sy, int sx, int64_t n, int *grid_out);
 hipError_t launch_dynamic_background(const DbLaunch &a, hipStream_t s);
+
+// ---- PCA decomposition (decomp.hip) ------------------------------------------------------
+struct DecLaunch {
+  const void *patterns; int dtype;  // m x k of `dtype` (the six pattern dtypes), device
+  int64_t m, k;
+  int centre;                       // DEC_CENTRE_* of decomp_plan.h
+  double *mean;                     // centre != 0: [m] ("signal") or [k] ("navigation") float64, device
+  double *mean_partial;             // "navigation": dec_mean_chunks(m) * k float64, device (only the means kernel)
+};
+hipError_t launch_decomposition_means(const DecLaunch &a, hipStream_t s);  // fills a.mean
+// gram[side][side], both triangles, from a.mean as filled above
+hipError_t launch_decomposition_gram(const DecLaunch &a, int transposed, double *gram, hipStream_t s);
+// transposed_op 0: out[m][c] = Xc basis[k][c]; 1: out[k][c] = Xc^T basis[m][c]
+hipError_t launch_decomposition_apply(const DecLaunch &a, int transposed_op, const double *basis, int c, double *out,
+                                      hipStream_t s);
+struct DecModelLaunch {
+  const void *loadings, *factors;   // [m][c], [k][c] of `dtype_out`, device
+  int64_t m, k, c;
+  const double *mean; int mean_kind;  // nullptr, or [k] (DEC_CENTRE_NAVIGATION) / [m] (DEC_CENTRE_SIGNAL), device
+  void *dst; int dtype_out;         // [m][k] of KPDI_F32 / KPDI_F64, device
+};
+hipError_t launch_decomposition_model(const DecModelLaunch &a, hipStream_t s);
+
+// ---- plain dtype change (intensity.hip): ndarray.astype of `count` values, src != dst ------
+hipError_t launch_change_dtype(const void *src, int dtype, void *dst, int dtype_out, int64_t count, hipStream_t s);
 
 }  // namespace kpdi

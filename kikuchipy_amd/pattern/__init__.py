@@ -20,3 +20,8 @@ from kikuchipy_amd.pattern._neighbours import (  # noqa: F401
     average_neighbour_patterns_stack,
     neighbour_dot_product_matrices,
 )
+from kikuchipy_amd.pattern._decomposition import (  # noqa: F401
+    LearningResults,
+    decomposition_model_stack,
+    decomposition_stack,
+)

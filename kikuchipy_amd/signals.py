@@ -26,7 +26,7 @@ import numpy as np
 
 from kikuchipy_amd import _lib
 from kikuchipy_amd.indexing._dictionary_indexing import dictionary_indexing as _dictionary_indexing
-from kikuchipy_amd.pattern import _neighbours, _pattern
+from kikuchipy_amd.pattern import _decomposition, _neighbours, _pattern
 from kikuchipy_amd.simulations import DTYPE_RANGE, ProjectedDictionary
 
 
@@ -161,6 +161,7 @@ class EBSD:
         self._devices = devices
         self._ctx = None
         self._groups = {}  # device ids -> _lib.Group, kept from call to call (its communicator is made once)
+        self._learning_results = None  # of the last `decomposition`; not carried over by `deepcopy` / `_like`
         if detector is not None:
             self.detector = detector
 
@@ -474,11 +475,66 @@ class EBSD:
         out.data = data
         out._static_background = static_bg
         out._detector = detector
+        out._learning_results = None  # (they belong to the patterns' old shape)
         if not inplace:
             if hasattr(self, "original_metadata"):
                 out.original_metadata = self.original_metadata
             return out
         return None
+
+    def change_dtype(self, dtype):
+        """HyperSpy's `change_dtype` for the six pattern dtypes, in place: `ndarray.astype(dtype)` of every pattern on the
+        GPU (kpdi_change_dtype: to integers by truncation with NumPy's wrap-around, to float32 by rounding).
+        `static_background` is left alone.  The workflow's `change_dtype("float32")` before a decomposition and
+        `change_dtype(dtype_orig)` after it."""
+        dt = _pattern.intensity_dtype_out(dtype, self.data.dtype)
+        if self.data.dtype.type not in _pattern.INTENSITY_DTYPES:
+            raise ValueError(f"pattern dtype {self.data.dtype} is not supported by the GPU pre-processing kernels")
+        if dt == self.data.dtype:
+            return None
+        self.data = _pattern._process(np.asarray(self.data), lambda c: c.change_dtype(dt), self.context, 0, None)
+        return None
+
+    @property
+    def learning_results(self):
+        """The `kikuchipy_amd.pattern.LearningResults` of the last `decomposition`, None before one."""
+        return self._learning_results
+
+    def decomposition(self, normalize_poissonian_noise=False, algorithm="SVD", output_dimension=None, centre=None,
+                      **kwargs):
+        """HyperSpy's `decomposition` as the reference's multivariate-analysis workflow calls it: principal component
+        analysis of the patterns, `s.decomposition(algorithm="SVD", output_dimension=100, centre="signal")`
+        (`kikuchipy_amd.pattern.decomposition_stack`: a float64 Gram matrix and two products on the GPU, the
+        eigen-solve in NumPy).  `centre`: None, "navigation" (subtract the mean pattern) or "signal" (subtract every
+        pattern's mean intensity).  The results go to `learning_results`; the patterns stay as they are.  Only this form
+        exists here: another `algorithm`, `normalize_poissonian_noise=True`, an `svd_solver` other than "auto" / "full"
+        or any other keyword raises NotImplementedError before any GPU work.  Integer patterns raise TypeError as in
+        HyperSpy: call `change_dtype("float32")` first."""
+        if algorithm != "SVD":
+            raise NotImplementedError(f"algorithm={algorithm!r}: only algorithm='SVD' is implemented")
+        if normalize_poissonian_noise is not False:
+            raise NotImplementedError(f"normalize_poissonian_noise={normalize_poissonian_noise!r}: only False is implemented")
+        _decomposition.check_centre(centre)
+        for name, value in kwargs.items():
+            if name == "svd_solver" and value in ("auto", "full"):
+                continue
+            raise NotImplementedError(f"{name}={value!r} is not implemented by the GPU decomposition")
+        checked = _decomposition.check_decomposition(self.data.shape, self.data.dtype, output_dimension, centre)
+        self._learning_results = _decomposition._decompose(np.asarray(self.data), checked, centre, self.context)
+        return None
+
+    def get_decomposition_model(self, components=None, dtype_out="float32"):
+        """signals/ebsd.py:2665-2723: the model signal rebuilt from `components` of the last decomposition - None: all,
+        an int: the first `components`, a list of ints: those - as `_update_learning_results` picks them
+        (signals/util/_dask.py:283-332): factors and loadings are cast to `dtype_out` (float32 / float64) first, then
+        loadings factors^T plus the mean that centring removed is summed in float64 on the GPU and rounded once
+        (`kikuchipy_amd.pattern.decomposition_model_stack`).  The new signal has this one's custom attributes and no
+        learning results; this signal's stay as they are."""
+        if self._learning_results is None:
+            raise ValueError("No learning results found: run EBSD.decomposition() first")
+        checked = _decomposition.check_model(self.data.shape, self._learning_results, components, dtype_out)
+        out = _decomposition._model(np.asarray(self.data), checked, self._learning_results, dtype_out, self.context)
+        return self._like(out)
 
     def get_image_quality(self, normalize=True, show_progressbar=None, *, devices=None):
         """signals/ebsd.py:1312-1375: Q of every pattern (`kikuchipy_amd.pattern.get_image_quality` with the default
