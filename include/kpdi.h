@@ -351,6 +351,27 @@ int kpdi_decomposition_model(kpdi_ctx *ctx, const void *loadings, const void *fa
                              int mean_kind, int dtype_out);
 int kpdi_change_dtype(kpdi_ctx *ctx, int dtype_out);
 
+/* ---- kinematical master pattern in the stereographic projection (KikuchiPatternSimulator.calculate_master_pattern,
+ * simulations/kikuchi_pattern_simulator.py:162-199, get_pattern :685-700) ---------------------------------------------------
+ * Independent of the resident patterns.  `unit_vectors` (m x 3), `theta` (m Bragg angles, rad) and `intensity` (m) are host
+ * float64; `out` is host float64 of (n_hemispheres, size, size), size = 2 half_size + 1, the upper hemisphere first for
+ * KPDI_HEMISPHERE_BOTH.  Pixel (row, col) looks along the inverse stereographic projection of x = arr[col], y = arr[row],
+ * arr = np.linspace(-1, 1, size): (2x, 2y, 1 - x^2 - y^2) / (1 + x^2 + y^2), z negated on the lower hemisphere; the
+ * directions are formed on the host with NumPy's operations one by one (csrc/kinematical_plan.h) and equal them bit for
+ * bit.  For every pixel the reflectors are visited in rising index, in float64 without contraction:
+ *   D = ((u0 v0) + u1 v1) + u2 v2;  |D| <= 1e-7 adds 0.5 intensity;  otherwise intensity is added when
+ *   pi/2 - theta <= acos(D) <= pi/2  (one-sided: D < 0 adds nothing; D > 1 by rounding adds nothing).
+ * acos is evaluated only for pairs within 1e-6 in D of the band edge, every other pair falls on the same side whatever the
+ * last bits of acos are: a pixel differs from the reference's plain-Python evaluation only where some reflector's acos(D)
+ * lies within the last bits of pi/2 - theta.  One thread per pixel, both hemispheres in one launch, no atomics, one
+ * summation order: results do not depend on the launch or the reflector chunk, bit for bit (csrc/kinematical.hip).
+ * KPDI_EINVAL before anything runs: NULL, m < 1, half_size < 0 or above 4096, an unknown hemisphere code. */
+#define KPDI_HEMISPHERE_UPPER 0
+#define KPDI_HEMISPHERE_LOWER 1
+#define KPDI_HEMISPHERE_BOTH 2
+int kpdi_kinematical_master_pattern(kpdi_ctx *ctx, const double *unit_vectors, const double *theta, const double *intensity,
+                                    int64_t m, int half_size, int hemispheres, double *out);
+
 /* ---- dictionary sweep (_dictionary_indexing loop, indexing/_dictionary_indexing.py:94-128)
  * One call = one loop iteration: prepare_dictionary (cast, mask, normalise) +
  * match + top-k of the chunk + merge into the running best-k, all on the GPU.
@@ -797,6 +818,7 @@ typedef struct kpdi_counters {
   int64_t epi_appended;
   int64_t epi_overflows;
   int64_t epi_direct_first;
+  double kinematical_ms;         /* the kernel of the last kpdi_kinematical_master_pattern, between two events (profiling on) */
 } kpdi_counters;
 /* sizeof(kpdi_counters) as the LIBRARY was built: a binding whose struct differs must refuse to call kpdi_get_counters
  * (the struct has grown between versions; kpdi_version() changes with it) */

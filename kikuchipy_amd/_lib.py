@@ -25,6 +25,8 @@ OP_SUBTRACT, OP_DIVIDE = 0, 1
 DOMAIN_FREQUENCY, DOMAIN_SPATIAL = 0, 1
 CENTRE_NONE, CENTRE_NAVIGATION, CENTRE_SIGNAL = 0, 1, 2  # kpdi_decomposition_*: what centring subtracts
 DECOMPOSITION_MAX_SIDE = 8192  # csrc/decomp_plan.h, DEC_MAX_SIDE
+HEMISPHERE_CODES = {"upper": 0, "lower": 1, "both": 2}  # kpdi_kinematical_master_pattern
+KINEMATICAL_MAX_HALF_SIZE = 4096  # csrc/kinematical_plan.h, KIN_MAX_HALF_SIZE
 UNIQUE_ID_BYTES = 128
 REFINE_ORI, REFINE_PC, REFINE_ORI_PC = 0, 1, 2
 REFINE_SIZES = {REFINE_ORI: (3, 3), REFINE_PC: (3, 4), REFINE_ORI_PC: (6, 0)}  # (control variables, fixed values)
@@ -82,6 +84,7 @@ class Counters(C.Structure):
         ("epi_appended", C.c_int64),
         ("epi_overflows", C.c_int64),
         ("epi_direct_first", C.c_int64),
+        ("kinematical_ms", C.c_double),
     ]
 
     def as_dict(self):
@@ -146,6 +149,7 @@ SIGNATURES = {
     "kpdi_decomposition_apply": (_i, [_vp, _i, _i, _vp, _i, _vp]),
     "kpdi_decomposition_model": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i]),
     "kpdi_change_dtype": (_i, [_vp, _i]),
+    "kpdi_kinematical_master_pattern": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
     "kpdi_average_neighbour_patterns": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i]),
     "kpdi_neighbour_dot_products": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "kpdi_push_dictionary_chunk": (_i, [_vp, _vp, _i, _i64, _i64]),
@@ -585,6 +589,26 @@ class Context:
         check(self._f.decomposition_model(self._h, _ptr(lo), _ptr(fa), int(lo.shape[1]), _ptr(mu), int(mean_kind),
                                           dtype_code(dt)))
         self._exp_dtype = dt
+
+    def kinematical_master_pattern(self, unit_vectors, theta, intensity, half_size, hemisphere):
+        """The kinematical master pattern in the stereographic projection from m reflectors (unit normals (m, 3), Bragg
+        angles, intensities; float64): (size, size) float64, or (2, size, size) for hemisphere "both", size =
+        2 half_size + 1 (include/kpdi.h, kpdi_kinematical_master_pattern).  Independent of the resident patterns."""
+        u = np.ascontiguousarray(unit_vectors, dtype=np.float64)
+        th = np.ascontiguousarray(theta, dtype=np.float64).ravel()
+        inten = np.ascontiguousarray(intensity, dtype=np.float64).ravel()
+        if u.ndim != 2 or u.shape[1] != 3 or th.size != u.shape[0] or inten.size != u.shape[0]:
+            raise KpdiError(f"unit vectors {u.shape}, {th.size} Bragg angles and {inten.size} intensities: (m, 3), m and "
+                            "m expected")
+        code = HEMISPHERE_CODES[hemisphere]
+        half_size = int(half_size)
+        size = 2 * max(half_size, 0) + 1
+        if half_size > KINEMATICAL_MAX_HALF_SIZE:  # (the library's refusal, before the output is asked for)
+            size = 1
+        out = np.empty((2, size, size) if code == 2 else (size, size), dtype=np.float64)
+        check(self._f.kinematical_master_pattern(self._h, _ptr(u), _ptr(th), _ptr(inten), u.shape[0], half_size, code,
+                                                 _ptr(out)))
+        return out
 
     def normalize_intensity(self, num_std=1, divide_by_square_root=False, dtype_out=None):
         """(p - mean) / (num_std * std [* sqrt(size)]) of every resident pattern into `dtype_out` (None: the patterns'
@@ -1424,6 +1448,9 @@ class Group(Context):
 
     def orientation_similarity_map(self, *args, **kwargs):
         return self.root.orientation_similarity_map(*args, **kwargs)
+
+    def kinematical_master_pattern(self, *args, **kwargs):
+        return self.root.kinematical_master_pattern(*args, **kwargs)
 
     def holds_result(self, simulation_indices):
         self.root._last_valid = self._last_valid

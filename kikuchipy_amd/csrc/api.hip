@@ -287,7 +287,7 @@ static int upload_taps(kpdi_ctx *c, const std::vector<double> &taps) {
 
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.10.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.11.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 
@@ -1204,6 +1204,71 @@ int kpdi_change_dtype(kpdi_ctx *c, int dtype_out) {
   c->exp_dtype = dtype_out;
   kpdi::patterns_changed(c);
   return KPDI_OK;
+}
+
+int kpdi_kinematical_master_pattern(kpdi_ctx *c, const double *unit_vectors, const double *theta, const double *intensity,
+                                    int64_t m, int half_size, int hemispheres, double *out) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!unit_vectors || !theta || !intensity || !out) return fail(KPDI_EINVAL, "unit_vectors, theta, intensity or out is NULL");
+  if (m < 1 || m > INT_MAX) return fail(KPDI_EINVAL, "%lld reflectors: at least one is needed", (long long)m);
+  if (half_size < 0 || half_size > kpdi::KIN_MAX_HALF_SIZE)
+    return fail(KPDI_EINVAL, "half_size %d: between 0 and %d", half_size, kpdi::KIN_MAX_HALF_SIZE);
+  if (!kpdi::kin_hemispheres(hemispheres))
+    return fail(KPDI_EINVAL, "hemispheres %d: 0 (upper), 1 (lower) or 2 (both)", hemispheres);
+  const kpdi::KinPlan plan = kpdi::kinematical_launch_plan(m, half_size, hemispheres);
+  if (!plan.ok) return fail(KPDI_EINVAL, "kinematical master pattern of half_size %d from %lld reflectors: no kernel takes this shape",
+                            half_size, (long long)m);
+  int rc = use_device(c);
+  if (rc) return rc;
+  // the pixel directions of the upper hemisphere and the reflector table, on the host with NumPy's operations
+  const int size = plan.size;
+  std::vector<double> axis((size_t)size), dirs((size_t)plan.pixels * 3), table((size_t)m * kpdi::KIN_ENTRY_DOUBLES);
+  for (int i = 0; i < size; ++i) axis[(size_t)i] = kpdi::kin_axis(i, size);
+  for (int r = 0; r < size; ++r)
+    for (int col = 0; col < size; ++col) kpdi::kin_direction(axis[(size_t)col], axis[(size_t)r], &dirs[((size_t)r * size + col) * 3]);
+  const double half_pi = 1.5707963267948966;  // np.pi / 2
+  for (int64_t i = 0; i < m; ++i) {
+    double *e = &table[(size_t)i * kpdi::KIN_ENTRY_DOUBLES];
+    e[0] = unit_vectors[3 * i];
+    e[1] = unit_vectors[3 * i + 1];
+    e[2] = unit_vectors[3 * i + 2];
+    e[3] = intensity[i];
+    e[6] = half_pi - theta[i];
+    kpdi::kin_screen(e[6], &e[4], &e[5]);
+    e[7] = 0.0;
+  }
+  const size_t out_bytes = (size_t)plan.hemispheres * (size_t)plan.pixels * sizeof(double);
+  HIPCHK(c->kin_dirs.reserve(dirs.size() * sizeof(double)));
+  HIPCHK(c->kin_table.reserve(table.size() * sizeof(double)));
+  HIPCHK(c->kin_out.reserve(out_bytes));
+  HIPCHK(hipMemcpyAsync(c->kin_dirs.p, dirs.data(), dirs.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->kin_table.p, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  kpdi::KinLaunch l{};
+  l.dirs = c->kin_dirs.as<double>();
+  l.table = c->kin_table.as<double>();
+  l.m = m;
+  l.half_size = half_size;
+  l.hemispheres = hemispheres;
+  l.out = c->kin_out.as<double>();
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  if (c->profiling) {
+    HIPCHK(hipEventCreate(&ev0));
+    HIPCHK(hipEventCreate(&ev1));
+    HIPCHK(hipEventRecord(ev0, c->stream));
+  }
+  hipError_t e = kpdi::launch_kinematical_master_pattern(l, c->stream);
+  if (ev1) (void)hipEventRecord(ev1, c->stream);
+  if (e == hipSuccess) rc = kpdi::results_to_host(c, out, c->kin_out.p, out_bytes);  // (synchronises: the host tables are read)
+  if (ev1) {
+    float ms = 0.f;
+    if (e == hipSuccess && rc == KPDI_OK && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) c->cnt.kinematical_ms = ms;
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+  }
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "kinematical master pattern kernel: %s (half_size %d, %lld reflectors)", hipGetErrorString(e), half_size,
+                (long long)m);
+  return rc;
 }
 
 size_t kpdi_dtype_size(int dtype) { return kpdi::dtype_size(dtype); }

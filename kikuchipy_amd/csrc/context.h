@@ -222,6 +222,8 @@ struct kpdi_ctx {
   // kpdi_decomposition_*: the Gram matrix or a product, the means (and the partial sums of the mean pattern), and the
   // caller's basis / loadings / factors
   kpdi::DevBuf dec_out, dec_mean, dec_in, dec_in2;
+  // kpdi_kinematical_master_pattern: pixel directions, reflector table, the pattern
+  kpdi::DevBuf kin_dirs, kin_table, kin_out;
 
   // dictionary chunk
   kpdi::DevBuf dict_raw, dict_y;

@@ -9,6 +9,7 @@
 #include "neighbours_plan.h"
 #include "downsample_plan.h"
 #include "decomp_plan.h"
+#include "kinematical_plan.h"
 #include "prep_plan.h"
 
 namespace kpdi {
@@ -490,5 +491,16 @@ hipError_t launch_decomposition_model(const DecModelLaunch &a, hipStream_t s);
 
 // ---- plain dtype change (intensity.hip): ndarray.astype of `count` values, src != dst ------
 hipError_t launch_change_dtype(const void *src, int dtype, void *dst, int dtype_out, int64_t count, hipStream_t s);
+
+// ---- kinematical master pattern (kinematical.hip) ----------------------------------------
+struct KinLaunch {
+  const double *dirs;    // [pixels][3]: the upper hemisphere's directions (kin_direction of kinematical_plan.h), device
+  const double *table;   // [m][KIN_ENTRY_DOUBLES]: ux uy uz I | lo hi theta1 0, device
+  int64_t m;
+  int half_size, hemispheres;  // KIN_UPPER / KIN_LOWER / KIN_BOTH
+  double *out;           // [kin_hemispheres][size][size], device
+};
+KinPlan kinematical_launch_plan(int64_t m, int half_size, int hemispheres);  // reads the developer switch
+hipError_t launch_kinematical_master_pattern(const KinLaunch &l, hipStream_t s);
 
 }  // namespace kpdi

@@ -20,6 +20,7 @@ that `kpdi_push_dictionary_chunk` then matches), as `bench.py --workload
 config3` does.
 """
 
+import copy
 import warnings
 
 import numpy as np
@@ -741,6 +742,26 @@ def _rotations_of(xmap):
     return np.asarray(getattr(rot, "data", rot), dtype=np.float64)
 
 
+def _lambert2vector(x, y):
+    """Square Lambert (X, Y) to vectors (n, 3), `_lambert2vector` of signals/util/_master_pattern.py:717-760 with the
+    same operations on whole arrays (not normalised, as there)."""
+    xi = x * np.sqrt(np.pi / 2)
+    yi = y * np.sqrt(np.pi / 2)
+    cart = np.zeros((x.size, 3), dtype=np.float64)
+    with np.errstate(all="ignore"):
+        qy = 2 * yi * np.sqrt(np.pi - yi**2) / np.pi
+        qqy = xi * np.pi * 0.25 / yi
+        qx = 2 * xi * np.sqrt(np.pi - xi**2) / np.pi
+        qqx = yi * np.pi * 0.25 / xi
+        by_y = np.stack([qy * np.sin(qqy), qy * np.cos(qqy), 1 - 2 * yi**2 / np.pi], axis=1)
+        by_x = np.stack([qx * np.cos(qqx), qx * np.sin(qqx), 1 - 2 * xi**2 / np.pi], axis=1)
+    use_y = np.abs(xi) <= np.abs(yi)
+    cart[use_y] = by_y[use_y]
+    cart[~use_y] = by_x[~use_y]
+    cart[np.maximum(np.abs(xi), np.abs(yi)) == 0] = [0, 0, 1]
+    return cart
+
+
 class EBSDMasterPattern:
     """Master pattern in the square Lambert projection: the surface of
     `kikuchipy.signals.EBSDMasterPattern` that `get_patterns` reads.
@@ -812,6 +833,42 @@ class EBSDMasterPattern:
         if error is not None and raise_if_not:
             raise error
         return error is None
+
+    def deepcopy(self):
+        """A copy that shares nothing with this master pattern."""
+        return copy.deepcopy(self)
+
+    # signals/_kikuchi_master_pattern.py:135-213
+    def as_lambert(self, show_progressbar=None):
+        """Return a new master pattern in the Lambert projection: the same data shape in float32, every navigation
+        slice (hemisphere, energy) interpolated from the stereographic one with the reference's steps (the Lambert grid,
+        its unit vectors, their stereographic coordinates, `scipy.interpolate.interpn(method="splinef2d")`).  Runs on the
+        host, once per master pattern; `show_progressbar` is accepted for the reference's signature."""
+        if self.projection == "lambert":
+            warnings.warn("Already in the Lambert projection, returning a deepcopy", UserWarning)
+            return self.deepcopy()
+        try:
+            from scipy.interpolate import interpn
+        except ImportError as e:  # pragma: no cover
+            raise ImportError("EBSDMasterPattern.as_lambert needs SciPy (scipy.interpolate.interpn fits the spline)") from e
+
+        sig_shape = self.data.shape[-2:]
+        arr = np.linspace(-1, 1, sig_shape[0], dtype=np.float64)
+        x_lambert, y_lambert = np.meshgrid(arr, arr)
+        xyz_upper = _lambert2vector(x_lambert.ravel(), y_lambert.ravel())
+        # orix' StereographicProjection().vector2xy (pole -1): (x, y) / (1 + z)
+        x_stereo = xyz_upper[:, 0] / (1 + xyz_upper[:, 2])
+        y_stereo = xyz_upper[:, 1] / (1 + xyz_upper[:, 2])
+        x_stereo += 1
+        y_stereo += 1
+        kwargs = {"points": (arr + 1, arr + 1), "xi": (y_stereo, x_stereo), "method": "splinef2d"}
+        data_out = np.zeros(self.data.shape, dtype=np.float32)
+        for idx in np.ndindex(self.data.shape[:-2]):
+            data_i = interpn(values=self.data[idx], **kwargs)
+            data_out[idx] = data_i.reshape(sig_shape)
+        return self.__class__(data_out, projection="lambert", hemisphere=copy.deepcopy(self.hemisphere),
+                              energies=None if self.energies is None else self.energies.copy(), phase_name=self.phase_name,
+                              has_inversion_symmetry=self.has_inversion_symmetry, device=self._device)
 
     # signals/_kikuchi_master_pattern.py:303-345
     def _get_master_pattern_arrays_from_energy(self, energy=None):

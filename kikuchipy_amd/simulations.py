@@ -9,7 +9,17 @@ engine generate every dictionary chunk directly in device memory
 (`kpdi_push_rotations_chunk`), so the dictionary never crosses PCIe and is
 never materialised on the host; `.compute()` materialises it (also on the
 GPU) for any other use.
+
+`KikuchiPatternSimulator.calculate_master_pattern`
+(simulations/kikuchi_pattern_simulator.py:122-215 of the reference) makes a
+dictionary source without EMsoft: the kinematical master pattern of a list of
+reflectors in the stereographic projection, summed on the GPU
+(csrc/kinematical.hip), which `EBSDMasterPattern.as_lambert` turns into the
+projection that `get_patterns` reads.  `Reflectors` is the plain holder of the
+reflector list (diffsims is not a dependency).
 """
+
+import copy
 
 import numpy as np
 
@@ -157,3 +167,158 @@ class ProjectedDictionary:
     def __repr__(self):
         return (f"ProjectedDictionary(shape={self.shape}, dtype={self.dtype}, rescale={self.rescale}, "
                 f"chunksize={self.chunksize})")
+
+
+class Reflectors:
+    """A list of reflectors for `KikuchiPatternSimulator`: what the simulator reads of diffsims'
+    `ReciprocalLatticeVector`, as plain arrays.
+
+    Parameters
+    ----------
+    hkl
+        (m, 3) Miller indices.
+    theta
+        m Bragg angles in radians, or None (not calculated: NaN, as in diffsims).
+    structure_factor
+        m (complex) structure factors, or None (not calculated: NaN).
+    reciprocal_basis
+        (3, 3) rows a*, b*, c* in Cartesian coordinates; the reflectors' Cartesian vectors are `hkl @ reciprocal_basis`.
+        None is the identity: a cubic lattice (the unit vectors do not depend on its parameter).
+    phase_name, has_inversion_symmetry
+        What the master pattern takes over from the phase (`EBSDMasterPattern`).
+    """
+
+    def __init__(self, hkl, theta, structure_factor=None, reciprocal_basis=None, phase_name="", has_inversion_symmetry=True):
+        self.hkl = np.atleast_2d(np.asarray(hkl, dtype=np.float64))
+        if self.hkl.ndim != 2 or self.hkl.shape[1] != 3:
+            raise ValueError(f"hkl of shape {np.shape(hkl)}: (m, 3) expected")
+        m = self.hkl.shape[0]
+        self.theta = np.full(m, np.nan) if theta is None else np.asarray(theta, dtype=np.float64).reshape(-1)
+        if structure_factor is None:
+            self.structure_factor = np.full(m, np.nan, dtype=np.complex128)
+        else:
+            self.structure_factor = np.asarray(structure_factor).reshape(-1)
+        if self.theta.size != m or self.structure_factor.size != m:
+            raise ValueError(f"{m} reflectors but {self.theta.size} Bragg angles and {self.structure_factor.size} "
+                             "structure factors")
+        basis = np.eye(3) if reciprocal_basis is None else np.asarray(reciprocal_basis, dtype=np.float64)
+        if basis.shape != (3, 3):
+            raise ValueError(f"reciprocal_basis of shape {basis.shape}: (3, 3) expected")
+        self.reciprocal_basis = basis
+        self.phase_name = phase_name
+        self.has_inversion_symmetry = has_inversion_symmetry
+
+    @property
+    def size(self):
+        return self.hkl.shape[0]
+
+    @property
+    def data(self):
+        """Cartesian coordinates of the reciprocal lattice vectors."""
+        return self.hkl @ self.reciprocal_basis
+
+    @property
+    def unit_vectors(self):
+        """`Vector3d(reflectors).unit.data`: the Cartesian vectors divided by sqrt(sum of squares)."""
+        data = self.data
+        return data / np.sqrt(np.sum(data**2, axis=-1))[:, np.newaxis]
+
+    def deepcopy(self):
+        return copy.deepcopy(self)
+
+    def flatten(self):
+        return self
+
+    def __repr__(self):
+        return (f"Reflectors ({self.size},), {self.phase_name or 'unnamed phase'}\n"
+                f"[{', '.join(str(row) for row in self.hkl[:4].astype(int).tolist())}{', ...' if self.size > 4 else ''}]")
+
+
+def _unit_vectors_of(reflectors):
+    """(m, 3) float64 unit normals of a `Reflectors` or of anything shaped like diffsims' `ReciprocalLatticeVector`
+    (`unit` being a vector object with `data`)."""
+    u = getattr(reflectors, "unit_vectors", None)
+    if u is None:
+        u = reflectors.unit
+        u = getattr(u, "data", u)
+    return np.ascontiguousarray(u, dtype=np.float64).reshape(-1, 3)
+
+
+def _phase_of(reflectors):
+    """(phase name, has_inversion_symmetry) of a `Reflectors`, or from the `phase` of a diffsims object."""
+    if hasattr(reflectors, "phase_name"):
+        return reflectors.phase_name, getattr(reflectors, "has_inversion_symmetry", True)
+    phase = getattr(reflectors, "phase", None)
+    point_group = getattr(phase, "point_group", None)
+    return getattr(phase, "name", "") or "", None if point_group is None else bool(point_group.contains_inversion)
+
+
+class KikuchiPatternSimulator:
+    """Setup and calculation of kinematical Kikuchi pattern simulations.
+
+    Parameters
+    ----------
+    reflectors
+        Reflectors to use in the simulation, flattened to one navigation dimension: a `Reflectors`, or any object with
+        `hkl`, `theta`, `structure_factor` and unit vectors (diffsims' `ReciprocalLatticeVector`).
+    """
+
+    def __init__(self, reflectors):
+        self._reflectors = reflectors.deepcopy().flatten()
+
+    @property
+    def reflectors(self):
+        """Return the reflectors to use in the simulation."""
+        return self._reflectors
+
+    def __repr__(self):
+        return f"{self.__class__.__name__}:\n" + repr(self.reflectors)
+
+    def calculate_master_pattern(self, half_size=500, hemisphere="upper", scaling="linear", *, device=0, context=None):
+        """Return a kinematical master pattern in the stereographic projection, summed on the GPU.
+
+        `half_size`: the pattern has 2 * half_size + 1 pixels per side; `hemisphere`: "upper", "lower" or "both";
+        `scaling` of the band intensities: "linear" |F|, "square" |F|^2, or None (all bands 1).  Returns an
+        `EBSDMasterPattern` of float64 data, (size, size) or (2, size, size) for "both", `projection="stereographic"`;
+        `as_lambert()` makes it ready for `get_patterns`.  `device` / `context`: the GPU, or a `Context` to run on."""
+        self._raise_if_no_theta()
+        self._raise_if_no_structure_factor()
+        if not isinstance(hemisphere, str) or hemisphere.lower() not in _lib.HEMISPHERE_CODES:
+            raise ValueError(f"Unknown hemisphere {hemisphere!r}, options are 'upper', 'lower', or 'both'")
+        hemisphere = hemisphere.lower()
+        ref = self.reflectors
+        if scaling == "linear":
+            intensity = abs(np.asarray(ref.structure_factor))
+        elif scaling == "square":
+            factor = np.asarray(ref.structure_factor)
+            intensity = abs(factor * factor.conjugate())
+        elif scaling is None:
+            intensity = np.ones(ref.size)
+        else:
+            raise ValueError(f"Unknown scaling {scaling!r}, options are 'linear', 'square', or None")
+        from kikuchipy_amd.signals import EBSDMasterPattern
+
+        ctx = context if context is not None else _lib.Context(device)
+        try:
+            data = ctx.kinematical_master_pattern(_unit_vectors_of(ref), ref.theta, intensity, half_size, hemisphere)
+        finally:
+            if context is None:
+                ctx.close()
+        phase_name, inversion = _phase_of(ref)
+        return EBSDMasterPattern(data, projection="stereographic", hemisphere=hemisphere, phase_name=phase_name,
+                                 has_inversion_symmetry=inversion, device=device)
+
+    def _raise_if_no_theta(self):
+        if np.isnan(self.reflectors.theta[0]):
+            raise ValueError(
+                "Reflectors have no Bragg angles. Calculate with "
+                "`diffsims.crystallography.ReciprocalLatticeVector.calculate_theta()`."
+            )
+
+    def _raise_if_no_structure_factor(self):
+        if np.isnan(self.reflectors.structure_factor[0]):
+            raise ValueError(
+                "Reflectors have no structure factors. Calculate with "
+                "`diffsims.crystallography.ReciprocalLatticeVector."
+                "calculate_structure_factor()`."
+            )
