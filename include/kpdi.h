@@ -372,6 +372,39 @@ int kpdi_change_dtype(kpdi_ctx *ctx, int dtype_out);
 int kpdi_kinematical_master_pattern(kpdi_ctx *ctx, const double *unit_vectors, const double *theta, const double *intensity,
                                     int64_t m, int half_size, int hemispheres, double *out);
 
+/* ---- geometrical simulations: Kikuchi lines and zone axes on the detector (KikuchiPatternSimulator.on_detector,
+ * simulations/kikuchi_pattern_simulator.py:217-380; _kikuchi_pattern_features.py; _kikuchi_pattern_simulation.py:468-534) -----
+ * Independent of the resident patterns.  All arrays are host memory, float64 unless said otherwise, row vectors.
+ * `rotations` (n_points x 4) are unit quaternions; U_o is the matrix of rotate_vector (orix's Rotation.to_matrix()).
+ * `u_s` (3 x 3) is detector.sample_to_detector transposed; `a_star` (3 x 3) has rows a*, b*, c*, `a_direct` rows a, b, c.
+ * Per point U_os = U_o u_s, hkl_d = hkl (a_star U_os), uvw_d = uvw (a_direct U_os), formed once per point.
+ * `pcs` (n_pc x 8, n_pc 1 or n_points) holds per projection centre: the gnomonic x_min, x_max, y_min, y_max each widened by
+ * one pixel, pcx / pcz * aspect_ratio, pcy / pcz, x_scale, y_scale.
+ *
+ * kpdi_geometrical_visibility: `kind` KPDI_GEOMETRICAL_LINES takes `vectors` (m x 3) as hkl and `basis` as a_star,
+ * KPDI_GEOMETRICAL_ZONE_AXES as uvw and a_direct.  flags[i] (uint8, m) gets bit 0 when z > 0 at one point at least, and for
+ * zone axes bit 1 when x / z and y / z lie inside the widened bounds of one point at least (any sign of z; comparisons with
+ * NaN or inf are false).
+ *
+ * kpdi_geometrical_coordinates: for n_points x m lines and n_points x z zone axes (z may be 0, its four pointers then
+ * unused): in_pattern (uint8) = z > 0; lines: the plane trace R (cos a1, sin a1, cos a2, sin a2) in gnomonic coordinates
+ * (n_points x m x 4), NaN unless |h| < R and z > -1e-5 with h = z / sqrt(x^2 + y^2), R = r_gnomonic, and in pixels
+ * ((g + xoff) / x_scale, (-g + yoff) / y_scale); zone axes: (x / z, y / z) (n_points x z x 2), NaN unless
+ * sqrt((x/z)^2 + (y/z)^2) < R and z > -1e-5, and in pixels, NaN also outside the point's widened bounds.  The map is
+ * walked in passes sized from free device memory; results do not depend on the pass or chunk length
+ * (csrc/geometrical.hip, csrc/geometrical_plan.h).
+ * KPDI_EINVAL before anything runs: NULL, m < 1, z < 0, n_points < 1, n_pc neither 1 nor n_points, an unknown kind. */
+#define KPDI_GEOMETRICAL_LINES 0
+#define KPDI_GEOMETRICAL_ZONE_AXES 1
+int kpdi_geometrical_visibility(kpdi_ctx *ctx, const double *vectors, int64_t m, int kind, const double *rotations,
+                                int64_t n_points, const double *u_s, const double *basis, const double *pcs, int64_t n_pc,
+                                uint8_t *flags);
+int kpdi_geometrical_coordinates(kpdi_ctx *ctx, const double *hkl, int64_t m, const double *uvw, int64_t z,
+                                 const double *rotations, int64_t n_points, const double *u_s, const double *a_star,
+                                 const double *a_direct, const double *pcs, int64_t n_pc, double r_gnomonic,
+                                 uint8_t *line_in_pattern, double *line_gnomonic, double *line_pixel,
+                                 uint8_t *zone_in_pattern, double *zone_gnomonic, double *zone_pixel);
+
 /* ---- dictionary sweep (_dictionary_indexing loop, indexing/_dictionary_indexing.py:94-128)
  * One call = one loop iteration: prepare_dictionary (cast, mask, normalise) +
  * match + top-k of the chunk + merge into the running best-k, all on the GPU.
@@ -819,6 +852,8 @@ typedef struct kpdi_counters {
   int64_t epi_overflows;
   int64_t epi_direct_first;
   double kinematical_ms;         /* the kernel of the last kpdi_kinematical_master_pattern, between two events (profiling on) */
+  double geometrical_visibility_ms;   /* the kernels of the last kpdi_geometrical_visibility (profiling on) */
+  double geometrical_coordinates_ms;  /* the kernels of the last kpdi_geometrical_coordinates, summed over its passes (profiling on) */
 } kpdi_counters;
 /* sizeof(kpdi_counters) as the LIBRARY was built: a binding whose struct differs must refuse to call kpdi_get_counters
  * (the struct has grown between versions; kpdi_version() changes with it) */

@@ -27,6 +27,9 @@ CENTRE_NONE, CENTRE_NAVIGATION, CENTRE_SIGNAL = 0, 1, 2  # kpdi_decomposition_*:
 DECOMPOSITION_MAX_SIDE = 8192  # csrc/decomp_plan.h, DEC_MAX_SIDE
 HEMISPHERE_CODES = {"upper": 0, "lower": 1, "both": 2}  # kpdi_kinematical_master_pattern
 KINEMATICAL_MAX_HALF_SIZE = 4096  # csrc/kinematical_plan.h, KIN_MAX_HALF_SIZE
+GEOMETRICAL_LINES, GEOMETRICAL_ZONE_AXES = 0, 1  # kpdi_geometrical_visibility
+GEOMETRICAL_UPPER, GEOMETRICAL_INSIDE = 1, 2     # bits of its flags
+GEOMETRICAL_PC_DOUBLES = 8  # csrc/geometrical_plan.h, GEO_PC_DOUBLES
 UNIQUE_ID_BYTES = 128
 REFINE_ORI, REFINE_PC, REFINE_ORI_PC = 0, 1, 2
 REFINE_SIZES = {REFINE_ORI: (3, 3), REFINE_PC: (3, 4), REFINE_ORI_PC: (6, 0)}  # (control variables, fixed values)
@@ -85,6 +88,8 @@ class Counters(C.Structure):
         ("epi_overflows", C.c_int64),
         ("epi_direct_first", C.c_int64),
         ("kinematical_ms", C.c_double),
+        ("geometrical_visibility_ms", C.c_double),
+        ("geometrical_coordinates_ms", C.c_double),
     ]
 
     def as_dict(self):
@@ -150,6 +155,9 @@ SIGNATURES = {
     "kpdi_decomposition_model": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i]),
     "kpdi_change_dtype": (_i, [_vp, _i]),
     "kpdi_kinematical_master_pattern": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
+    "kpdi_geometrical_visibility": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "kpdi_geometrical_coordinates": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.c_double,
+                                          _vp, _vp, _vp, _vp, _vp, _vp]),
     "kpdi_average_neighbour_patterns": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _i]),
     "kpdi_neighbour_dot_products": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "kpdi_push_dictionary_chunk": (_i, [_vp, _vp, _i, _i64, _i64]),
@@ -608,6 +616,54 @@ class Context:
         out = np.empty((2, size, size) if code == 2 else (size, size), dtype=np.float64)
         check(self._f.kinematical_master_pattern(self._h, _ptr(u), _ptr(th), _ptr(inten), u.shape[0], half_size, code,
                                                  _ptr(out)))
+        return out
+
+    @staticmethod
+    def _geometrical_inputs(rotations, u_s, pcs, *bases):
+        rot = np.ascontiguousarray(rotations, dtype=np.float64)
+        pc = np.ascontiguousarray(pcs, dtype=np.float64)
+        mats = [np.ascontiguousarray(a, dtype=np.float64) for a in (u_s,) + bases]
+        if rot.ndim != 2 or rot.shape[1] != 4 or pc.ndim != 2 or pc.shape[1] != GEOMETRICAL_PC_DOUBLES:
+            raise KpdiError(f"rotations {rot.shape} and projection centre table {pc.shape}: (n, 4) and (1 or n, "
+                            f"{GEOMETRICAL_PC_DOUBLES}) expected")
+        if any(a.shape != (3, 3) for a in mats):
+            raise KpdiError(f"matrices of shapes {[a.shape for a in mats]}: (3, 3) expected")
+        return rot, pc, mats
+
+    def geometrical_visibility(self, vectors, kind, rotations, u_s, basis, pcs):
+        """Which of m features are in some pattern of a map (include/kpdi.h, kpdi_geometrical_visibility): `vectors`
+        (m, 3) hkl with `basis` rows a*, b*, c* (`kind` GEOMETRICAL_LINES) or uvw with rows a, b, c
+        (GEOMETRICAL_ZONE_AXES); `rotations` (n, 4); `u_s` the sample-to-detector matrix transposed; `pcs` (1 or n, 8).
+        Returns m uint8 flags: GEOMETRICAL_UPPER | GEOMETRICAL_INSIDE."""
+        v = np.ascontiguousarray(vectors, dtype=np.float64)
+        if v.ndim != 2 or v.shape[1] != 3:
+            raise KpdiError(f"vectors {v.shape}: (m, 3) expected")
+        rot, pc, (us, b) = self._geometrical_inputs(rotations, u_s, pcs, basis)
+        flags = np.zeros(v.shape[0], dtype=np.uint8)
+        check(self._f.geometrical_visibility(self._h, _ptr(v), v.shape[0], int(kind), _ptr(rot), rot.shape[0], _ptr(us),
+                                             _ptr(b), _ptr(pc), pc.shape[0], _ptr(flags)))
+        return flags
+
+    def geometrical_coordinates(self, hkl, uvw, rotations, u_s, a_star, a_direct, pcs, r_gnomonic):
+        """Lines and zone axes of every map point on the detector (include/kpdi.h, kpdi_geometrical_coordinates): a dict
+        of `line_in_pattern` (n, m) bool, `line_gnomonic` and `line_pixel` (n, m, 4), `zone_in_pattern` (n, z) bool,
+        `zone_gnomonic` and `zone_pixel` (n, z, 2); float64, NaN where the reference has NaN."""
+        h = np.ascontiguousarray(hkl, dtype=np.float64)
+        w = np.ascontiguousarray(uvw, dtype=np.float64).reshape(-1, 3)
+        if h.ndim != 2 or h.shape[1] != 3:
+            raise KpdiError(f"hkl {h.shape}: (m, 3) expected")
+        rot, pc, (us, a_s, a_d) = self._geometrical_inputs(rotations, u_s, pcs, a_star, a_direct)
+        n, m, z = rot.shape[0], h.shape[0], w.shape[0]
+        out = {"line_in_pattern": np.zeros((n, m), dtype=np.uint8), "line_gnomonic": np.empty((n, m, 4)),
+               "line_pixel": np.empty((n, m, 4)), "zone_in_pattern": np.zeros((n, z), dtype=np.uint8),
+               "zone_gnomonic": np.empty((n, z, 2)), "zone_pixel": np.empty((n, z, 2))}
+        check(self._f.geometrical_coordinates(self._h, _ptr(h), m, _ptr(w) if z else None, z, _ptr(rot), n, _ptr(us),
+                                              _ptr(a_s), _ptr(a_d), _ptr(pc), pc.shape[0], float(r_gnomonic),
+                                              _ptr(out["line_in_pattern"]), _ptr(out["line_gnomonic"]),
+                                              _ptr(out["line_pixel"]), *((_ptr(out[k]) if z else None) for k in
+                                                                         ("zone_in_pattern", "zone_gnomonic", "zone_pixel"))))
+        out["line_in_pattern"] = out["line_in_pattern"].view(np.bool_)
+        out["zone_in_pattern"] = out["zone_in_pattern"].view(np.bool_)
         return out
 
     def normalize_intensity(self, num_std=1, divide_by_square_root=False, dtype_out=None):
@@ -1451,6 +1507,12 @@ class Group(Context):
 
     def kinematical_master_pattern(self, *args, **kwargs):
         return self.root.kinematical_master_pattern(*args, **kwargs)
+
+    def geometrical_visibility(self, *args, **kwargs):
+        return self.root.geometrical_visibility(*args, **kwargs)
+
+    def geometrical_coordinates(self, *args, **kwargs):
+        return self.root.geometrical_coordinates(*args, **kwargs)
 
     def holds_result(self, simulation_indices):
         self.root._last_valid = self._last_valid

@@ -287,7 +287,7 @@ static int upload_taps(kpdi_ctx *c, const std::vector<double> &taps) {
 
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.11.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.12.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 
@@ -1268,6 +1268,167 @@ int kpdi_kinematical_master_pattern(kpdi_ctx *c, const double *unit_vectors, con
   if (e != hipSuccess)
     return fail(KPDI_EHIP, "kinematical master pattern kernel: %s (half_size %d, %lld reflectors)", hipGetErrorString(e), half_size,
                 (long long)m);
+  return rc;
+}
+
+// the per-point entries of a geometrical simulation, formed on the host (geometrical_plan.h) and uploaded to c->geo_points
+static int geometrical_points(kpdi_ctx *c, const double *rotations, int64_t n_points, const double *u_s, const double *a_star,
+                              const double *a_direct, const double *pcs, int64_t n_pc) {
+  std::vector<double> entries((size_t)n_points * kpdi::GEO_ENTRY_DOUBLES);
+  for (int64_t p = 0; p < n_points; ++p)
+    kpdi::geo_point_entry(rotations + 4 * p, u_s, a_star, a_direct, pcs + (n_pc == 1 ? 0 : p) * kpdi::GEO_PC_DOUBLES,
+                          &entries[(size_t)p * kpdi::GEO_ENTRY_DOUBLES]);
+  HIPCHK(c->geo_points.reserve(entries.size() * sizeof(double)));
+  HIPCHK(hipMemcpyAsync(c->geo_points.p, entries.data(), entries.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // `entries` leaves scope
+  return KPDI_OK;
+}
+
+static int geometrical_shape_refused(int64_t n_points, int64_t n_pc) {
+  if (n_points < 1 || n_points > INT_MAX) return fail(KPDI_EINVAL, "%lld map points: at least one is needed", (long long)n_points);
+  if (n_pc != 1 && n_pc != n_points)
+    return fail(KPDI_EINVAL, "%lld projection centres for %lld map points: one, or one per point", (long long)n_pc, (long long)n_points);
+  return KPDI_OK;
+}
+
+int kpdi_geometrical_visibility(kpdi_ctx *c, const double *vectors, int64_t m, int kind, const double *rotations,
+                                int64_t n_points, const double *u_s, const double *basis, const double *pcs, int64_t n_pc,
+                                uint8_t *flags) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!vectors || !rotations || !u_s || !basis || !pcs || !flags)
+    return fail(KPDI_EINVAL, "vectors, rotations, u_s, basis, pcs or flags is NULL");
+  if (m < 1 || m > INT_MAX) return fail(KPDI_EINVAL, "%lld features: at least one is needed", (long long)m);
+  int rc = geometrical_shape_refused(n_points, n_pc);
+  if (rc) return rc;
+  if (kind != KPDI_GEOMETRICAL_LINES && kind != KPDI_GEOMETRICAL_ZONE_AXES)
+    return fail(KPDI_EINVAL, "kind %d: 0 (lines) or 1 (zone axes)", kind);
+  const kpdi::GeoVisPlan plan = kpdi::geometrical_visibility_plan(m, n_points);
+  if (!plan.ok) return fail(KPDI_EINVAL, "visibility of %lld features at %lld map points: no kernel takes this shape", (long long)m,
+                            (long long)n_points);
+  rc = use_device(c);
+  if (rc) return rc;
+  rc = geometrical_points(c, rotations, n_points, u_s, kind == KPDI_GEOMETRICAL_LINES ? basis : nullptr,
+                          kind == KPDI_GEOMETRICAL_ZONE_AXES ? basis : nullptr, pcs, n_pc);
+  if (rc) return rc;
+  const size_t vec_bytes = (size_t)m * 3 * sizeof(double), partial_bytes = (size_t)plan.grid_y * (size_t)m;
+  HIPCHK(c->geo_vec.reserve(vec_bytes));
+  HIPCHK(c->geo_flags.reserve(partial_bytes + (size_t)m));
+  HIPCHK(hipMemcpyAsync(c->geo_vec.p, vectors, vec_bytes, hipMemcpyHostToDevice, c->stream));
+  kpdi::GeoVisLaunch l{};
+  l.vec = c->geo_vec.as<double>();
+  l.points = c->geo_points.as<double>();
+  l.m = m;
+  l.n_points = n_points;
+  l.kind = kind;
+  l.partial = c->geo_flags.as<uint8_t>();
+  l.flags = c->geo_flags.as<uint8_t>() + partial_bytes;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  if (c->profiling) {
+    HIPCHK(hipEventCreate(&ev0));
+    HIPCHK(hipEventCreate(&ev1));
+    HIPCHK(hipEventRecord(ev0, c->stream));
+  }
+  hipError_t e = kpdi::launch_geometrical_visibility(l, c->stream);
+  if (ev1) (void)hipEventRecord(ev1, c->stream);
+  if (e == hipSuccess) rc = kpdi::results_to_host(c, flags, l.flags, (size_t)m);  // (synchronises: `vectors` has been read)
+  if (ev1) {
+    float ms = 0.f;
+    if (e == hipSuccess && rc == KPDI_OK && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) c->cnt.geometrical_visibility_ms = ms;
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+  }
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "geometrical visibility kernel: %s (%lld features, %lld map points)", hipGetErrorString(e), (long long)m,
+                (long long)n_points);
+  return rc;
+}
+
+int kpdi_geometrical_coordinates(kpdi_ctx *c, const double *hkl, int64_t m, const double *uvw, int64_t z,
+                                 const double *rotations, int64_t n_points, const double *u_s, const double *a_star,
+                                 const double *a_direct, const double *pcs, int64_t n_pc, double r_gnomonic,
+                                 uint8_t *line_in_pattern, double *line_gnomonic, double *line_pixel,
+                                 uint8_t *zone_in_pattern, double *zone_gnomonic, double *zone_pixel) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!hkl || !rotations || !u_s || !a_star || !a_direct || !pcs || !line_in_pattern || !line_gnomonic || !line_pixel)
+    return fail(KPDI_EINVAL, "hkl, rotations, u_s, a_star, a_direct, pcs or a line output is NULL");
+  if (m < 1 || m > INT_MAX) return fail(KPDI_EINVAL, "%lld lines: at least one is needed", (long long)m);
+  if (z < 0 || z > INT_MAX) return fail(KPDI_EINVAL, "%lld zone axes: none or more", (long long)z);
+  if (z > 0 && (!uvw || !zone_in_pattern || !zone_gnomonic || !zone_pixel))
+    return fail(KPDI_EINVAL, "uvw or a zone axis output is NULL");
+  int rc = geometrical_shape_refused(n_points, n_pc);
+  if (rc) return rc;
+  rc = use_device(c);
+  if (rc) return rc;
+  size_t free_bytes = 0, total_bytes = 0;
+  HIPCHK(hipMemGetInfo(&free_bytes, &total_bytes));
+  const kpdi::GeoCoordPlan plan = kpdi::geometrical_coord_plan(m, z, n_points, free_bytes / 4);
+  if (!plan.ok) return fail(KPDI_EINVAL, "coordinates of %lld lines and %lld zone axes at %lld map points: no kernel takes this shape",
+                            (long long)m, (long long)z, (long long)n_points);
+  rc = geometrical_points(c, rotations, n_points, u_s, a_star, a_direct, pcs, n_pc);
+  if (rc) return rc;
+  // the outputs of one pass, each at a multiple of 256 bytes
+  const size_t P = (size_t)plan.points, M = (size_t)m, Z = (size_t)z;
+  const size_t sizes[6] = {P * M * 4 * sizeof(double), P * M * 4 * sizeof(double), P * Z * 2 * sizeof(double),
+                           P * Z * 2 * sizeof(double), P * M, P * Z};
+  size_t offset[6], total = 0;
+  for (int i = 0; i < 6; ++i) {
+    offset[i] = total;
+    total += (sizes[i] + 255) / 256 * 256;
+  }
+  const size_t hkl_bytes = M * 3 * sizeof(double), uvw_bytes = Z * 3 * sizeof(double);
+  HIPCHK(c->geo_out.reserve(total));
+  HIPCHK(c->geo_vec.reserve((hkl_bytes + 255) / 256 * 256 + uvw_bytes));
+  char *vec = c->geo_vec.as<char>(), *out = c->geo_out.as<char>();
+  HIPCHK(hipMemcpyAsync(vec, hkl, hkl_bytes, hipMemcpyHostToDevice, c->stream));
+  if (z > 0) HIPCHK(hipMemcpyAsync(vec + (hkl_bytes + 255) / 256 * 256, uvw, uvw_bytes, hipMemcpyHostToDevice, c->stream));
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  if (c->profiling) {
+    HIPCHK(hipEventCreate(&ev0));
+    HIPCHK(hipEventCreate(&ev1));
+  }
+  double kernel_ms = 0.0;
+  hipError_t e = hipSuccess;
+  for (int64_t pass = 0; pass < plan.n_passes && e == hipSuccess && rc == KPDI_OK; ++pass) {
+    const int64_t p0 = pass * plan.points;
+    const size_t np = (size_t)(pass == plan.n_passes - 1 ? plan.tail : plan.points);
+    kpdi::GeoCoordLaunch l{};
+    l.hkl = reinterpret_cast<const double *>(vec);
+    l.uvw = z > 0 ? reinterpret_cast<const double *>(vec + (hkl_bytes + 255) / 256 * 256) : nullptr;
+    l.points = c->geo_points.as<double>() + (size_t)p0 * kpdi::GEO_ENTRY_DOUBLES;
+    l.m = m;
+    l.z = z;
+    l.points_in_pass = (int64_t)np;
+    l.r_gnomonic = r_gnomonic;
+    l.line_gn = reinterpret_cast<double *>(out + offset[0]);
+    l.line_px = reinterpret_cast<double *>(out + offset[1]);
+    l.zone_gn = z > 0 ? reinterpret_cast<double *>(out + offset[2]) : nullptr;
+    l.zone_px = z > 0 ? reinterpret_cast<double *>(out + offset[3]) : nullptr;
+    l.line_in = reinterpret_cast<uint8_t *>(out + offset[4]);
+    l.zone_in = z > 0 ? reinterpret_cast<uint8_t *>(out + offset[5]) : nullptr;
+    if (ev0) (void)hipEventRecord(ev0, c->stream);
+    e = kpdi::launch_geometrical_coordinates(l, c->stream);
+    if (ev1) (void)hipEventRecord(ev1, c->stream);
+    if (e != hipSuccess) break;
+    const size_t at = (size_t)p0;
+    rc = kpdi::results_to_host(c, line_gnomonic + at * M * 4, l.line_gn, np * M * 4 * sizeof(double));
+    if (rc == KPDI_OK) rc = kpdi::results_to_host(c, line_pixel + at * M * 4, l.line_px, np * M * 4 * sizeof(double));
+    if (rc == KPDI_OK) rc = kpdi::results_to_host(c, line_in_pattern + at * M, l.line_in, np * M);
+    if (rc == KPDI_OK && z > 0) rc = kpdi::results_to_host(c, zone_gnomonic + at * Z * 2, l.zone_gn, np * Z * 2 * sizeof(double));
+    if (rc == KPDI_OK && z > 0) rc = kpdi::results_to_host(c, zone_pixel + at * Z * 2, l.zone_px, np * Z * 2 * sizeof(double));
+    if (rc == KPDI_OK && z > 0) rc = kpdi::results_to_host(c, zone_in_pattern + at * Z, l.zone_in, np * Z);
+    float ms = 0.f;
+    if (ev1 && rc == KPDI_OK && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) kernel_ms += ms;
+  }
+  if (ev1) {
+    if (e == hipSuccess && rc == KPDI_OK) c->cnt.geometrical_coordinates_ms = kernel_ms;
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(c->stream);  // the host copies of hkl / uvw may still be in flight
+    return fail(KPDI_EHIP, "geometrical coordinates kernel: %s (%lld lines, %lld zone axes, %lld map points)", hipGetErrorString(e),
+                (long long)m, (long long)z, (long long)n_points);
+  }
   return rc;
 }
 

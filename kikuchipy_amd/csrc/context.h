@@ -224,6 +224,9 @@ struct kpdi_ctx {
   kpdi::DevBuf dec_out, dec_mean, dec_in, dec_in2;
   // kpdi_kinematical_master_pattern: pixel directions, reflector table, the pattern
   kpdi::DevBuf kin_dirs, kin_table, kin_out;
+  // kpdi_geometrical_*: the feature indices, the per-point entries, the visibility flags (partial rows, then the OR) and the
+  // outputs of one pass of the coordinate kernel
+  kpdi::DevBuf geo_vec, geo_points, geo_flags, geo_out;
 
   // dictionary chunk
   kpdi::DevBuf dict_raw, dict_y;

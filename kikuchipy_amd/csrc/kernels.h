@@ -10,6 +10,7 @@
 #include "downsample_plan.h"
 #include "decomp_plan.h"
 #include "kinematical_plan.h"
+#include "geometrical_plan.h"
 #include "prep_plan.h"
 
 namespace kpdi {
@@ -502,5 +503,29 @@ struct KinLaunch {
 };
 KinPlan kinematical_launch_plan(int64_t m, int half_size, int hemispheres);  // reads the developer switch
 hipError_t launch_kinematical_master_pattern(const KinLaunch &l, hipStream_t s);
+
+// ---- geometrical simulations (geometrical.hip) ---------------------------------------------
+struct GeoVisLaunch {
+  const double *vec;     // [m][3]: hkl (GEO_LINES) or uvw (GEO_ZONE_AXES), device
+  const double *points;  // [n_points][GEO_ENTRY_DOUBLES] (geo_point_entry of geometrical_plan.h), device
+  int64_t m, n_points;
+  int kind;
+  uint8_t *partial;      // [GEO_MAX_GRID_Y][m] workspace, device
+  uint8_t *flags;        // [m]: GEO_FLAG_UPPER | GEO_FLAG_INSIDE, device
+};
+struct GeoCoordLaunch {
+  const double *hkl, *uvw;  // [m][3], [z][3] (z may be 0), device
+  const double *points;     // the entries of this pass's points, device
+  int64_t m, z, points_in_pass;
+  double r_gnomonic;
+  uint8_t *line_in;         // [points][m]
+  double *line_gn, *line_px;  // [points][m][4], 32-byte aligned
+  uint8_t *zone_in;         // [points][z]
+  double *zone_gn, *zone_px;  // [points][z][2], 16-byte aligned
+};
+GeoVisPlan geometrical_visibility_plan(int64_t m, int64_t n_points);                             // both read the
+GeoCoordPlan geometrical_coord_plan(int64_t m, int64_t z, int64_t n_points, size_t budget_bytes);  // developer switch
+hipError_t launch_geometrical_visibility(const GeoVisLaunch &l, hipStream_t s);
+hipError_t launch_geometrical_coordinates(const GeoCoordLaunch &l, hipStream_t s);
 
 }  // namespace kpdi
