@@ -575,6 +575,23 @@ int kpdi_refine_solve(kpdi_ctx *ctx, int mode, int64_t n_patterns, int n_starts,
 int kpdi_nelder_mead_selftest(kpdi_ctx *ctx, int kind, int nvar, const double *x0,
                               const double *lower, const double *upper, double xatol,
                               double fatol, int maxiter, int maxfev, double *result);
+/* scipy.optimize.minimize(method="Powell") of SciPy 1.15.3 (csrc/powell.h) from every start of every pattern: the
+ * arguments of kpdi_refine_solve with Powell's xtol / ftol.  Bounds: none, or finite for every variable (lower == upper
+ * allowed); non-finite bounds are refused.  maxiter / maxfev <= 0 = unset, by Powell's rule: 1000 * nvar each when both
+ * are unset, else the unset one is unlimited.  Result rows as kpdi_refine_solve.
+ * trace: NULL, or room for trace_capacity rows of nvar + 1 doubles: (x[0..nvar), f) of every objective evaluation of
+ * job trace_job (= pattern * n_starts + start), in order; evaluations beyond the capacity are counted (the job's nfev)
+ * but not stored. */
+int kpdi_refine_solve_powell(kpdi_ctx *ctx, int mode, int64_t n_patterns, int n_starts,
+                             const double *x0, const double *fixed, const double *lower,
+                             const double *upper, double xtol, double ftol, int maxiter, int maxfev,
+                             double *results, int64_t trace_job, double *trace, int trace_capacity);
+/* Powell alone on an analytic f64 objective, nvar <= 6 (kind 0: Rosenbrock, 1: weighted bowl, 2: kind 1 rounded to
+ * float32 and back, 3: kind 1 but NaN where x[0] > 1.9, 4: NaN everywhere).
+ * result: fun, nfev, nit, status (SciPy's 0..4), x[0..nvar). */
+int kpdi_powell_selftest(kpdi_ctx *ctx, int kind, int nvar, const double *x0, const double *lower,
+                         const double *upper, double xtol, double ftol, int maxiter, int maxfev,
+                         double *result);
 
 /* The top-k merge kernels alone, on lists the caller makes (tests/test_gpu_merge.py): everything is host memory.
  * kpdi_merge_selftest: n_src <= 3 sources; src_scores / src_idx / src_cnt are arrays of n_src host pointers

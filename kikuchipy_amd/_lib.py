@@ -181,6 +181,9 @@ SIGNATURES = {
     "kpdi_refine_objective": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp]),
     "kpdi_refine_solve": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i, _i, _vp]),
     "kpdi_nelder_mead_selftest": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _i, _i, _vp]),
+    "kpdi_refine_solve_powell": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i, _i, _vp, _i64, _vp,
+                                      _i]),
+    "kpdi_powell_selftest": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _i, _i, _vp]),
     "kpdi_merge_selftest": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.c_uint32,
                                  _vp, _vp, _i, _vp, _vp]),
     "kpdi_merge64_selftest": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _i, _i, _i64, _i64, _vp, _i, _i, _i,
@@ -887,6 +890,45 @@ class Context:
                                                _ptr(res)))
         return res
 
+    def refine_solve_powell(self, mode, x0, fixed=None, lower=None, upper=None, xtol=1e-4, ftol=1e-4, maxiter=0,
+                            maxfev=0, trace_job=None, trace_capacity=0):
+        """`scipy.optimize.minimize(method="Powell")` from every start on the device (kpdi_refine_solve_powell).
+        x0: (n_patterns, n_starts, nvar); bounds: none or finite.  Returns the (n_patterns, n_starts, 3 + nvar) rows
+        fun, nfev, nit, x.  With `trace_job` (= pattern * n_starts + start) also the (n_stored, nvar + 1) rows (x, f)
+        of that job's evaluations, the first `trace_capacity` of them, and how many there were in all."""
+        nvar, nfixed = REFINE_SIZES[mode]
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        if x0.ndim != 3 or x0.shape[2] != nvar:
+            raise KpdiError(f"x0 must have shape (n_patterns, n_starts, {nvar})")
+        n, starts = x0.shape[:2]
+        f = None if nfixed == 0 else np.ascontiguousarray(fixed, dtype=np.float64).reshape(n, starts, nfixed)
+        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).reshape(x0.shape)
+        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).reshape(x0.shape)
+        res = np.empty((n, starts, REFINE_RESULT_STRIDE), dtype=np.float64)
+        trace = None
+        if trace_job is not None:
+            if int(trace_capacity) < 1:
+                raise KpdiError("a trace needs trace_capacity >= 1")
+            trace = np.zeros((int(trace_capacity), nvar + 1), dtype=np.float64)
+        check(self._f.refine_solve_powell(self._h, int(mode), n, starts, _ptr(x0), _ptr(f), _ptr(lo), _ptr(hi),
+                                          float(xtol), float(ftol), int(maxiter or 0), int(maxfev or 0), _ptr(res),
+                                          int(trace_job or 0), _ptr(trace), int(trace_capacity) if trace is not None else 0))
+        res = res[:, :, :3 + nvar]
+        if trace is None:
+            return res
+        total = int(res.reshape(-1, 3 + nvar)[int(trace_job), 1])
+        return res, trace[:min(total, trace.shape[0])], total
+
+    def powell_selftest(self, kind, x0, lower=None, upper=None, xtol=1e-4, ftol=1e-4, maxiter=0, maxfev=0):
+        """csrc/powell.h alone on an analytic objective (kpdi_powell_selftest): fun, nfev, nit, status, x."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).ravel()
+        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).ravel()
+        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).ravel()
+        res = np.empty(4 + x0.size, dtype=np.float64)
+        check(self._f.powell_selftest(self._h, int(kind), x0.size, _ptr(x0), _ptr(lo), _ptr(hi), float(xtol),
+                                      float(ftol), int(maxiter or 0), int(maxfev or 0), _ptr(res)))
+        return res
+
     def merge_selftest(self, sources, m, k, out_scores, out_idx, out_offset=0, segments=None, seg_sources=0, force=-1):
         """merge.hip alone (kpdi_merge_selftest).  sources: up to three dicts of scores (float32), idx (int32), cnt
         (int32 (m, lists) or None), lists, len, row_stride, list_stride; out_scores / out_idx: (m, out_stride), prefilled.
@@ -1501,6 +1543,12 @@ class Group(Context):
 
     def nelder_mead_selftest(self, *args, **kwargs):
         return self.root.nelder_mead_selftest(*args, **kwargs)
+
+    def refine_solve_powell(self, *args, **kwargs):
+        return self.root.refine_solve_powell(*args, **kwargs)
+
+    def powell_selftest(self, *args, **kwargs):
+        return self.root.powell_selftest(*args, **kwargs)
 
     def orientation_similarity_map(self, *args, **kwargs):
         return self.root.orientation_similarity_map(*args, **kwargs)

@@ -287,7 +287,7 @@ static int upload_taps(kpdi_ctx *c, const std::vector<double> &taps) {
 
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.12.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.13.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 

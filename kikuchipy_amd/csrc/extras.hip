@@ -422,6 +422,106 @@ int kpdi_nelder_mead_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0,
   return KPDI_OK;
 }
 
+namespace {
+int powell_check_bounds(const double *lower, const double *upper, size_t count) {
+  for (size_t i = 0; i < count; ++i) {
+    if (!std::isfinite(lower[i]) || !std::isfinite(upper[i]))
+      return fail(KPDI_EINVAL, "Powell - bounds must be finite for every variable (one-sided bounds are not built)");
+    if (lower[i] > upper[i]) return fail(KPDI_EINVAL, "Powell - one of the lower bounds is greater than an upper bound.");
+  }
+  return KPDI_OK;
+}
+}  // namespace
+
+int kpdi_refine_solve_powell(kpdi_ctx *c, int mode, int64_t n_patterns, int n_starts, const double *x0,
+                             const double *fixed, const double *lower, const double *upper, double xtol, double ftol,
+                             int maxiter, int maxfev, double *results, int64_t trace_job, double *trace,
+                             int trace_capacity) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!x0 || !results) return fail(KPDI_EINVAL, "NULL argument");
+  if ((lower == nullptr) != (upper == nullptr)) return fail(KPDI_EINVAL, "give both bounds or neither");
+  if (n_starts <= 0) return fail(KPDI_EINVAL, "need at least one start per pattern");
+  int rc = use_device(c);
+  if (rc) return rc;
+  kpdi::RefineLaunch a{};
+  rc = refine_fill_launch(c, mode, &a);
+  if (rc) return rc;
+  if (n_patterns != c->ref_n)
+    return fail(KPDI_EINVAL, "%lld patterns were set but starts for %lld were given", (long long)c->ref_n,
+                (long long)n_patterns);
+  if (a.nfixed > 0 && !fixed) return fail(KPDI_EINVAL, "this mode needs the `fixed` array");
+  const int64_t jobs = n_patterns * n_starts;
+  if (jobs >= (int64_t)INT_MAX) return fail(KPDI_EINVAL, "too many (pattern, start) pairs");
+  if (trace && (trace_capacity <= 0 || trace_job < 0 || trace_job >= jobs))
+    return fail(KPDI_EINVAL, "the trace needs a capacity of at least 1 and a job within 0..%lld", (long long)jobs - 1);
+  const size_t nx = (size_t)jobs * a.nvar, nf = (size_t)jobs * a.nfixed;
+  if (lower && (rc = powell_check_bounds(lower, upper, nx))) return rc;
+  const size_t total = nx * (lower ? 3 : 1) + nf + 1;
+  const size_t trace_doubles = trace ? (size_t)trace_capacity * (a.nvar + 1) : 0;
+  HIPCHK(c->ref_in.reserve(total * sizeof(double)));
+  HIPCHK(c->ref_out.reserve(((size_t)jobs * kpdi::REFINE_RESULT_STRIDE + trace_doubles) * sizeof(double)));
+  double *d_x = c->ref_in.as<double>(), *d_f = d_x + nx, *d_lo = d_f + nf, *d_hi = d_lo + nx;
+  double *d_trace = c->ref_out.as<double>() + (size_t)jobs * kpdi::REFINE_RESULT_STRIDE;
+  HIPCHK(hipMemcpyAsync(d_x, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (nf) HIPCHK(hipMemcpyAsync(d_f, fixed, nf * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (lower) {
+    HIPCHK(hipMemcpyAsync(d_lo, lower, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_hi, upper, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(hipMemsetAsync(c->ref_out.p, 0, ((size_t)jobs * kpdi::REFINE_RESULT_STRIDE + trace_doubles) * sizeof(double),
+                        c->stream));
+  a.n_jobs = jobs;
+  a.n_starts = n_starts;
+  a.x0 = d_x;
+  a.fixed = d_f;
+  a.lower = lower ? d_lo : nullptr;
+  a.upper = lower ? d_hi : nullptr;
+  a.xatol = xtol;
+  a.fatol = ftol;
+  a.maxiter = maxiter;  // <= 0 = unset: resolved by Powell's rule (N * 1000 each, or the other unlimited) in powell.h
+  a.maxfun = maxfev;
+  a.results = c->ref_out.as<double>();
+  hipEvent_t e0 = c->get_event(), e1 = c->get_event();
+  HIPCHK(hipEventRecord(e0, c->stream));
+  HIPCHK(kpdi::launch_refine_solve_powell(a, trace_job, trace ? d_trace : nullptr, trace_capacity, c->stream));
+  HIPCHK(hipEventRecord(e1, c->stream));
+  if (trace)
+    HIPCHK(hipMemcpyAsync(trace, d_trace, trace_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  rc = results_to_host(c, results, c->ref_out.p, (size_t)jobs * kpdi::REFINE_RESULT_STRIDE * sizeof(double));
+  if (rc) return rc;
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+  c->cnt.refine_ms += ms;
+  c->ev_pool.push_back(e0);
+  c->ev_pool.push_back(e1);
+  return KPDI_OK;
+}
+
+int kpdi_powell_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0, const double *lower, const double *upper,
+                         double xtol, double ftol, int maxiter, int maxfev, double *result) {
+  if (!c || !x0 || !result) return fail(KPDI_EINVAL, "NULL argument");
+  if (kind < 0 || kind > 4) return fail(KPDI_EINVAL, "kind must be within 0..4");
+  if (nvar < 1 || nvar > 6) return fail(KPDI_EINVAL, "nvar must be within 1..6");
+  if ((lower == nullptr) != (upper == nullptr)) return fail(KPDI_EINVAL, "give both bounds or neither");
+  int rc;
+  if (lower && (rc = powell_check_bounds(lower, upper, (size_t)nvar))) return rc;
+  rc = use_device(c);
+  if (rc) return rc;
+  HIPCHK(c->ref_in.reserve((size_t)(3 * nvar + 1) * sizeof(double)));
+  HIPCHK(c->ref_out.reserve((size_t)(4 + nvar) * sizeof(double)));
+  double *d_x = c->ref_in.as<double>(), *d_lo = d_x + nvar, *d_hi = d_lo + nvar;
+  HIPCHK(hipMemcpyAsync(d_x, x0, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (lower) {
+    HIPCHK(hipMemcpyAsync(d_lo, lower, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_hi, upper, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(kpdi::launch_powell_selftest(kind, nvar, d_x, lower ? d_lo : nullptr, lower ? d_hi : nullptr, xtol, ftol,
+                                      maxiter, maxfev, c->ref_out.as<double>(), c->stream));
+  HIPCHK(hipMemcpyAsync(result, c->ref_out.p, (size_t)(4 + nvar) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return KPDI_OK;
+}
+
 // ---- the merge and fill kernels on caller-made lists (tests/test_gpu_merge.py) ------------------------------------
 // Host arrays in, the whole output buffer out: a test decides every byte the kernels see, what lies behind a list's
 // count included.  Every extent is checked against the buffer sizes given before anything is launched.

@@ -330,6 +330,13 @@ hipError_t launch_refine_prep(const void *raw, int dtype, int64_t n, int npix, c
                               float *out, double *sqnorm, hipStream_t s);
 hipError_t launch_refine_solve(const RefineLaunch &a, hipStream_t s);
 hipError_t launch_refine_objective(const RefineLaunch &a, const int *pattern_index, double *out, hipStream_t s);
+// SciPy's Powell (powell.h): a.xatol / a.fatol = xtol / ftol, a.maxiter / a.maxfun <= 0 = unset.  trace: rows
+// (x[0..nvar), f) of the evaluations of job `trace_job`, the first `trace_capacity` of them, or nullptr
+hipError_t launch_refine_solve_powell(const RefineLaunch &a, int64_t trace_job, double *trace, int trace_capacity,
+                                      hipStream_t s);
+// result: fun, nfev, nit, status, x[0..nvar)
+hipError_t launch_powell_selftest(int kind, int nvar, const double *x0, const double *lower, const double *upper,
+                                  double xtol, double ftol, int maxiter, int maxfev, double *result, hipStream_t s);
 hipError_t launch_nelder_mead_selftest(int kind, int nvar, const double *x0, const double *lower, const double *upper,
                                        double xatol, double fatol, int maxiter, int maxfun, double *result,
                                        hipStream_t s);

@@ -10,7 +10,10 @@
 // third-party dependency (pyproject: scipy >= 1.7); `NelderMead` below restates SciPy
 // 1.15.3's `_minimize_neldermead` (scipy/optimize/_optimize.py) operation for operation in
 // f64 without fused multiply-add, so that on the same objective values it walks the same
-// simplex path (kpdi_nelder_mead_selftest pins that bit for bit against SciPy).
+// simplex path (kpdi_nelder_mead_selftest pins that bit for bit against SciPy).  The second
+// device optimiser is scipy.optimize.minimize(method="Powell"), restated in powell.h and run
+// by `refine_solve_powell_kernel` (kpdi_powell_selftest pins it the same way); every other
+// optimiser stays on the host and calls `refine_objective_kernel`.
 //
 // One workgroup per (experimental pattern, start) runs the WHOLE optimisation: thread 0
 // owns the simplex (LDS) and decides the next point; all 256 threads evaluate the
@@ -27,6 +30,8 @@
 #pragma clang fp contract(off)
 
 #include <climits>
+
+#include "powell.h"
 
 namespace kpdi {
 
@@ -456,6 +461,89 @@ __global__ void nelder_mead_selftest_kernel(int kind, int nvar, const double *x0
   for (int i = 0; i < nvar; ++i) result[3 + i] = nm.sim[0][i];
 }
 
+// ---- SciPy's Powell (powell.h) on the device.  `refine_objective` returns the same bits in every thread and has
+// barriers inside, so the optimiser is not handed to one thread: EVERY thread runs it, as straight-line code on those
+// uniform values, with its state in private memory.  Control flow is then uniform by construction - all 256 threads
+// ask for the same evaluations in the same order and meet at the same barriers - and nothing is shared but `red`.
+struct RefinePowellEval {
+  int mode, nvar;
+  const double *fx;
+  const RefineGeom *g;
+  const float *pat;
+  double sqn;
+  double *red;
+  double *trace;  // rows (x[0..nvar), f) of this job's evaluations, or nullptr
+  int trace_capacity;
+  long long n_eval;
+  __device__ double eval(const double *x) {
+    double q[4], pc[3];
+    unpack_variables(mode, x, fx, q, pc);
+    const double f = refine_objective(q, pc, *g, pat, sqn, red);
+    if (trace != nullptr && threadIdx.x == 0 && n_eval < (long long)trace_capacity) {
+      double *row = trace + n_eval * (nvar + 1);
+      for (int i = 0; i < nvar; ++i) row[i] = x[i];
+      row[nvar] = f;
+    }
+    ++n_eval;
+    return f;
+  }
+};
+
+__global__ __launch_bounds__(REF_THREADS, 4) void refine_solve_powell_kernel(
+    int mode, int nvar, int nfixed, int n_starts, const double *x0, const double *fixed, const double *lower,
+    const double *upper, RefineGeom g, const float *patterns, const double *sqnorm, double xtol, double ftol, int maxiter,
+    int maxfev, double *results, long long trace_job, double *trace, int trace_capacity) {
+  __shared__ double red[3 * REF_THREADS / 64];
+  const int64_t job = blockIdx.x;  // (pattern, start)
+  const int64_t pat_id = job / n_starts;
+  RefinePowellEval ev;
+  ev.mode = mode;
+  ev.nvar = nvar;
+  ev.fx = fixed + job * nfixed;
+  ev.g = &g;
+  ev.pat = patterns + pat_id * g.k;
+  ev.sqn = sqnorm[pat_id];
+  ev.red = red;
+  ev.trace = job == trace_job ? trace : nullptr;
+  ev.trace_capacity = trace_capacity;
+  ev.n_eval = 0;
+  Powell<NV_MAX, RefinePowellEval> pw(ev);
+  pw.minimize(nvar, x0 + job * nvar, lower ? lower + job * nvar : nullptr, upper ? upper + job * nvar : nullptr, xtol,
+              ftol, maxiter, maxfev);
+  if (threadIdx.x == 0) {
+    double *o = results + job * RESULT_STRIDE;
+    o[0] = pw.fval;
+    o[1] = (double)pw.fcalls;
+    o[2] = (double)pw.iter;
+    for (int i = 0; i < nvar; ++i) o[3 + i] = pw.x[i];
+  }
+}
+
+// ---- powell.h alone on analytic f64 objectives: kinds 0 and 1 of `selftest_objective`, 2 = kind 1 rounded to float32
+// and back (plateaus and ties, like the real objective's float32 noise), 3 = kind 1 but NaN where x[0] > 1.9, 4 = NaN
+struct PowellSelftestEval {
+  int kind, n;
+  __device__ double eval(const double *x) const {
+    if (kind == 4 || (kind == 3 && x[0] > 1.9)) return __builtin_nan("");
+    const double f = selftest_objective(kind == 0 ? 0 : 1, n, x);
+    return kind == 2 ? (double)(float)f : f;
+  }
+};
+
+// result: fun, nfev, nit, status, x[0..nvar)
+__global__ void powell_selftest_kernel(int kind, int nvar, const double *x0, const double *lower, const double *upper,
+                                       double xtol, double ftol, int maxiter, int maxfev, double *result) {
+  if (threadIdx.x != 0) return;
+  PowellSelftestEval ev{kind, nvar};
+  Powell<NV_MAX, PowellSelftestEval> pw(ev);
+  pw.minimize(nvar, x0, lower, upper, xtol, ftol, maxiter, maxfev);
+  result[0] = pw.fval;
+  result[1] = (double)pw.fcalls;
+  result[2] = (double)pw.iter;
+  result[3] = (double)pw.status;
+  for (int i = 0; i < nvar; ++i) result[4 + i] = pw.x[i];
+}
+
 // ---- launchers
 static RefineGeom make_geom(const RefineLaunch &a) {
   RefineGeom g;
@@ -508,6 +596,23 @@ hipError_t launch_refine_objective(const RefineLaunch &a, const int *pattern_ind
   if (a.n_jobs <= 0) return hipSuccess;
   hipLaunchKernelGGL(refine_objective_kernel, dim3((unsigned)a.n_jobs), dim3(REF_THREADS), 0, s, a.mode, a.nvar,
                      a.nfixed, pattern_index, a.x0, a.fixed, make_geom(a), a.patterns, a.sqnorm, out);
+  return hipGetLastError();
+}
+
+// a.xatol / a.fatol: Powell's xtol / ftol; a.maxiter / a.maxfun as given (<= 0 = unset: powell.h resolves them)
+hipError_t launch_refine_solve_powell(const RefineLaunch &a, int64_t trace_job, double *trace, int trace_capacity,
+                                      hipStream_t s) {
+  if (a.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(refine_solve_powell_kernel, dim3((unsigned)a.n_jobs), dim3(REF_THREADS), 0, s, a.mode, a.nvar,
+                     a.nfixed, a.n_starts, a.x0, a.fixed, a.lower, a.upper, make_geom(a), a.patterns, a.sqnorm, a.xatol,
+                     a.fatol, a.maxiter, a.maxfun, a.results, (long long)trace_job, trace, trace_capacity);
+  return hipGetLastError();
+}
+
+hipError_t launch_powell_selftest(int kind, int nvar, const double *x0, const double *lower, const double *upper,
+                                  double xtol, double ftol, int maxiter, int maxfev, double *result, hipStream_t s) {
+  hipLaunchKernelGGL(powell_selftest_kernel, dim3(1), dim3(64), 0, s, kind, nvar, x0, lower, upper, xtol, ftol, maxiter,
+                     maxfev, result);
   return hipGetLastError();
 }
 

@@ -9,12 +9,18 @@ pattern to SciPy, which calls a Numba objective a few hundred times; here the
 whole map is ONE kernel launch (`kpdi_refine_solve`): a workgroup per (pattern,
 start) evaluates the objective and walks SciPy's simplex on the device.
 
-Every other optimiser the reference can dispatch to (SciPy's local methods and their options, its global
-methods, NLopt's LN_NELDERMEAD) keeps ITS optimiser on the host, called with the reference's arguments, with
-the objective evaluated on the device (`_HostOptimizer`); `compute=False` returns a `DeferredRefinement`
-in place of the reference's lazy Dask array.
+`scipy.optimize.minimize(method="Powell")` with its plain options (`tol`, `xtol`, `ftol`, `maxiter`, `maxfev`; what
+the reference's pattern-matching tutorial refines projection centres with) runs on the device in the same way
+(`kpdi_refine_solve_powell`, `_device_powell_options`); the environment variable KPDI_REFINE_POWELL=host, read at
+each call, sends it to the host path below instead.
+
+Every other optimiser the reference can dispatch to (SciPy's other local methods, Powell with `direc`, `callback` or
+`return_all`, its global methods, NLopt's LN_NELDERMEAD) keeps ITS optimiser on the host, called with the reference's
+arguments, with the objective evaluated on the device (`_HostOptimizer`); `compute=False` returns a
+`DeferredRefinement` in place of the reference's lazy Dask array.
 """
 
+import os
 import time
 
 import numpy as np
@@ -177,7 +183,8 @@ def _nelder_mead_options(method, method_kwargs, initial_step, maxeval):
 
 class _HostOptimizer:
     """Every optimiser of the reference other than plain Nelder-Mead (SciPy local methods with their
-    options, the SciPy global methods, NLopt's LN_NELDERMEAD): the OPTIMISER runs on the host exactly as
+    options, the SciPy global methods, NLopt's LN_NELDERMEAD; plain Powell only when `_device_powell_options`
+    declines it or KPDI_REFINE_POWELL=host asks for this path): the OPTIMISER runs on the host exactly as
     in the reference (indexing/_refinement/_solvers.py:79-250, :464-600: same call, same keyword
     arguments), the OBJECTIVE - master-pattern projection + NCC of one pattern - is one call into the
     device per evaluation (`kpdi_refine_objective`).  Slow next to the on-device simplex search (one
@@ -256,6 +263,42 @@ def _optimization_plan(method, method_kwargs, initial_step, rtol, maxeval, mode)
         host = _HostOptimizer((method or "minimize").lower(), method_kwargs, initial_step, rtol, maxeval, mode)
         return None, host, dict(method_name=host.method_name, type=host.type, package=host.package,
                                 supports_bounds=host.supports_bounds, kwargs=host.shown_kwargs, host=host)
+
+
+def _device_powell_options(host):
+    """dict(xtol, ftol, maxiter, maxfev) if `host` is `scipy.optimize.minimize(method="Powell")` with nothing but the
+    options the device solver restates (csrc/powell.h), else None: `direc`, `callback`, `return_all=True`, limits that
+    are not finite integers and every keyword this function does not know keep the optimiser on the host."""
+    if host is None or host.method != "minimize" or str(host.kwargs.get("method", "")).lower() != "powell":
+        return None
+    if set(host.kwargs) - {"method", "tol", "options"}:
+        return None
+    options = host.kwargs.get("options")
+    if options is None:
+        options = {}
+    if not isinstance(options, dict) or set(options) - {"xtol", "ftol", "maxiter", "maxfev", "disp", "return_all"}:
+        return None
+    if options.get("return_all"):
+        return None
+    tol = host.kwargs.get("tol")
+    out = {}
+    try:
+        for name in ("xtol", "ftol"):  # scipy.optimize.minimize: options.setdefault(name, tol)
+            value = options.get(name, 1e-4 if tol is None else tol)
+            out[name] = float(value)
+            if not np.isfinite(out[name]) or out[name] < 0:  # SciPy's Brent raises on a negative tolerance
+                return None
+        for name in ("maxiter", "maxfev"):
+            value = options.get(name)
+            if value is None:
+                out[name] = None
+                continue
+            if isinstance(value, bool) or not np.isfinite(value) or int(value) != value or not 0 < int(value) < 2**31:
+                return None
+            out[name] = int(value)
+    except (TypeError, ValueError):
+        return None
+    return out
 
 
 def _host_solve(ctx, mode_code, host, x0, fixed, lower, upper):
@@ -501,6 +544,12 @@ def _run_refinement(mode, n, starts, x0, fixed, lower, upper, pats, signal_mask,
             return c.refine_solve(MODES[mode], x0[part], None if fixed is None else fixed[part],
                                   None if lower is None else lower[part], None if upper is None else upper[part],
                                   nm["xatol"], nm["fatol"], nm["maxiter"] or 0, nm["maxfev"] or 0)
+        powell = _device_powell_options(host)
+        if powell is not None and os.environ.get("KPDI_REFINE_POWELL", "").lower() != "host":
+            # SciPy's Powell on the device: one launch, no objective call from the host
+            return c.refine_solve_powell(MODES[mode], x0[part], None if fixed is None else fixed[part],
+                                         None if lower is None else lower[part], None if upper is None else upper[part],
+                                         powell["xtol"], powell["ftol"], powell["maxiter"] or 0, powell["maxfev"] or 0)
         # the reference's optimiser on the host, the objective on the device
         return _host_solve(c, MODES[mode], host, x0[part], None if fixed is None else fixed[part],
                            None if lower is None else lower[part], None if upper is None else upper[part])

@@ -1,0 +1,237 @@
+"""SciPy's Powell without a GPU: csrc/powell.h compiled with the host compiler and run over tests/_powell_cases.py
+against `scipy.optimize.minimize(method="Powell")` bit for bit, with every branch of the header reached; which
+`method_kwargs` take the device solver (`_device_powell_options`); and the dispatch of `refine` with a stand-in context."""
+
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import _powell_cases as pc
+from kikuchipy_amd.indexing import _refinement as rf
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# The five objectives in the operation order of tests/_powell_cases.py.  One line per case on stdin:
+#   kind n bounded xtol ftol maxiter maxfev x0[n] [lower[n] upper[n]]     (floats as C99 hex)
+# one line per case out: status nfev nit fun x[n] (floats as their 64 bits), then "count <name> <hits>" per branch.
+DRIVER = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include "powell.h"
+
+struct Analytic {
+  int kind, n;
+  double eval(const double *x) {
+    if (kind == 4) return __builtin_nan("");
+    if (kind == 3 && x[0] > 1.9) return __builtin_nan("");
+    double acc = 0.0;
+    if (kind == 0) {
+      for (int i = 0; i + 1 < n; ++i) {
+        const double d = x[i + 1] - x[i] * x[i], e = 1.0 - x[i];
+        const double t = 100.0 * (d * d) + e * e;
+        acc = i == 0 ? t : acc + t;
+      }
+    } else {
+      for (int i = 0; i < n; ++i) {
+        const double d = x[i] - 0.3 * (double)(i + 1);
+        const double t = (double)(i + 1) * (d * d);
+        acc = i == 0 ? t : acc + t;
+      }
+    }
+    if (kind == 2) acc = (double)(float)acc;
+    return acc;
+  }
+};
+
+static unsigned long long bits(double v) {
+  unsigned long long u;
+  std::memcpy(&u, &v, 8);
+  return u;
+}
+
+int main() {
+  char line[4096];
+  while (std::fgets(line, sizeof line, stdin)) {
+    char *p = line;
+    Analytic f;
+    f.kind = (int)std::strtol(p, &p, 10);
+    f.n = (int)std::strtol(p, &p, 10);
+    const int bounded = (int)std::strtol(p, &p, 10);
+    const double xtol = std::strtod(p, &p), ftol = std::strtod(p, &p);
+    const long long maxiter = std::strtoll(p, &p, 10), maxfev = std::strtoll(p, &p, 10);
+    double x0[6], lo[6], hi[6];
+    if (f.n < 1 || f.n > 6) return 2;
+    for (int i = 0; i < f.n; ++i) x0[i] = std::strtod(p, &p);
+    if (bounded) {
+      for (int i = 0; i < f.n; ++i) lo[i] = std::strtod(p, &p);
+      for (int i = 0; i < f.n; ++i) hi[i] = std::strtod(p, &p);
+    }
+    kpdi::Powell<6, Analytic> pw(f);
+    pw.minimize(f.n, x0, bounded ? lo : nullptr, bounded ? hi : nullptr, xtol, ftol, maxiter, maxfev);
+    std::printf("%d %lld %lld %016llx", pw.status, pw.fcalls, pw.iter, bits(pw.fval));
+    for (int i = 0; i < f.n; ++i) std::printf(" %016llx", bits(pw.x[i]));
+    std::printf("\n");
+  }
+  for (int b = 0; b < kpdi::PWB_COUNT; ++b)
+    std::printf("count %s %lld\n", kpdi::kpdi_powell_branch_names[b], kpdi::kpdi_powell_count[b]);
+  return 0;
+}
+"""
+
+# Branches of powell.h that no analytic case reaches, with the reason (at most three may be listed).
+UNREACHED = {
+    "br_cap": "bracket's 1000-iteration cap: every pass that does not end the loop moves at least a golden-ratio step "
+              "downhill, and the five objectives are bounded below (or NaN, which ends the loop)",
+    "bt_exit_cap": "Brent's 500-iteration cap: a golden-section step shrinks the bracket by 0.62 at least every other "
+                   "pass, so a bracket of these objectives (width < 1e6) is below mintol = 1e-11 within 100 passes",
+    "ls_zero": "_linesearch_powell's all-zero direction: direc starts as the identity (it is not an argument here), a "
+               "new direction is stored only if np.any(direc1), and x - x1 = 0 means fx == fval, which ends the search "
+               "before the direction is used",
+}
+
+
+def case_line(case):
+    kind, x0, bounds, opt, _ = case
+    words = [str(kind), str(len(x0)), "0" if bounds is None else "1", float(opt.get("xtol", 1e-4)).hex(),
+             float(opt.get("ftol", 1e-4)).hex(), str(opt.get("maxiter", 0)), str(opt.get("maxfev", 0))]
+    words += [float(v).hex() for v in x0]
+    if bounds is not None:
+        words += [float(v).hex() for v in bounds[0]] + [float(v).hex() for v in bounds[1]]
+    return " ".join(words)
+
+
+@pytest.fixture(scope="module")
+def driver_output(tmp_path_factory):
+    cxx = shutil.which("c++") or shutil.which("g++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    tmp = tmp_path_factory.mktemp("powell")
+    src, exe = tmp / "powell_driver.cpp", tmp / "powell_driver"
+    src.write_text(DRIVER)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-DKPDI_POWELL_COUNT", "-I",
+                    os.path.join(ROOT, "kikuchipy_amd", "csrc"), str(src), "-o", str(exe)], check=True)
+    text = "\n".join(case_line(c) for c in pc.CASES) + "\n"
+    out = subprocess.run([str(exe)], input=text, check=True, capture_output=True, text=True).stdout.strip().split("\n")
+    rows = [ln.split() for ln in out if not ln.startswith("count ")]
+    counts = {ln.split()[1]: int(ln.split()[2]) for ln in out if ln.startswith("count ")}
+    assert len(rows) == len(pc.CASES)
+    return rows, counts
+
+
+def from_bits(words):
+    return np.array([int(w, 16) for w in words], dtype=np.uint64).view(np.float64)
+
+
+@pytest.mark.parametrize("case", range(len(pc.CASES)))
+def test_header_matches_scipy_bit_for_bit(driver_output, case):
+    row = driver_output[0][case]
+    want, pinned = pc.want(case), pc.CASES[case][4]
+    for name, value in pinned.items():  # what SciPy 1.15.3 returned when the table was written
+        assert int(getattr(want, name)) == value, (name, want)
+    status, nfev, nit = int(row[0]), int(row[1]), int(row[2])
+    fun, x = from_bits(row[3:4])[0], from_bits(row[4:])
+    assert (nfev, nit, status) == (want.nfev, want.nit, want.status), (row, want)
+    assert pc.same_bits(x, want.x), (x, want.x)
+    assert pc.same_bits(fun, want.fun), (fun, want.fun)
+
+
+def test_every_branch_of_the_header_is_reached(driver_output):
+    counts = driver_output[1]
+    assert len(UNREACHED) <= 3 and set(UNREACHED) <= set(counts)
+    missed = sorted(name for name, hits in counts.items() if hits == 0 and name not in UNREACHED)
+    assert not missed, missed
+    assert all(counts[name] == 0 for name in UNREACHED), "a branch listed as unreachable was reached: take it off the list"
+
+
+# ------------------------------------------------------------------ which calls take the device solver
+def _host(_optimiser="minimize", **method_kwargs):
+    return rf._optimization_plan(_optimiser, method_kwargs or None, None, 1e-4, None, "ori")[1]
+
+
+def test_device_powell_options():
+    assert rf._device_powell_options(_host(method="Powell")) == dict(xtol=1e-4, ftol=1e-4, maxiter=None, maxfev=None)
+    # tol fills xtol and ftol as scipy.optimize.minimize does; options override it; disp is ignored
+    assert rf._device_powell_options(_host(method="Powell", tol=1e-3)) == dict(xtol=1e-3, ftol=1e-3, maxiter=None,
+                                                                                maxfev=None)
+    got = rf._device_powell_options(_host(method="Powell", tol=1e-3, options=dict(ftol=1e-6, maxfev=120, disp=True)))
+    assert got == dict(xtol=1e-3, ftol=1e-6, maxiter=None, maxfev=120)
+    got = rf._device_powell_options(_host(method="powell", options=dict(xtol=1e-2, maxiter=7, return_all=False)))
+    assert got == dict(xtol=1e-2, ftol=1e-4, maxiter=7, maxfev=None)
+    # what the device solver does not restate stays on the host
+    for kwargs in (dict(options=dict(direc=np.eye(3))), dict(callback=print), dict(options=dict(return_all=True)),
+                   dict(options=dict(maxfev=np.inf)), dict(options=dict(maxiter=np.inf)), dict(options=dict(maxfev=2.5)),
+                   dict(options=dict(unknown_option=1)), dict(jac="2-point"), dict(options=dict(xtol=-1e-4)),
+                   dict(tol=float("nan"))):
+        assert rf._device_powell_options(_host(method="Powell", **kwargs)) is None, kwargs
+    assert rf._device_powell_options(_host(method="Nelder-Mead", options=dict(adaptive=True))) is None
+    assert rf._device_powell_options(_host(method="L-BFGS-B")) is None
+    assert rf._device_powell_options(_host("basinhopping", minimizer_kwargs=dict(method="Powell"))) is None
+    assert rf._device_powell_options(None) is None
+    # the plan itself is what it was: a host optimiser and the reference's message
+    nm, host, plan = rf._optimization_plan("minimize", dict(method="Powell"), None, 1e-4, None, "ori")
+    assert nm is None and isinstance(host, rf._HostOptimizer) and plan["method_name"] == "Powell"
+    info = rf._info_message("ori", [1, 1, 1], plan["kwargs"], 0, plan)
+    assert info == ("Refinement information:\n  Method: Powell (local) from SciPy\n  Trust region (+/-): [1 1 1]\n"
+                    "  Keyword arguments passed to method: {'method': 'Powell'}")
+
+
+class _Recorder:
+    """Stands in for the engine context of `refine`: records the solver and objective calls."""
+
+    def __init__(self):
+        self.powell, self.objective = [], 0
+
+    def set_master_pattern(self, up, lo):
+        pass
+
+    def refine_set_patterns(self, pats, signal_mask, rescale, om):
+        pass
+
+    def refine_solve_powell(self, mode, x0, fixed, lower, upper, xtol, ftol, maxiter, maxfev):
+        self.powell.append(dict(mode=mode, n=len(x0), bounded=lower is not None, xtol=xtol, ftol=ftol, maxiter=maxiter,
+                                maxfev=maxfev))
+        out = np.zeros(x0.shape[:2] + (3 + x0.shape[2],))
+        out[:, :, 0], out[:, :, 1], out[:, :, 3:] = 0.25, 77, x0
+        return out
+
+    def refine_objective(self, mode, pattern_index, x, fixed=None):
+        self.objective += len(pattern_index)
+        return np.array([0.5 + float(np.sum((np.asarray(xx) - 0.1) ** 2)) for xx in x])
+
+
+def test_refine_sends_plain_powell_to_the_device(monkeypatch):
+    import kikuchipy_amd as ka
+
+    det = ka.EBSDDetector(shape=(6, 6), pc=(0.4, 0.6, 0.5))
+    mp = ka.EBSDMasterPattern(np.random.default_rng(0).random((11, 11), dtype=np.float32))
+    pats = np.random.default_rng(1).integers(0, 255, (2, 3, 6, 6), dtype=np.uint8)
+    rot = np.tile([1.0, 0, 0, 0], (2, 3, 1))
+    monkeypatch.delenv("KPDI_REFINE_POWELL", raising=False)
+
+    def run(mode="ori", contexts=None, **method_kwargs):
+        ctx = _Recorder()
+        kw = dict(contexts=contexts(ctx)) if contexts else dict(context=ctx)
+        rf.refine(mode, pats, rot, det, mp, method_kwargs=dict(method="Powell", **method_kwargs), verbose=False,
+                  trust_region=[0.02] * 3 if mode == "pc" else None, **kw)
+        return ctx
+
+    ctx = run(tol=1e-3, options=dict(maxfev=120))
+    assert ctx.powell == [dict(mode=rf.MODES["ori"], n=6, bounded=False, xtol=1e-3, ftol=1e-3, maxiter=0, maxfev=120)]
+    assert ctx.objective == 0
+    ctx = run("pc", tol=1e-3)   # the tutorial's call: bounded
+    assert ctx.powell == [dict(mode=rf.MODES["pc"], n=6, bounded=True, xtol=1e-3, ftol=1e-3, maxiter=0, maxfev=0)]
+    assert ctx.objective == 0
+    ctx = run(contexts=lambda c: [c, c])   # one call per block of points
+    assert [call["n"] for call in ctx.powell] == [3, 3] and ctx.objective == 0
+    ctx = run(options=dict(direc=np.eye(3), maxfev=20))   # SciPy on the host, the objective through the context
+    assert ctx.powell == [] and ctx.objective == 6 * 20
+    monkeypatch.setenv("KPDI_REFINE_POWELL", "host")
+    ctx = run(options=dict(maxfev=20))
+    assert ctx.powell == [] and ctx.objective == 6 * 20
+    monkeypatch.setenv("KPDI_REFINE_POWELL", "device")   # anything but "host"
+    ctx = run(options=dict(maxfev=20))
+    assert len(ctx.powell) == 1 and ctx.objective == 0
