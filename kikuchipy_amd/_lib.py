@@ -863,10 +863,10 @@ class Context:
         check(self._f.refine_objective(self._h, int(mode), idx.size, _ptr(idx), _ptr(x), _ptr(f), _ptr(out)))
         return out
 
-    def refine_solve(self, mode, x0, fixed=None, lower=None, upper=None, xatol=1e-4, fatol=1e-4, maxiter=0,
-                     maxfev=0):
-        """x0: (n_patterns, n_starts, nvar).  Returns (n_patterns, n_starts, 3 + nvar):
-        fun, nfev, nit, x."""
+    @staticmethod
+    def _solve_arrays(mode, x0, fixed, lower, upper):
+        """The arrays of a batch of solves, shaped for the library: nvar, x0 (n_patterns, n_starts, nvar), fixed,
+        lower, upper (or None) and the empty result rows."""
         nvar, nfixed = REFINE_SIZES[mode]
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         if x0.ndim != 3 or x0.shape[2] != nvar:
@@ -875,20 +875,30 @@ class Context:
         f = None if nfixed == 0 else np.ascontiguousarray(fixed, dtype=np.float64).reshape(n, starts, nfixed)
         lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).reshape(x0.shape)
         hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).reshape(x0.shape)
-        res = np.empty((n, starts, REFINE_RESULT_STRIDE), dtype=np.float64)
-        check(self._f.refine_solve(self._h, int(mode), n, starts, _ptr(x0), _ptr(f), _ptr(lo), _ptr(hi),
-                                       float(xatol), float(fatol), int(maxiter or 0), int(maxfev or 0), _ptr(res)))
-        return res[:, :, :3 + nvar]
+        return nvar, x0, f, lo, hi, np.empty((n, starts, REFINE_RESULT_STRIDE), dtype=np.float64)
 
-    def nelder_mead_selftest(self, kind, x0, lower=None, upper=None, xatol=1e-4, fatol=1e-4, maxiter=0, maxfev=0):
+    def _optimiser_selftest(self, entry, n_head, kind, x0, lower, upper, xtol, ftol, maxiter, maxfev):
+        """One optimiser alone on an analytic objective: `n_head` result fields, then x."""
         x0 = np.ascontiguousarray(x0, dtype=np.float64).ravel()
         lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).ravel()
         hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).ravel()
-        res = np.empty(3 + x0.size, dtype=np.float64)
-        check(self._f.nelder_mead_selftest(self._h, int(kind), x0.size, _ptr(x0), _ptr(lo), _ptr(hi),
-                                               float(xatol), float(fatol), int(maxiter or 0), int(maxfev or 0),
-                                               _ptr(res)))
+        res = np.empty(n_head + x0.size, dtype=np.float64)
+        check(entry(self._h, int(kind), x0.size, _ptr(x0), _ptr(lo), _ptr(hi), float(xtol), float(ftol),
+                    int(maxiter or 0), int(maxfev or 0), _ptr(res)))
         return res
+
+    def refine_solve(self, mode, x0, fixed=None, lower=None, upper=None, xatol=1e-4, fatol=1e-4, maxiter=0,
+                     maxfev=0):
+        """x0: (n_patterns, n_starts, nvar).  Returns (n_patterns, n_starts, 3 + nvar):
+        fun, nfev, nit, x."""
+        nvar, x0, f, lo, hi, res = self._solve_arrays(mode, x0, fixed, lower, upper)
+        check(self._f.refine_solve(self._h, int(mode), x0.shape[0], x0.shape[1], _ptr(x0), _ptr(f), _ptr(lo), _ptr(hi),
+                                   float(xatol), float(fatol), int(maxiter or 0), int(maxfev or 0), _ptr(res)))
+        return res[:, :, :3 + nvar]
+
+    def nelder_mead_selftest(self, kind, x0, lower=None, upper=None, xatol=1e-4, fatol=1e-4, maxiter=0, maxfev=0):
+        return self._optimiser_selftest(self._f.nelder_mead_selftest, 3, kind, x0, lower, upper, xatol, fatol, maxiter,
+                                        maxfev)
 
     def refine_solve_powell(self, mode, x0, fixed=None, lower=None, upper=None, xtol=1e-4, ftol=1e-4, maxiter=0,
                             maxfev=0, trace_job=None, trace_capacity=0):
@@ -896,22 +906,14 @@ class Context:
         x0: (n_patterns, n_starts, nvar); bounds: none or finite.  Returns the (n_patterns, n_starts, 3 + nvar) rows
         fun, nfev, nit, x.  With `trace_job` (= pattern * n_starts + start) also the (n_stored, nvar + 1) rows (x, f)
         of that job's evaluations, the first `trace_capacity` of them, and how many there were in all."""
-        nvar, nfixed = REFINE_SIZES[mode]
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        if x0.ndim != 3 or x0.shape[2] != nvar:
-            raise KpdiError(f"x0 must have shape (n_patterns, n_starts, {nvar})")
-        n, starts = x0.shape[:2]
-        f = None if nfixed == 0 else np.ascontiguousarray(fixed, dtype=np.float64).reshape(n, starts, nfixed)
-        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).reshape(x0.shape)
-        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).reshape(x0.shape)
-        res = np.empty((n, starts, REFINE_RESULT_STRIDE), dtype=np.float64)
+        nvar, x0, f, lo, hi, res = self._solve_arrays(mode, x0, fixed, lower, upper)
         trace = None
         if trace_job is not None:
             if int(trace_capacity) < 1:
                 raise KpdiError("a trace needs trace_capacity >= 1")
             trace = np.zeros((int(trace_capacity), nvar + 1), dtype=np.float64)
-        check(self._f.refine_solve_powell(self._h, int(mode), n, starts, _ptr(x0), _ptr(f), _ptr(lo), _ptr(hi),
-                                          float(xtol), float(ftol), int(maxiter or 0), int(maxfev or 0), _ptr(res),
+        check(self._f.refine_solve_powell(self._h, int(mode), x0.shape[0], x0.shape[1], _ptr(x0), _ptr(f), _ptr(lo),
+                                          _ptr(hi), float(xtol), float(ftol), int(maxiter or 0), int(maxfev or 0), _ptr(res),
                                           int(trace_job or 0), _ptr(trace), int(trace_capacity) if trace is not None else 0))
         res = res[:, :, :3 + nvar]
         if trace is None:
@@ -921,13 +923,7 @@ class Context:
 
     def powell_selftest(self, kind, x0, lower=None, upper=None, xtol=1e-4, ftol=1e-4, maxiter=0, maxfev=0):
         """csrc/powell.h alone on an analytic objective (kpdi_powell_selftest): fun, nfev, nit, status, x."""
-        x0 = np.ascontiguousarray(x0, dtype=np.float64).ravel()
-        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64).ravel()
-        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).ravel()
-        res = np.empty(4 + x0.size, dtype=np.float64)
-        check(self._f.powell_selftest(self._h, int(kind), x0.size, _ptr(x0), _ptr(lo), _ptr(hi), float(xtol),
-                                      float(ftol), int(maxiter or 0), int(maxfev or 0), _ptr(res)))
-        return res
+        return self._optimiser_selftest(self._f.powell_selftest, 4, kind, x0, lower, upper, xtol, ftol, maxiter, maxfev)
 
     def merge_selftest(self, sources, m, k, out_scores, out_idx, out_offset=0, segments=None, seg_sources=0, force=-1):
         """merge.hip alone (kpdi_merge_selftest).  sources: up to three dicts of scores (float32), idx (int32), cnt

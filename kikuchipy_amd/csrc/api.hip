@@ -1250,21 +1250,13 @@ int kpdi_kinematical_master_pattern(kpdi_ctx *c, const double *unit_vectors, con
   l.half_size = half_size;
   l.hemispheres = hemispheres;
   l.out = c->kin_out.as<double>();
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (c->profiling) {
-    HIPCHK(hipEventCreate(&ev0));
-    HIPCHK(hipEventCreate(&ev1));
-    HIPCHK(hipEventRecord(ev0, c->stream));
-  }
+  kpdi::EventPair timer(c, c->profiling != 0);
+  HIPCHK(timer.begin());
   hipError_t e = kpdi::launch_kinematical_master_pattern(l, c->stream);
-  if (ev1) (void)hipEventRecord(ev1, c->stream);
+  (void)timer.end();
   if (e == hipSuccess) rc = kpdi::results_to_host(c, out, c->kin_out.p, out_bytes);  // (synchronises: the host tables are read)
-  if (ev1) {
-    float ms = 0.f;
-    if (e == hipSuccess && rc == KPDI_OK && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) c->cnt.kinematical_ms = ms;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-  }
+  float ms = 0.f;
+  if (e == hipSuccess && rc == KPDI_OK && timer.elapsed(&ms) == hipSuccess) c->cnt.kinematical_ms = ms;
   if (e != hipSuccess)
     return fail(KPDI_EHIP, "kinematical master pattern kernel: %s (half_size %d, %lld reflectors)", hipGetErrorString(e), half_size,
                 (long long)m);
@@ -1322,21 +1314,13 @@ int kpdi_geometrical_visibility(kpdi_ctx *c, const double *vectors, int64_t m, i
   l.kind = kind;
   l.partial = c->geo_flags.as<uint8_t>();
   l.flags = c->geo_flags.as<uint8_t>() + partial_bytes;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (c->profiling) {
-    HIPCHK(hipEventCreate(&ev0));
-    HIPCHK(hipEventCreate(&ev1));
-    HIPCHK(hipEventRecord(ev0, c->stream));
-  }
+  kpdi::EventPair timer(c, c->profiling != 0);
+  HIPCHK(timer.begin());
   hipError_t e = kpdi::launch_geometrical_visibility(l, c->stream);
-  if (ev1) (void)hipEventRecord(ev1, c->stream);
+  (void)timer.end();
   if (e == hipSuccess) rc = kpdi::results_to_host(c, flags, l.flags, (size_t)m);  // (synchronises: `vectors` has been read)
-  if (ev1) {
-    float ms = 0.f;
-    if (e == hipSuccess && rc == KPDI_OK && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) c->cnt.geometrical_visibility_ms = ms;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-  }
+  float ms = 0.f;
+  if (e == hipSuccess && rc == KPDI_OK && timer.elapsed(&ms) == hipSuccess) c->cnt.geometrical_visibility_ms = ms;
   if (e != hipSuccess)
     return fail(KPDI_EHIP, "geometrical visibility kernel: %s (%lld features, %lld map points)", hipGetErrorString(e), (long long)m,
                 (long long)n_points);
@@ -1381,11 +1365,7 @@ int kpdi_geometrical_coordinates(kpdi_ctx *c, const double *hkl, int64_t m, cons
   char *vec = c->geo_vec.as<char>(), *out = c->geo_out.as<char>();
   HIPCHK(hipMemcpyAsync(vec, hkl, hkl_bytes, hipMemcpyHostToDevice, c->stream));
   if (z > 0) HIPCHK(hipMemcpyAsync(vec + (hkl_bytes + 255) / 256 * 256, uvw, uvw_bytes, hipMemcpyHostToDevice, c->stream));
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (c->profiling) {
-    HIPCHK(hipEventCreate(&ev0));
-    HIPCHK(hipEventCreate(&ev1));
-  }
+  kpdi::EventPair timer(c, c->profiling != 0);  // recorded again in every pass
   double kernel_ms = 0.0;
   hipError_t e = hipSuccess;
   for (int64_t pass = 0; pass < plan.n_passes && e == hipSuccess && rc == KPDI_OK; ++pass) {
@@ -1405,9 +1385,9 @@ int kpdi_geometrical_coordinates(kpdi_ctx *c, const double *hkl, int64_t m, cons
     l.zone_px = z > 0 ? reinterpret_cast<double *>(out + offset[3]) : nullptr;
     l.line_in = reinterpret_cast<uint8_t *>(out + offset[4]);
     l.zone_in = z > 0 ? reinterpret_cast<uint8_t *>(out + offset[5]) : nullptr;
-    if (ev0) (void)hipEventRecord(ev0, c->stream);
+    (void)timer.begin();
     e = kpdi::launch_geometrical_coordinates(l, c->stream);
-    if (ev1) (void)hipEventRecord(ev1, c->stream);
+    (void)timer.end();
     if (e != hipSuccess) break;
     const size_t at = (size_t)p0;
     rc = kpdi::results_to_host(c, line_gnomonic + at * M * 4, l.line_gn, np * M * 4 * sizeof(double));
@@ -1417,13 +1397,9 @@ int kpdi_geometrical_coordinates(kpdi_ctx *c, const double *hkl, int64_t m, cons
     if (rc == KPDI_OK && z > 0) rc = kpdi::results_to_host(c, zone_pixel + at * Z * 2, l.zone_px, np * Z * 2 * sizeof(double));
     if (rc == KPDI_OK && z > 0) rc = kpdi::results_to_host(c, zone_in_pattern + at * Z, l.zone_in, np * Z);
     float ms = 0.f;
-    if (ev1 && rc == KPDI_OK && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) kernel_ms += ms;
+    if (rc == KPDI_OK && timer.elapsed(&ms) == hipSuccess) kernel_ms += ms;
   }
-  if (ev1) {
-    if (e == hipSuccess && rc == KPDI_OK) c->cnt.geometrical_coordinates_ms = kernel_ms;
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-  }
+  if (timer.on() && e == hipSuccess && rc == KPDI_OK) c->cnt.geometrical_coordinates_ms = kernel_ms;
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(c->stream);  // the host copies of hkl / uvw may still be in flight
     return fail(KPDI_EHIP, "geometrical coordinates kernel: %s (%lld lines, %lld zone axes, %lld map points)", hipGetErrorString(e),

@@ -425,6 +425,30 @@ struct ScopedTimer {
   }
 };
 
+// the event pair of an entry point that times its own kernel and synchronises before it returns: both events are
+// back in ev_pool on every path out, error returns included.  `on` = false takes no events and records nothing.
+struct EventPair {
+  kpdi_ctx *c;
+  hipEvent_t a = nullptr, b = nullptr;
+  explicit EventPair(kpdi_ctx *ctx, bool on = true) : c(ctx) {
+    if (on) {
+      a = c->get_event();
+      b = c->get_event();
+    }
+  }
+  EventPair(const EventPair &) = delete;
+  EventPair &operator=(const EventPair &) = delete;
+  ~EventPair() {
+    if (a) c->ev_pool.push_back(a);
+    if (b) c->ev_pool.push_back(b);
+  }
+  bool on() const { return a && b; }
+  hipError_t begin() { return on() ? hipEventRecord(a, c->stream) : hipSuccess; }
+  hipError_t end() { return on() ? hipEventRecord(b, c->stream) : hipSuccess; }
+  // after the stream has been synchronised
+  hipError_t elapsed(float *ms) { return on() ? hipEventElapsedTime(ms, a, b) : hipErrorInvalidValue; }
+};
+
 // ---- api.hip
 int drain_events(kpdi_ctx *c, std::vector<std::pair<hipEvent_t, hipEvent_t>> &list, double *ms_sum);
 int wait_result_copy(kpdi_ctx *c);

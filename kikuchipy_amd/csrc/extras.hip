@@ -335,94 +335,14 @@ void resolve_budget(int nvar, int maxiter, int maxfev, int *it, int *fev) {
     *fev = maxfev;
   }
 }
-}  // namespace
 
-extern "C" {
-
-int kpdi_refine_solve(kpdi_ctx *c, int mode, int64_t n_patterns, int n_starts, const double *x0, const double *fixed,
-                      const double *lower, const double *upper, double xatol, double fatol, int maxiter, int maxfev,
-                      double *results) {
-  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
-  if (!x0 || !results) return fail(KPDI_EINVAL, "NULL argument");
-  if ((lower == nullptr) != (upper == nullptr)) return fail(KPDI_EINVAL, "give both bounds or neither");
-  if (n_starts <= 0) return fail(KPDI_EINVAL, "need at least one start per pattern");
-  int rc = use_device(c);
-  if (rc) return rc;
-  kpdi::RefineLaunch a{};
-  rc = refine_fill_launch(c, mode, &a);
-  if (rc) return rc;
-  if (n_patterns != c->ref_n)
-    return fail(KPDI_EINVAL, "%lld patterns were set but starts for %lld were given", (long long)c->ref_n,
-                (long long)n_patterns);
-  if (a.nfixed > 0 && !fixed) return fail(KPDI_EINVAL, "this mode needs the `fixed` array");
-  const int64_t jobs = n_patterns * n_starts;
-  if (jobs >= (int64_t)INT_MAX) return fail(KPDI_EINVAL, "too many (pattern, start) pairs");
-  const size_t nx = (size_t)jobs * a.nvar, nf = (size_t)jobs * a.nfixed;
-  if (lower)
-    for (size_t i = 0; i < nx; ++i)
-      if (lower[i] > upper[i])
-        return fail(KPDI_EINVAL, "Nelder Mead - one of the lower bounds is greater than an upper bound.");
-  const size_t total = nx * (lower ? 3 : 1) + nf + 1;
-  HIPCHK(c->ref_in.reserve(total * sizeof(double)));
-  HIPCHK(c->ref_out.reserve((size_t)jobs * kpdi::REFINE_RESULT_STRIDE * sizeof(double)));
-  double *d_x = c->ref_in.as<double>(), *d_f = d_x + nx, *d_lo = d_f + nf, *d_hi = d_lo + nx;
-  HIPCHK(hipMemcpyAsync(d_x, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (nf) HIPCHK(hipMemcpyAsync(d_f, fixed, nf * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (lower) {
-    HIPCHK(hipMemcpyAsync(d_lo, lower, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_hi, upper, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  }
-  HIPCHK(hipMemsetAsync(c->ref_out.p, 0, (size_t)jobs * kpdi::REFINE_RESULT_STRIDE * sizeof(double), c->stream));
-  a.n_jobs = jobs;
-  a.n_starts = n_starts;
-  a.x0 = d_x;
-  a.fixed = d_f;
-  a.lower = lower ? d_lo : nullptr;
-  a.upper = lower ? d_hi : nullptr;
-  a.xatol = xatol;
-  a.fatol = fatol;
-  resolve_budget(a.nvar, maxiter, maxfev, &a.maxiter, &a.maxfun);
-  a.results = c->ref_out.as<double>();
-  hipEvent_t e0 = c->get_event(), e1 = c->get_event();
-  HIPCHK(hipEventRecord(e0, c->stream));
-  HIPCHK(kpdi::launch_refine_solve(a, c->stream));
-  HIPCHK(hipEventRecord(e1, c->stream));
-  rc = results_to_host(c, results, c->ref_out.p, (size_t)jobs * kpdi::REFINE_RESULT_STRIDE * sizeof(double));
-  if (rc) return rc;
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-  c->cnt.refine_ms += ms;
-  c->ev_pool.push_back(e0);
-  c->ev_pool.push_back(e1);
+int nelder_mead_check_bounds(const double *lower, const double *upper, size_t count) {
+  for (size_t i = 0; i < count; ++i)
+    if (lower[i] > upper[i])
+      return fail(KPDI_EINVAL, "Nelder Mead - one of the lower bounds is greater than an upper bound.");
   return KPDI_OK;
 }
 
-int kpdi_nelder_mead_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0, const double *lower,
-                              const double *upper, double xatol, double fatol, int maxiter, int maxfev,
-                              double *result) {
-  if (!c || !x0 || !result) return fail(KPDI_EINVAL, "NULL argument");
-  if (nvar < 1 || nvar > 6) return fail(KPDI_EINVAL, "nvar must be within 1..6");
-  if ((lower == nullptr) != (upper == nullptr)) return fail(KPDI_EINVAL, "give both bounds or neither");
-  int rc = use_device(c);
-  if (rc) return rc;
-  HIPCHK(c->ref_in.reserve((size_t)(3 * nvar + 1) * sizeof(double)));
-  HIPCHK(c->ref_out.reserve((size_t)kpdi::REFINE_RESULT_STRIDE * sizeof(double)));
-  double *d_x = c->ref_in.as<double>(), *d_lo = d_x + nvar, *d_hi = d_lo + nvar;
-  HIPCHK(hipMemcpyAsync(d_x, x0, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (lower) {
-    HIPCHK(hipMemcpyAsync(d_lo, lower, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_hi, upper, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  }
-  int it, fev;
-  resolve_budget(nvar, maxiter, maxfev, &it, &fev);
-  HIPCHK(kpdi::launch_nelder_mead_selftest(kind, nvar, d_x, lower ? d_lo : nullptr, lower ? d_hi : nullptr, xatol,
-                                           fatol, it, fev, c->ref_out.as<double>(), c->stream));
-  HIPCHK(hipMemcpyAsync(result, c->ref_out.p, (size_t)(3 + nvar) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return KPDI_OK;
-}
-
-namespace {
 int powell_check_bounds(const double *lower, const double *upper, size_t count) {
   for (size_t i = 0; i < count; ++i) {
     if (!std::isfinite(lower[i]) || !std::isfinite(upper[i]))
@@ -431,12 +351,20 @@ int powell_check_bounds(const double *lower, const double *upper, size_t count) 
   }
   return KPDI_OK;
 }
-}  // namespace
 
-int kpdi_refine_solve_powell(kpdi_ctx *c, int mode, int64_t n_patterns, int n_starts, const double *x0,
-                             const double *fixed, const double *lower, const double *upper, double xtol, double ftol,
-                             int maxiter, int maxfev, double *results, int64_t trace_job, double *trace,
-                             int trace_capacity) {
+// what a solver plugs into refine_solve: everything else of a solve is the same for every solver
+struct RefineSolver {
+  int (*check_bounds)(const double *lower, const double *upper, size_t count);
+  // a.maxiter / a.maxfun from the caller's maxiter / maxfev (<= 0 = unset)
+  void (*budget)(int nvar, int maxiter, int maxfev, int *it, int *fev);
+  hipError_t (*launch)(const kpdi::RefineLaunch &a, int64_t trace_job, double *d_trace, int trace_capacity, hipStream_t s);
+};
+
+// one solve of n_patterns * n_starts jobs.  ref_in holds x0 | fixed | lower | upper, ref_out the result rows and, behind
+// them, the `trace_capacity` rows (x[0..nvar), f) of job `trace_job` when the caller gives a `trace`
+int refine_solve(kpdi_ctx *c, const RefineSolver &solver, int mode, int64_t n_patterns, int n_starts, const double *x0,
+                 const double *fixed, const double *lower, const double *upper, double xtol, double ftol, int maxiter,
+                 int maxfev, double *results, int64_t trace_job, double *trace, int trace_capacity) {
   if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
   if (!x0 || !results) return fail(KPDI_EINVAL, "NULL argument");
   if ((lower == nullptr) != (upper == nullptr)) return fail(KPDI_EINVAL, "give both bounds or neither");
@@ -455,21 +383,21 @@ int kpdi_refine_solve_powell(kpdi_ctx *c, int mode, int64_t n_patterns, int n_st
   if (trace && (trace_capacity <= 0 || trace_job < 0 || trace_job >= jobs))
     return fail(KPDI_EINVAL, "the trace needs a capacity of at least 1 and a job within 0..%lld", (long long)jobs - 1);
   const size_t nx = (size_t)jobs * a.nvar, nf = (size_t)jobs * a.nfixed;
-  if (lower && (rc = powell_check_bounds(lower, upper, nx))) return rc;
+  if (lower && (rc = solver.check_bounds(lower, upper, nx))) return rc;
   const size_t total = nx * (lower ? 3 : 1) + nf + 1;
+  const size_t result_doubles = (size_t)jobs * kpdi::REFINE_RESULT_STRIDE;
   const size_t trace_doubles = trace ? (size_t)trace_capacity * (a.nvar + 1) : 0;
   HIPCHK(c->ref_in.reserve(total * sizeof(double)));
-  HIPCHK(c->ref_out.reserve(((size_t)jobs * kpdi::REFINE_RESULT_STRIDE + trace_doubles) * sizeof(double)));
+  HIPCHK(c->ref_out.reserve((result_doubles + trace_doubles) * sizeof(double)));
   double *d_x = c->ref_in.as<double>(), *d_f = d_x + nx, *d_lo = d_f + nf, *d_hi = d_lo + nx;
-  double *d_trace = c->ref_out.as<double>() + (size_t)jobs * kpdi::REFINE_RESULT_STRIDE;
+  double *d_trace = c->ref_out.as<double>() + result_doubles;
   HIPCHK(hipMemcpyAsync(d_x, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (nf) HIPCHK(hipMemcpyAsync(d_f, fixed, nf * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (lower) {
     HIPCHK(hipMemcpyAsync(d_lo, lower, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_hi, upper, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
-  HIPCHK(hipMemsetAsync(c->ref_out.p, 0, ((size_t)jobs * kpdi::REFINE_RESULT_STRIDE + trace_doubles) * sizeof(double),
-                        c->stream));
+  HIPCHK(hipMemsetAsync(c->ref_out.p, 0, (result_doubles + trace_doubles) * sizeof(double), c->stream));
   a.n_jobs = jobs;
   a.n_starts = n_starts;
   a.x0 = d_x;
@@ -478,23 +406,93 @@ int kpdi_refine_solve_powell(kpdi_ctx *c, int mode, int64_t n_patterns, int n_st
   a.upper = lower ? d_hi : nullptr;
   a.xatol = xtol;
   a.fatol = ftol;
-  a.maxiter = maxiter;  // <= 0 = unset: resolved by Powell's rule (N * 1000 each, or the other unlimited) in powell.h
-  a.maxfun = maxfev;
+  solver.budget(a.nvar, maxiter, maxfev, &a.maxiter, &a.maxfun);
   a.results = c->ref_out.as<double>();
-  hipEvent_t e0 = c->get_event(), e1 = c->get_event();
-  HIPCHK(hipEventRecord(e0, c->stream));
-  HIPCHK(kpdi::launch_refine_solve_powell(a, trace_job, trace ? d_trace : nullptr, trace_capacity, c->stream));
-  HIPCHK(hipEventRecord(e1, c->stream));
+  kpdi::EventPair timer(c);
+  HIPCHK(timer.begin());
+  HIPCHK(solver.launch(a, trace_job, trace ? d_trace : nullptr, trace_capacity, c->stream));
+  HIPCHK(timer.end());
   if (trace)
     HIPCHK(hipMemcpyAsync(trace, d_trace, trace_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  rc = results_to_host(c, results, c->ref_out.p, (size_t)jobs * kpdi::REFINE_RESULT_STRIDE * sizeof(double));
+  rc = results_to_host(c, results, c->ref_out.p, result_doubles * sizeof(double));
   if (rc) return rc;
   float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+  HIPCHK(timer.elapsed(&ms));
   c->cnt.refine_ms += ms;
-  c->ev_pool.push_back(e0);
-  c->ev_pool.push_back(e1);
   return KPDI_OK;
+}
+
+// one job of an optimiser's self-test: x0 | lower | upper into ref_in (`lo` and `hi` stay NULL without bounds) and room
+// for `n_out` doubles in ref_out
+struct SelftestIn {
+  double *x, *lo, *hi;
+};
+
+int selftest_upload(kpdi_ctx *c, int nvar, const double *x0, const double *lower, const double *upper, int n_out,
+                    SelftestIn *in) {
+  HIPCHK(c->ref_in.reserve((size_t)(3 * nvar + 1) * sizeof(double)));
+  HIPCHK(c->ref_out.reserve((size_t)n_out * sizeof(double)));
+  in->x = c->ref_in.as<double>();
+  in->lo = lower ? in->x + nvar : nullptr;
+  in->hi = lower ? in->x + 2 * nvar : nullptr;
+  HIPCHK(hipMemcpyAsync(in->x, x0, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (lower) {
+    HIPCHK(hipMemcpyAsync(in->lo, lower, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(in->hi, upper, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  return KPDI_OK;
+}
+
+int selftest_download(kpdi_ctx *c, double *result, int n_out) {
+  HIPCHK(hipMemcpyAsync(result, c->ref_out.p, (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return KPDI_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kpdi_refine_solve(kpdi_ctx *c, int mode, int64_t n_patterns, int n_starts, const double *x0, const double *fixed,
+                      const double *lower, const double *upper, double xatol, double fatol, int maxiter, int maxfev,
+                      double *results) {
+  static const RefineSolver nelder_mead = {
+      nelder_mead_check_bounds, resolve_budget,
+      [](const kpdi::RefineLaunch &a, int64_t, double *, int, hipStream_t s) { return kpdi::launch_refine_solve(a, s); }};
+  return refine_solve(c, nelder_mead, mode, n_patterns, n_starts, x0, fixed, lower, upper, xatol, fatol, maxiter, maxfev,
+                      results, 0, nullptr, 0);
+}
+
+int kpdi_nelder_mead_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0, const double *lower,
+                              const double *upper, double xatol, double fatol, int maxiter, int maxfev,
+                              double *result) {
+  if (!c || !x0 || !result) return fail(KPDI_EINVAL, "NULL argument");
+  if (nvar < 1 || nvar > 6) return fail(KPDI_EINVAL, "nvar must be within 1..6");
+  if ((lower == nullptr) != (upper == nullptr)) return fail(KPDI_EINVAL, "give both bounds or neither");
+  int rc = use_device(c);
+  if (rc) return rc;
+  SelftestIn in;
+  rc = selftest_upload(c, nvar, x0, lower, upper, 3 + nvar, &in);
+  if (rc) return rc;
+  int it, fev;
+  resolve_budget(nvar, maxiter, maxfev, &it, &fev);
+  HIPCHK(kpdi::launch_nelder_mead_selftest(kind, nvar, in.x, in.lo, in.hi, xatol, fatol, it, fev,
+                                           c->ref_out.as<double>(), c->stream));
+  return selftest_download(c, result, 3 + nvar);
+}
+
+int kpdi_refine_solve_powell(kpdi_ctx *c, int mode, int64_t n_patterns, int n_starts, const double *x0,
+                             const double *fixed, const double *lower, const double *upper, double xtol, double ftol,
+                             int maxiter, int maxfev, double *results, int64_t trace_job, double *trace,
+                             int trace_capacity) {
+  // the budget goes through as given: Powell's rule (N * 1000 each, or the other unlimited) resolves it in powell.h
+  static const RefineSolver powell = {powell_check_bounds,
+                                      [](int, int maxiter, int maxfev, int *it, int *fev) {
+                                        *it = maxiter;
+                                        *fev = maxfev;
+                                      },
+                                      kpdi::launch_refine_solve_powell};
+  return refine_solve(c, powell, mode, n_patterns, n_starts, x0, fixed, lower, upper, xtol, ftol, maxiter, maxfev, results,
+                      trace_job, trace, trace_capacity);
 }
 
 int kpdi_powell_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0, const double *lower, const double *upper,
@@ -507,19 +505,12 @@ int kpdi_powell_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0, cons
   if (lower && (rc = powell_check_bounds(lower, upper, (size_t)nvar))) return rc;
   rc = use_device(c);
   if (rc) return rc;
-  HIPCHK(c->ref_in.reserve((size_t)(3 * nvar + 1) * sizeof(double)));
-  HIPCHK(c->ref_out.reserve((size_t)(4 + nvar) * sizeof(double)));
-  double *d_x = c->ref_in.as<double>(), *d_lo = d_x + nvar, *d_hi = d_lo + nvar;
-  HIPCHK(hipMemcpyAsync(d_x, x0, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (lower) {
-    HIPCHK(hipMemcpyAsync(d_lo, lower, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_hi, upper, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  }
-  HIPCHK(kpdi::launch_powell_selftest(kind, nvar, d_x, lower ? d_lo : nullptr, lower ? d_hi : nullptr, xtol, ftol,
-                                      maxiter, maxfev, c->ref_out.as<double>(), c->stream));
-  HIPCHK(hipMemcpyAsync(result, c->ref_out.p, (size_t)(4 + nvar) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return KPDI_OK;
+  SelftestIn in;
+  rc = selftest_upload(c, nvar, x0, lower, upper, 4 + nvar, &in);
+  if (rc) return rc;
+  HIPCHK(kpdi::launch_powell_selftest(kind, nvar, in.x, in.lo, in.hi, xtol, ftol, maxiter, maxfev,
+                                      c->ref_out.as<double>(), c->stream));
+  return selftest_download(c, result, 4 + nvar);
 }
 
 // ---- the merge and fill kernels on caller-made lists (tests/test_gpu_merge.py) ------------------------------------

@@ -540,19 +540,16 @@ def _run_refinement(mode, n, starts, x0, fixed, lower, upper, pats, signal_mask,
         c.set_master_pattern(*_master_pattern_data(master_pattern, energy))
         # rescale exactly when the patterns are float32 (_refinement.py:956)
         c.refine_set_patterns(pats[part], signal_mask, pats.dtype == np.float32, detector.detector_to_sample)
+        block = [a if a is None else a[part] for a in (x0, fixed, lower, upper)]
         if host is None:  # the whole simplex search on the device
-            return c.refine_solve(MODES[mode], x0[part], None if fixed is None else fixed[part],
-                                  None if lower is None else lower[part], None if upper is None else upper[part],
-                                  nm["xatol"], nm["fatol"], nm["maxiter"] or 0, nm["maxfev"] or 0)
+            return c.refine_solve(MODES[mode], *block, nm["xatol"], nm["fatol"], nm["maxiter"] or 0, nm["maxfev"] or 0)
         powell = _device_powell_options(host)
         if powell is not None and os.environ.get("KPDI_REFINE_POWELL", "").lower() != "host":
             # SciPy's Powell on the device: one launch, no objective call from the host
-            return c.refine_solve_powell(MODES[mode], x0[part], None if fixed is None else fixed[part],
-                                         None if lower is None else lower[part], None if upper is None else upper[part],
-                                         powell["xtol"], powell["ftol"], powell["maxiter"] or 0, powell["maxfev"] or 0)
+            return c.refine_solve_powell(MODES[mode], *block, powell["xtol"], powell["ftol"], powell["maxiter"] or 0,
+                                         powell["maxfev"] or 0)
         # the reference's optimiser on the host, the objective on the device
-        return _host_solve(c, MODES[mode], host, x0[part], None if fixed is None else fixed[part],
-                           None if lower is None else lower[part], None if upper is None else upper[part])
+        return _host_solve(c, MODES[mode], host, *block)
 
     try:
         t0 = time.time()

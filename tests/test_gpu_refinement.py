@@ -218,6 +218,50 @@ def test_refine_pc_and_orientation_pc(ctx, g, g115):
     assert np.all(1 - start < got[:, 0])
 
 
+@pytest.mark.parametrize("mode", ["ori", "pc", "ori_pc"])
+@pytest.mark.parametrize("solver", ["nelder_mead", "powell"])
+def test_a_batch_equals_its_jobs_solved_alone(ctx, g, solver, mode):
+    """Job (pattern p, start s) of a batch reads its own rows of x0, fixed, lower and upper: every result row of a
+    batch of 3 patterns x 2 starts, and Powell's trace of job 3, equal bit for bit what that job gives when it is
+    solved alone.  Both solvers are deterministic per job (one thread's simplex, or uniform straight-line code,
+    over a fixed-order reduction), so no tolerance is involved."""
+    from kikuchipy_amd import _lib
+
+    pats, om = g["patterns"].reshape(-1, 60, 60)[:3], g["om_detector_to_sample"]
+    deg = np.deg2rad(1.0)
+    # the second start of a pattern lies 3 degrees / 0.01 in PC from the first
+    eu = np.stack([g["eu0"][:3], g["eu0"][:3] + 3 * deg], axis=1)
+    pc = np.stack([g["pc0"][:3], g["pc0"][:3] + 0.01], axis=1)
+    if mode == "ori":
+        code, x0, fixed, unit = _lib.REFINE_ORI, eu, pc, [deg] * 3
+    elif mode == "pc":
+        quats = np.array([ko.rotation_from_euler(*e) for e in eu.reshape(-1, 3)]).reshape(3, 2, 4)
+        code, x0, fixed, unit = _lib.REFINE_PC, pc, quats, [0.01] * 3
+    else:
+        code, x0, fixed, unit = _lib.REFINE_ORI_PC, np.concatenate([eu, pc], axis=2), None, [deg] * 3 + [0.01] * 3
+    # bounds of their own for every job: x0 -+ (0.5 + 0.25 job) degrees, or hundredths in PC
+    half = (0.5 + 0.25 * np.arange(6)).reshape(3, 2, 1) * np.array(unit)
+    lower, upper = x0 - half, x0 + half
+
+    def solve(where, trace_job=None):
+        args = [a if a is None else a[where] for a in (x0, fixed, lower, upper)]
+        if solver == "nelder_mead":
+            return ctx.refine_solve(code, *args, maxfev=40), None, None
+        return ctx.refine_solve_powell(code, *args, maxfev=60, trace_job=trace_job, trace_capacity=128)
+
+    ctx.refine_set_patterns(pats, None, False, om)
+    batch, batch_trace, batch_total = solve(slice(None), trace_job=3)
+    assert batch.shape == (3, 2, 3 + x0.shape[2]) and np.all(batch[:, :, 1] > 0)
+    for p in range(3):
+        ctx.refine_set_patterns(pats[p:p + 1], None, False, om)
+        for s in range(2):
+            alone, trace, total = solve((slice(p, p + 1), slice(s, s + 1)), trace_job=0)
+            assert np.array_equal(alone[0, 0], batch[p, s]), (p, s, alone[0, 0], batch[p, s])
+            if solver == "powell" and 2 * p + s == 3:
+                assert total == batch_total > 0 and len(trace) == min(total, 128)
+                assert np.array_equal(trace, batch_trace)
+
+
 def test_error_paths(g):
     from kikuchipy_amd import _lib
 
