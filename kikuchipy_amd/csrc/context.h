@@ -1,8 +1,10 @@
-// context.h - what the host translation units of libkpdi.so share: the context (one GPU, one stream), its buffers, the
-// error convention, and the internal entry points between api.hip (life cycle, set-up, pre-processing, counters),
-// sweep.hip (preparation + match + merge of a dictionary chunk, uploads, resident chunks), exact64.hip (float64
-// arithmetic), finalize.hip (hand-over of the result, communicators, hooks of kpdi_group) and extras.hip (dictionary
-// generation, refinement, orientation similarity map).  Nothing here is part of the C ABI (include/kpdi.h).
+// context.h - what the host translation units of libkpdi.so share: the context (one GPU, one stream), its buffers,
+// events and streams, the error convention, and the internal entry points between api.hip (life cycle, the problem and
+// the experimental set, device buffers, counters), pattern_ops.hip (every op on the resident experimental patterns),
+// simulation_ops.hip (kinematical master pattern, geometrical simulations), sweep.hip (preparation + match + merge of a
+// dictionary chunk, uploads, resident chunks), exact64.hip (float64 arithmetic), finalize.hip (hand-over of the result,
+// communicators, hooks of kpdi_group) and extras.hip (dictionary generation, refinement, orientation similarity map).
+// Nothing here is part of the C ABI (include/kpdi.h).
 //
 // What one context holds (all in the HBM of ONE MI355X):
 //   raw experimental patterns (m_all x npix, caller's dtype)      - pre-processed in place
@@ -117,6 +119,29 @@ struct PinBuf {
   }
 };
 
+// a HIP event created on first use (ensure) and destroyed with its owner (move-only); reads as the raw handle
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event &&o) noexcept : e(std::exchange(o.e, nullptr)) {}
+  Event &operator=(Event &&o) noexcept { return std::swap(e, o.e), *this; }
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  hipError_t ensure(unsigned flags = hipEventDisableTiming) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+  operator hipEvent_t() const { return e; }
+};
+using EventPairs = std::vector<std::pair<Event, Event>>;  // timed regions waiting for kpdi_get_counters
+
+// the same for a non-blocking HIP stream; whoever lets one go synchronises it first (kpdi_destroy)
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(Stream &&o) noexcept : s(std::exchange(o.s, nullptr)) {}
+  Stream &operator=(Stream &&o) noexcept { return std::swap(s, o.s), *this; }
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+  hipError_t ensure() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+  operator hipStream_t() const { return s; }
+};
+
 struct Rccl {
   void *lib = nullptr;
   decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
@@ -184,7 +209,8 @@ extern Rccl g_rccl;  // (finalize.hip)
 struct kpdi_ctx {
   int device = 0;
   int n_cu = 256;
-  hipStream_t stream = nullptr;
+  // declared before every buffer and event, so destroyed after them: nothing below outlives the stream it was used on
+  kpdi::Stream stream;
   kpdi::Switches sw;
 
   // problem
@@ -250,9 +276,9 @@ struct kpdi_ctx {
     // sweep in front of it had finished, and the uploads of a chunked call ran after its sweeps instead of beside them).
     kpdi::DevBuf raw_b;
     int cur = 0;                                        // 0: `raw` is being filled, 1: `raw_b`
-    hipEvent_t consumed[2] = {nullptr, nullptr};        // behind the preparation kernel that read buffer i (compute stream)
+    kpdi::Event consumed[2];                            // behind the preparation kernel that read buffer i (compute stream)
     bool consumed_set[2] = {false, false};
-    hipEvent_t filled = nullptr;                        // behind the last upload into the current buffer (copy stream)
+    kpdi::Event filled;                                 // behind the last upload into the current buffer (copy stream)
     bool filled_pending = false;                        // ... which the next flush has to wait for
     kpdi::DevBuf &buf() { return cur ? raw_b : raw; }
     int dtype = -1;
@@ -266,11 +292,11 @@ struct kpdi_ctx {
   // host-pointer pushes are cut into pieces whose upload (copy stream) overlaps the sweep of
   // the previous piece (compute stream): two staging buffers, events for hand-over
   kpdi::DevBuf stage[2];
-  hipStream_t stream2 = nullptr;  // second compute stream of multi-launch sweeps
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipStream_t copy_stream = nullptr;
+  kpdi::Stream stream2;  // second compute stream of multi-launch sweeps
+  kpdi::Event ev_fork, ev_join;
+  kpdi::Stream copy_stream;
   int stage_next = 0;
-  hipEvent_t stage_filled[2] = {nullptr, nullptr}, stage_free[2] = {nullptr, nullptr};
+  kpdi::Event stage_filled[2], stage_free[2];
 
   // top-k state
   kpdi::DevBuf part_s, part_i;       // partial lists of one match launch
@@ -299,7 +325,7 @@ struct kpdi_ctx {
     int gemm_rows = 0;  // float32 form of match16.hip: dictionary rows behind the whole rounds that tailgemm.hip takes (0 = none)
   } preplan;
   bool final_valid = false;       // `final_idx` points at the lists kpdi_finalize handed out last
-  const int *final_idx = nullptr;
+  const int *final_idx = nullptr;  // (a view of lists some buffer below owns)
   kpdi::DevBuf osm_idx, osm_out;
   kpdi::DevBuf gthr;                            // shared rejection bound of the match kernel
   int bound_key = -1;                     // plan the bound array was initialised for (-1: none)
@@ -320,22 +346,22 @@ struct kpdi_ctx {
     const void *raw = nullptr;
     int raw_dtype = 0, n_tiles = 0, nsplit = 0, rows_per_launch = 0, cap = 0, done = 0, extra = 0;
     int64_t n_chunk = 0, global_start = 0;
-    hipEvent_t ready = nullptr;
+    kpdi::Event ready;
     kpdi::PinBuf flag;  // int: patterns the last merge could not certify
   } pend64;
   // kpdi_finalize[_async]: two page-locked slots (scores + indices on their way to the caller) with an event each
   struct ResultSlot {
     kpdi::PinBuf pin;
-    hipEvent_t ready = nullptr;
+    kpdi::Event ready;
     size_t n = 0;
     bool pending = false;
   } slots[2];
   int next_slot = 0;
   // the copies of a result run on a stream of their own (the next map's kernels need not queue behind them); whoever
   // next WRITES the lists they read (the merge into the running best-k) waits for `result_copy` first
-  hipStream_t result_stream = nullptr;
-  hipEvent_t result_done = nullptr;   // compute stream: the lists of the result are final
-  hipEvent_t result_copy = nullptr;   // = slots[].ready of the copy still to be waited for, or nullptr
+  kpdi::Stream result_stream;
+  kpdi::Event result_done;            // compute stream: the lists of the result are final
+  hipEvent_t result_copy = nullptr;   // = slots[].ready of the copy still to be waited for, or nullptr (a view: the slot owns it)
   const int32_t *result_i32 = nullptr;    // the indices of the last kpdi_finalize in that buffer (kpdi_result_indices_i32)
   int64_t result_n = 0;
 
@@ -358,7 +384,7 @@ struct kpdi_ctx {
   // it is copied here on the host, 32 bytes per pattern) so that no push has to wait for the stream
   struct RotStage {
     kpdi::PinBuf pin;
-    hipEvent_t copied = nullptr;  // the upload out of this slot has run
+    kpdi::Event copied;  // the upload out of this slot has run
   } rot_stage[4];
   int rot_next = 0;
 
@@ -375,12 +401,12 @@ struct kpdi_ctx {
   // kpdi_comm_drop has run: a kpdi_comm_init that is still inside ncclCommInitRank on another thread (it hung, its caller
   // gave up) must not install its communicator when it finally returns
   std::atomic<bool> comm_dropped{false};
-  void *selftest_left[2] = {nullptr, nullptr};  // device buffers of a kpdi_comm_selftest that timed out, freed by kpdi_comm_drop
+  kpdi::DevBuf selftest_left[2];  // device buffers of a kpdi_comm_selftest that timed out, released by kpdi_comm_drop
   // in-process groups (group.hip): the members' lists peer-copied into gather_s / gather_i (gather64_*) of the ROOT
   // member instead of an RCCL all-gather; `p2p_ranks` > 0 = that many lists are waiting there for the next finalize
   int p2p_ranks = 0;
-  hipEvent_t lists_final = nullptr;  // this member's running lists are final (recorded on `stream`)
-  hipEvent_t peer_read = nullptr;    // root: the peer copies of the members' lists have run
+  kpdi::Event lists_final;  // this member's running lists are final (recorded on `stream`)
+  kpdi::Event peer_read;    // root: the peer copies of the members' lists have run
 
   // measurement: 0 off; 1 every phase bracketed by HIP events; 2 the match launches (and the all-gather) only - an event
   // record between two kernels costs ~6 us of idle GPU (profiles/r04_share_timeline.txt: 71 us per 3 ms step with level 1)
@@ -388,18 +414,23 @@ struct kpdi_ctx {
   bool timed(const void *list) const {
     return profiling == 1 || profiling == 3 || (profiling == 2 && (list == &ev_match || list == &ev_comm));
   }
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_match, ev_prep, ev_merge, ev_proj, ev_pre, ev_rescore, ev_comm, ev_fixed;
-  std::vector<hipEvent_t> ev_pool;
+  kpdi::EventPairs ev_match, ev_prep, ev_merge, ev_proj, ev_pre, ev_rescore, ev_comm, ev_fixed;
+  std::vector<kpdi::Event> ev_pool;  // timing events between uses
   kpdi_counters cnt{};
 
-  hipEvent_t get_event() {
+  void sync_streams() {  // every stream of the context that exists
+    for (kpdi::Stream *s : {&stream, &stream2, &copy_stream, &result_stream})
+      if (*s) (void)hipStreamSynchronize(*s);
+  }
+
+  kpdi::Event get_event() {
+    kpdi::Event e;
     if (!ev_pool.empty()) {
-      hipEvent_t e = ev_pool.back();
+      e = std::move(ev_pool.back());
       ev_pool.pop_back();
-      return e;
+    } else {
+      (void)e.ensure(hipEventDefault);
     }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
     return e;
   }
 };
@@ -408,9 +439,9 @@ namespace kpdi {
 
 struct ScopedTimer {
   kpdi_ctx *c;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> *list;
-  hipEvent_t a = nullptr, b = nullptr;
-  ScopedTimer(kpdi_ctx *ctx, std::vector<std::pair<hipEvent_t, hipEvent_t>> *l) : c(ctx), list(l) {
+  EventPairs *list;
+  Event a, b;
+  ScopedTimer(kpdi_ctx *ctx, EventPairs *l) : c(ctx), list(l) {
     if (c->timed(list)) {
       a = c->get_event();
       b = c->get_event();
@@ -420,7 +451,7 @@ struct ScopedTimer {
   ~ScopedTimer() {
     if (a) {
       (void)hipEventRecord(b, c->stream);
-      list->push_back({a, b});
+      list->emplace_back(std::move(a), std::move(b));
     }
   }
 };
@@ -429,7 +460,7 @@ struct ScopedTimer {
 // back in ev_pool on every path out, error returns included.  `on` = false takes no events and records nothing.
 struct EventPair {
   kpdi_ctx *c;
-  hipEvent_t a = nullptr, b = nullptr;
+  Event a, b;
   explicit EventPair(kpdi_ctx *ctx, bool on = true) : c(ctx) {
     if (on) {
       a = c->get_event();
@@ -439,8 +470,8 @@ struct EventPair {
   EventPair(const EventPair &) = delete;
   EventPair &operator=(const EventPair &) = delete;
   ~EventPair() {
-    if (a) c->ev_pool.push_back(a);
-    if (b) c->ev_pool.push_back(b);
+    if (a) c->ev_pool.push_back(std::move(a));
+    if (b) c->ev_pool.push_back(std::move(b));
   }
   bool on() const { return a && b; }
   hipError_t begin() { return on() ? hipEventRecord(a, c->stream) : hipSuccess; }
@@ -450,7 +481,7 @@ struct EventPair {
 };
 
 // ---- api.hip
-int drain_events(kpdi_ctx *c, std::vector<std::pair<hipEvent_t, hipEvent_t>> &list, double *ms_sum);
+int drain_events(kpdi_ctx *c, EventPairs &list, double *ms_sum);
 int wait_result_copy(kpdi_ctx *c);
 int flush_fills(kpdi_ctx *c);
 int queue_fill(kpdi_ctx *c, void *p, size_t words, unsigned value, int bound_used = -1);
@@ -460,6 +491,7 @@ void dtype_range(int dtype, float *omin, float *omax);
 // BEFORE it looks at the float64 certification of the previous chunk
 int use_device(kpdi_ctx *c, bool keep_pending = false);
 int results_to_host(kpdi_ctx *c, void *dst, const void *d_src, size_t bytes);
+void set_detector_layout(kpdi_ctx *c, int sy, int sx, bool have_mask, std::vector<int> keep);
 
 // what the prep kernels are told: `ndp` is evaluated in its centred form (prep.hip) except in the float16 form
 inline int prep_metric(const kpdi_ctx *c) { return c->metric == KPDI_METRIC_NDP && c->compute != KPDI_COMPUTE_F16 ? 2 : c->metric; }

@@ -129,7 +129,7 @@ int sweep_exact64(kpdi_ctx *c, const float *y, int64_t n_chunk, int64_t global_s
   HIPCHK(kpdi::launch_fill_topk(c->bound_s.as<float>(), c->bound_i.as<int>(), c->m_pad, c->stream));
   HIPCHK(kpdi::launch_fill_topk(c->loc_s.as<float>(), c->loc_i.as<int>(), (int64_t)n, c->stream));
   kpdi_ctx::Pending64 &q = c->pend64;
-  if (!q.ready) HIPCHK(hipEventCreateWithFlags(&q.ready, hipEventDisableTiming));
+  HIPCHK(q.ready.ensure());
   HIPCHK(q.flag.reserve(sizeof(int)));
   q.y = y;
   q.raw = raw;

@@ -21,7 +21,7 @@ int project_to_device(kpdi_ctx *c, const double *rotations, int64_t n, int resca
     if (st.copied) HIPCHK(hipEventSynchronize(st.copied));  // (four pushes ago: long done)
     if (st.pin.reserve(rot_bytes) == hipSuccess) {
       c->rot_next = (c->rot_next + 1) % 4;
-      if (!st.copied) HIPCHK(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+      HIPCHK(st.copied.ensure());
       memcpy(st.pin.p, rotations, rot_bytes);
       HIPCHK(hipMemcpyAsync(c->rot.p, st.pin.p, rot_bytes, hipMemcpyHostToDevice, c->stream));
       HIPCHK(hipEventRecord(st.copied, c->stream));

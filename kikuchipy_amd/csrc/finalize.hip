@@ -107,7 +107,7 @@ int finalize_enqueue(kpdi_ctx *c, int slot, bool own_stream) {
   const size_t n = (size_t)c->m * c->keep_n;
   kpdi_ctx::ResultSlot &rs = c->slots[slot];
   HIPCHK(rs.pin.reserve(n * (sizeof(float) + sizeof(int))));
-  if (!rs.ready) HIPCHK(hipEventCreateWithFlags(&rs.ready, hipEventDisableTiming));
+  HIPCHK(rs.ready.ensure());
   rs.n = n;
   rs.pending = true;
   c->result_i32 = nullptr;
@@ -119,8 +119,8 @@ int finalize_enqueue(kpdi_ctx *c, int slot, bool own_stream) {
     return KPDI_OK;
   }
   if (!c->result_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&c->result_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->result_done, hipEventDisableTiming));
+    HIPCHK(c->result_stream.ensure());
+    HIPCHK(c->result_done.ensure());
   }
   HIPCHK(hipEventRecord(c->result_done, c->stream));
   HIPCHK(hipStreamWaitEvent(c->result_stream, c->result_done, 0));
@@ -264,46 +264,33 @@ int kpdi_comm_selftest(kpdi_ctx *c, int64_t n_bytes, int timeout_ms) {
   if (rc) return rc;
   const size_t n = (size_t)n_bytes / 4;
   // buffers and event of the test: freed on EVERY way out - except after a time-out, where the collective may still touch
-  // the buffers: they pass to the context and go when kpdi_comm_drop has aborted the communicator
-  struct Scratch {
-    kpdi_ctx *c;
-    unsigned *send = nullptr, *recv = nullptr;
-    hipEvent_t done = nullptr;
-    bool keep = false;
-    ~Scratch() {
-      if (done) (void)hipEventDestroy(done);
-      if (keep) {
-        c->selftest_left[0] = send;
-        c->selftest_left[1] = recv;
-      } else {
-        if (send) (void)hipFree(send);
-        if (recv) (void)hipFree(recv);
-      }
-    }
-  } sc{c};
-  HIPCHK(hipMalloc(&sc.send, n * 4));
-  HIPCHK(hipMalloc(&sc.recv, n * 4 * c->nranks));
+  // the buffers: they pass to the context and go when kpdi_comm_drop has aborted the communicator (or with the context)
+  DevBuf send, recv;
+  Event done;
+  HIPCHK(send.reserve(n * 4));
+  HIPCHK(recv.reserve(n * 4 * c->nranks));
   std::vector<unsigned> h(n, 0x5eed0000u + (unsigned)c->rank);
-  HIPCHK(hipMemcpyAsync(sc.send, h.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(send.p, h.data(), n * 4, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  ncclResult_t r = g_rccl.AllGather(sc.send, sc.recv, n, ncclUint32, c->comm, c->stream);
+  ncclResult_t r = g_rccl.AllGather(send.p, recv.p, n, ncclUint32, c->comm, c->stream);
   if (r != ncclSuccess) return fail(KPDI_ECOMM, "RCCL all-gather (self-test): %s", g_rccl.GetErrorString(r));
-  HIPCHK(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(sc.done, c->stream));
+  HIPCHK(done.ensure());
+  HIPCHK(hipEventRecord(done, c->stream));
   const auto t0 = std::chrono::steady_clock::now();
   for (;;) {
-    const hipError_t q = hipEventQuery(sc.done);
+    const hipError_t q = hipEventQuery(done);
     if (q == hipSuccess) break;
     if (q != hipErrorNotReady) return fail(KPDI_EHIP, "self-test all-gather: %s", hipGetErrorString(q));
     if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(timeout_ms)) {
-      sc.keep = true;
+      c->selftest_left[0] = std::move(send);
+      c->selftest_left[1] = std::move(recv);
       return fail(KPDI_ETIMEOUT, "the first RCCL all-gather (%lld bytes per rank, %d ranks) did not complete within %d ms", (long long)n_bytes,
                   c->nranks, timeout_ms);
     }
     std::this_thread::sleep_for(std::chrono::microseconds(200));
   }
   std::vector<unsigned> got(n * c->nranks);
-  HIPCHK(hipMemcpy(got.data(), sc.recv, got.size() * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(got.data(), recv.p, got.size() * 4, hipMemcpyDeviceToHost));
   for (int j = 0; j < c->nranks; ++j)
     if (got[(size_t)j * n] != 0x5eed0000u + (unsigned)j || got[(size_t)j * n + n - 1] != 0x5eed0000u + (unsigned)j)
       return fail(KPDI_ECOMM, "self-test all-gather: the block of rank %d arrived damaged", j);
@@ -323,10 +310,8 @@ int kpdi_comm_drop(kpdi_ctx *c) {
     if (g_rccl.CommAbort) g_rccl.CommAbort(comm);
     else if (g_rccl.CommDestroy) g_rccl.CommDestroy(comm);
   }
-  for (void *&p : c->selftest_left) {  // (what a timed-out self-test left behind: nothing touches it any more)
-    if (p && use_device(c) == KPDI_OK) (void)hipFree(p);
-    p = nullptr;
-  }
+  for (DevBuf &b : c->selftest_left)  // (what a timed-out self-test left behind: nothing touches it any more)
+    if (b.p && use_device(c) == KPDI_OK) b.release();
   return KPDI_OK;
 }
 
@@ -460,7 +445,7 @@ int member_lists_ready(kpdi_ctx *c, ListsView *v) {
     v->scores = c->run_s[c->run_cur].p;
     v->idx = c->run_i[c->run_cur].as<int>();
   }
-  if (!c->lists_final) HIPCHK(hipEventCreateWithFlags(&c->lists_final, hipEventDisableTiming));
+  HIPCHK(c->lists_final.ensure());
   HIPCHK(hipEventRecord(c->lists_final, c->stream));
   v->ready = c->lists_final;
   return KPDI_OK;
@@ -494,7 +479,7 @@ int root_gather_p2p(kpdi_ctx *c, const ListsView *v, int n, hipEvent_t *read_don
                                 cnt * sizeof(int), c->stream));
     }
   }
-  if (!c->peer_read) HIPCHK(hipEventCreateWithFlags(&c->peer_read, hipEventDisableTiming));
+  HIPCHK(c->peer_read.ensure());
   HIPCHK(hipEventRecord(c->peer_read, c->stream));
   *read_done = c->peer_read;
   c->p2p_ranks = n;

@@ -1,0 +1,225 @@
+// simulation_ops.hip - host side of libkpdi.so, the simulations that need no resident patterns: the kinematical master
+// pattern (kinematical.hip) and the geometrical simulations (geometrical.hip), their tables formed on the host
+// (kinematical_plan.h, geometrical_plan.h).
+#include "context.h"
+
+using namespace kpdi;
+
+namespace {
+
+// How the single-launch simulations end: the launch between two events, its result to the host (synchronises: the host
+// tables have been read), the kernel's time into `counter`.  *launched = what `launch` returned: the caller words it.
+template <typename Launch>
+int launch_to_host(kpdi_ctx *c, Launch launch, void *dst, const void *d_src, size_t bytes, double *counter, hipError_t *launched) {
+  EventPair timer(c, c->profiling != 0);
+  HIPCHK(timer.begin());
+  *launched = launch();
+  (void)timer.end();
+  if (*launched != hipSuccess) return KPDI_OK;
+  const int rc = results_to_host(c, dst, d_src, bytes);
+  float ms = 0.f;
+  if (rc == KPDI_OK && timer.elapsed(&ms) == hipSuccess) *counter = ms;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kpdi_kinematical_master_pattern(kpdi_ctx *c, const double *unit_vectors, const double *theta, const double *intensity,
+                                    int64_t m, int half_size, int hemispheres, double *out) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!unit_vectors || !theta || !intensity || !out) return fail(KPDI_EINVAL, "unit_vectors, theta, intensity or out is NULL");
+  if (m < 1 || m > INT_MAX) return fail(KPDI_EINVAL, "%lld reflectors: at least one is needed", (long long)m);
+  if (half_size < 0 || half_size > kpdi::KIN_MAX_HALF_SIZE)
+    return fail(KPDI_EINVAL, "half_size %d: between 0 and %d", half_size, kpdi::KIN_MAX_HALF_SIZE);
+  if (!kpdi::kin_hemispheres(hemispheres))
+    return fail(KPDI_EINVAL, "hemispheres %d: 0 (upper), 1 (lower) or 2 (both)", hemispheres);
+  const kpdi::KinPlan plan = kpdi::kinematical_launch_plan(m, half_size, hemispheres);
+  if (!plan.ok) return fail(KPDI_EINVAL, "kinematical master pattern of half_size %d from %lld reflectors: no kernel takes this shape",
+                            half_size, (long long)m);
+  int rc = use_device(c);
+  if (rc) return rc;
+  // the pixel directions of the upper hemisphere and the reflector table, on the host with NumPy's operations
+  const int size = plan.size;
+  std::vector<double> axis((size_t)size), dirs((size_t)plan.pixels * 3), table((size_t)m * kpdi::KIN_ENTRY_DOUBLES);
+  for (int i = 0; i < size; ++i) axis[(size_t)i] = kpdi::kin_axis(i, size);
+  for (int r = 0; r < size; ++r)
+    for (int col = 0; col < size; ++col) kpdi::kin_direction(axis[(size_t)col], axis[(size_t)r], &dirs[((size_t)r * size + col) * 3]);
+  const double half_pi = 1.5707963267948966;  // np.pi / 2
+  for (int64_t i = 0; i < m; ++i) {
+    double *e = &table[(size_t)i * kpdi::KIN_ENTRY_DOUBLES];
+    e[0] = unit_vectors[3 * i];
+    e[1] = unit_vectors[3 * i + 1];
+    e[2] = unit_vectors[3 * i + 2];
+    e[3] = intensity[i];
+    e[6] = half_pi - theta[i];
+    kpdi::kin_screen(e[6], &e[4], &e[5]);
+    e[7] = 0.0;
+  }
+  const size_t out_bytes = (size_t)plan.hemispheres * (size_t)plan.pixels * sizeof(double);
+  HIPCHK(c->kin_dirs.reserve(dirs.size() * sizeof(double)));
+  HIPCHK(c->kin_table.reserve(table.size() * sizeof(double)));
+  HIPCHK(c->kin_out.reserve(out_bytes));
+  HIPCHK(hipMemcpyAsync(c->kin_dirs.p, dirs.data(), dirs.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->kin_table.p, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  kpdi::KinLaunch l{};
+  l.dirs = c->kin_dirs.as<double>();
+  l.table = c->kin_table.as<double>();
+  l.m = m;
+  l.half_size = half_size;
+  l.hemispheres = hemispheres;
+  l.out = c->kin_out.as<double>();
+  hipError_t e = hipSuccess;
+  rc = launch_to_host(c, [&] { return kpdi::launch_kinematical_master_pattern(l, c->stream); }, out, c->kin_out.p, out_bytes,
+                      &c->cnt.kinematical_ms, &e);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "kinematical master pattern kernel: %s (half_size %d, %lld reflectors)", hipGetErrorString(e), half_size,
+                (long long)m);
+  return rc;
+}
+
+// the per-point entries of a geometrical simulation, formed on the host (geometrical_plan.h) and uploaded to c->geo_points
+static int geometrical_points(kpdi_ctx *c, const double *rotations, int64_t n_points, const double *u_s, const double *a_star,
+                              const double *a_direct, const double *pcs, int64_t n_pc) {
+  std::vector<double> entries((size_t)n_points * kpdi::GEO_ENTRY_DOUBLES);
+  for (int64_t p = 0; p < n_points; ++p)
+    kpdi::geo_point_entry(rotations + 4 * p, u_s, a_star, a_direct, pcs + (n_pc == 1 ? 0 : p) * kpdi::GEO_PC_DOUBLES,
+                          &entries[(size_t)p * kpdi::GEO_ENTRY_DOUBLES]);
+  HIPCHK(c->geo_points.reserve(entries.size() * sizeof(double)));
+  HIPCHK(hipMemcpyAsync(c->geo_points.p, entries.data(), entries.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));  // `entries` leaves scope
+  return KPDI_OK;
+}
+
+static int geometrical_shape_refused(int64_t n_points, int64_t n_pc) {
+  if (n_points < 1 || n_points > INT_MAX) return fail(KPDI_EINVAL, "%lld map points: at least one is needed", (long long)n_points);
+  if (n_pc != 1 && n_pc != n_points)
+    return fail(KPDI_EINVAL, "%lld projection centres for %lld map points: one, or one per point", (long long)n_pc, (long long)n_points);
+  return KPDI_OK;
+}
+
+int kpdi_geometrical_visibility(kpdi_ctx *c, const double *vectors, int64_t m, int kind, const double *rotations,
+                                int64_t n_points, const double *u_s, const double *basis, const double *pcs, int64_t n_pc,
+                                uint8_t *flags) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!vectors || !rotations || !u_s || !basis || !pcs || !flags)
+    return fail(KPDI_EINVAL, "vectors, rotations, u_s, basis, pcs or flags is NULL");
+  if (m < 1 || m > INT_MAX) return fail(KPDI_EINVAL, "%lld features: at least one is needed", (long long)m);
+  int rc = geometrical_shape_refused(n_points, n_pc);
+  if (rc) return rc;
+  if (kind != KPDI_GEOMETRICAL_LINES && kind != KPDI_GEOMETRICAL_ZONE_AXES)
+    return fail(KPDI_EINVAL, "kind %d: 0 (lines) or 1 (zone axes)", kind);
+  const kpdi::GeoVisPlan plan = kpdi::geometrical_visibility_plan(m, n_points);
+  if (!plan.ok) return fail(KPDI_EINVAL, "visibility of %lld features at %lld map points: no kernel takes this shape", (long long)m,
+                            (long long)n_points);
+  rc = use_device(c);
+  if (rc) return rc;
+  rc = geometrical_points(c, rotations, n_points, u_s, kind == KPDI_GEOMETRICAL_LINES ? basis : nullptr,
+                          kind == KPDI_GEOMETRICAL_ZONE_AXES ? basis : nullptr, pcs, n_pc);
+  if (rc) return rc;
+  const size_t vec_bytes = (size_t)m * 3 * sizeof(double), partial_bytes = (size_t)plan.grid_y * (size_t)m;
+  HIPCHK(c->geo_vec.reserve(vec_bytes));
+  HIPCHK(c->geo_flags.reserve(partial_bytes + (size_t)m));
+  HIPCHK(hipMemcpyAsync(c->geo_vec.p, vectors, vec_bytes, hipMemcpyHostToDevice, c->stream));
+  kpdi::GeoVisLaunch l{};
+  l.vec = c->geo_vec.as<double>();
+  l.points = c->geo_points.as<double>();
+  l.m = m;
+  l.n_points = n_points;
+  l.kind = kind;
+  l.partial = c->geo_flags.as<uint8_t>();
+  l.flags = c->geo_flags.as<uint8_t>() + partial_bytes;
+  hipError_t e = hipSuccess;
+  rc = launch_to_host(c, [&] { return kpdi::launch_geometrical_visibility(l, c->stream); }, flags, l.flags, (size_t)m,
+                      &c->cnt.geometrical_visibility_ms, &e);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "geometrical visibility kernel: %s (%lld features, %lld map points)", hipGetErrorString(e), (long long)m,
+                (long long)n_points);
+  return rc;
+}
+
+int kpdi_geometrical_coordinates(kpdi_ctx *c, const double *hkl, int64_t m, const double *uvw, int64_t z,
+                                 const double *rotations, int64_t n_points, const double *u_s, const double *a_star,
+                                 const double *a_direct, const double *pcs, int64_t n_pc, double r_gnomonic,
+                                 uint8_t *line_in_pattern, double *line_gnomonic, double *line_pixel,
+                                 uint8_t *zone_in_pattern, double *zone_gnomonic, double *zone_pixel) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!hkl || !rotations || !u_s || !a_star || !a_direct || !pcs || !line_in_pattern || !line_gnomonic || !line_pixel)
+    return fail(KPDI_EINVAL, "hkl, rotations, u_s, a_star, a_direct, pcs or a line output is NULL");
+  if (m < 1 || m > INT_MAX) return fail(KPDI_EINVAL, "%lld lines: at least one is needed", (long long)m);
+  if (z < 0 || z > INT_MAX) return fail(KPDI_EINVAL, "%lld zone axes: none or more", (long long)z);
+  if (z > 0 && (!uvw || !zone_in_pattern || !zone_gnomonic || !zone_pixel))
+    return fail(KPDI_EINVAL, "uvw or a zone axis output is NULL");
+  int rc = geometrical_shape_refused(n_points, n_pc);
+  if (rc) return rc;
+  rc = use_device(c);
+  if (rc) return rc;
+  size_t free_bytes = 0, total_bytes = 0;
+  HIPCHK(hipMemGetInfo(&free_bytes, &total_bytes));
+  const kpdi::GeoCoordPlan plan = kpdi::geometrical_coord_plan(m, z, n_points, free_bytes / 4);
+  if (!plan.ok) return fail(KPDI_EINVAL, "coordinates of %lld lines and %lld zone axes at %lld map points: no kernel takes this shape",
+                            (long long)m, (long long)z, (long long)n_points);
+  rc = geometrical_points(c, rotations, n_points, u_s, a_star, a_direct, pcs, n_pc);
+  if (rc) return rc;
+  // the outputs of one pass, each at a multiple of 256 bytes
+  const size_t P = (size_t)plan.points, M = (size_t)m, Z = (size_t)z;
+  const size_t sizes[6] = {P * M * 4 * sizeof(double), P * M * 4 * sizeof(double), P * Z * 2 * sizeof(double),
+                           P * Z * 2 * sizeof(double), P * M, P * Z};
+  const auto pad256 = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+  size_t offset[6], total = 0;
+  for (int i = 0; i < 6; ++i) {
+    offset[i] = total;
+    total += pad256(sizes[i]);
+  }
+  const size_t hkl_bytes = M * 3 * sizeof(double), uvw_bytes = Z * 3 * sizeof(double);
+  const size_t uvw_at = pad256(hkl_bytes);  // uvw follows hkl in c->geo_vec
+  HIPCHK(c->geo_out.reserve(total));
+  HIPCHK(c->geo_vec.reserve(uvw_at + uvw_bytes));
+  char *vec = c->geo_vec.as<char>(), *out = c->geo_out.as<char>();
+  HIPCHK(hipMemcpyAsync(vec, hkl, hkl_bytes, hipMemcpyHostToDevice, c->stream));
+  if (z > 0) HIPCHK(hipMemcpyAsync(vec + uvw_at, uvw, uvw_bytes, hipMemcpyHostToDevice, c->stream));
+  kpdi::EventPair timer(c, c->profiling != 0);  // recorded again in every pass
+  double kernel_ms = 0.0;
+  hipError_t e = hipSuccess;
+  for (int64_t pass = 0; pass < plan.n_passes && e == hipSuccess && rc == KPDI_OK; ++pass) {
+    const int64_t p0 = pass * plan.points;
+    const size_t np = (size_t)(pass == plan.n_passes - 1 ? plan.tail : plan.points);
+    kpdi::GeoCoordLaunch l{};
+    l.hkl = reinterpret_cast<const double *>(vec);
+    l.uvw = z > 0 ? reinterpret_cast<const double *>(vec + uvw_at) : nullptr;
+    l.points = c->geo_points.as<double>() + (size_t)p0 * kpdi::GEO_ENTRY_DOUBLES;
+    l.m = m;
+    l.z = z;
+    l.points_in_pass = (int64_t)np;
+    l.r_gnomonic = r_gnomonic;
+    l.line_gn = reinterpret_cast<double *>(out + offset[0]);
+    l.line_px = reinterpret_cast<double *>(out + offset[1]);
+    l.zone_gn = z > 0 ? reinterpret_cast<double *>(out + offset[2]) : nullptr;
+    l.zone_px = z > 0 ? reinterpret_cast<double *>(out + offset[3]) : nullptr;
+    l.line_in = reinterpret_cast<uint8_t *>(out + offset[4]);
+    l.zone_in = z > 0 ? reinterpret_cast<uint8_t *>(out + offset[5]) : nullptr;
+    (void)timer.begin();
+    e = kpdi::launch_geometrical_coordinates(l, c->stream);
+    (void)timer.end();
+    if (e != hipSuccess) break;
+    const size_t at = (size_t)p0;
+    rc = kpdi::results_to_host(c, line_gnomonic + at * M * 4, l.line_gn, np * M * 4 * sizeof(double));
+    if (rc == KPDI_OK) rc = kpdi::results_to_host(c, line_pixel + at * M * 4, l.line_px, np * M * 4 * sizeof(double));
+    if (rc == KPDI_OK) rc = kpdi::results_to_host(c, line_in_pattern + at * M, l.line_in, np * M);
+    if (rc == KPDI_OK && z > 0) rc = kpdi::results_to_host(c, zone_gnomonic + at * Z * 2, l.zone_gn, np * Z * 2 * sizeof(double));
+    if (rc == KPDI_OK && z > 0) rc = kpdi::results_to_host(c, zone_pixel + at * Z * 2, l.zone_px, np * Z * 2 * sizeof(double));
+    if (rc == KPDI_OK && z > 0) rc = kpdi::results_to_host(c, zone_in_pattern + at * Z, l.zone_in, np * Z);
+    float ms = 0.f;
+    if (rc == KPDI_OK && timer.elapsed(&ms) == hipSuccess) kernel_ms += ms;
+  }
+  if (timer.on() && e == hipSuccess && rc == KPDI_OK) c->cnt.geometrical_coordinates_ms = kernel_ms;
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(c->stream);  // the host copies of hkl / uvw may still be in flight
+    return fail(KPDI_EHIP, "geometrical coordinates kernel: %s (%lld lines, %lld zone axes, %lld map points)", hipGetErrorString(e),
+                (long long)m, (long long)z, (long long)n_points);
+  }
+  return rc;
+}
+
+}  // extern "C"

@@ -260,9 +260,9 @@ int run_match(kpdi_ctx *c, const float *dict_y, int n_chunk, int n_tiles, int ns
     const bool tail2 = tail_tiles > 0 && c->sw.tail_stream2;  // the tail launch runs on the second stream
     if (two || tail2) {
       if (!c->stream2) {
-        HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+        HIPCHK(c->stream2.ensure());
+        HIPCHK(c->ev_fork.ensure());
+        HIPCHK(c->ev_join.ensure());
       }
       HIPCHK(hipEventRecord(c->ev_fork, c->stream));
       HIPCHK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
@@ -522,7 +522,7 @@ int flush_pending(kpdi_ctx *c, bool hold) {
   }
   const int b = p.cur;
   const void *raw = p.buf().p;
-  if (!p.consumed[b]) HIPCHK(hipEventCreateWithFlags(&p.consumed[b], hipEventDisableTiming));
+  HIPCHK(p.consumed[b].ensure());
   p.cur ^= 1;
   p.capacity = 0;  // (of the buffer that is filled next: pending_slot sizes it)
   p.consumed_set[b] = true;
@@ -766,6 +766,18 @@ int sweep_prepared(kpdi_ctx *c, const float *y, int64_t n_chunk, int64_t global_
 
 namespace {
 
+// the copy stream of host-pointer pushes and the events that hand its two staging buffers back and forth, on first use
+int ensure_copy_stream(kpdi_ctx *c) {
+  if (c->copy_stream) return KPDI_OK;
+  HIPCHK(c->copy_stream.ensure());
+  for (int b = 0; b < 2; ++b) {
+    HIPCHK(c->stage_filled[b].ensure());
+    HIPCHK(c->stage_free[b].ensure());
+    HIPCHK(hipEventRecord(c->stage_free[b], c->stream));
+  }
+  return KPDI_OK;
+}
+
 // Host chunk -> device in pieces of `per` patterns through two staging buffers on the copy
 // stream; `consume(d_piece, n, offset)` queues the work that reads a piece on the compute
 // stream.  The upload of piece j+1 overlaps whatever `consume` queued for piece j - pieces
@@ -774,19 +786,13 @@ namespace {
 template <typename F>
 int staged_upload(kpdi_ctx *c, const void *patterns, size_t row_bytes, const std::vector<int64_t> &pieces, F consume) {
   const int64_t per = *std::max_element(pieces.begin(), pieces.end());
-  if (!c->copy_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int b = 0; b < 2; ++b) {
-      HIPCHK(hipEventCreateWithFlags(&c->stage_filled[b], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->stage_free[b], hipEventDisableTiming));
-      HIPCHK(hipEventRecord(c->stage_free[b], c->stream));
-    }
-  }
+  int rc = ensure_copy_stream(c);
+  if (rc) return rc;
   for (int b = 0; b < 2; ++b)
     if (c->stage[b].cap < (size_t)per * row_bytes) {
       // growing a buffer frees it: everything queued on it must have finished (and a float64 chunk whose certification
       // has not been looked at yet may still want to read it)
-      int rc = resolve_exact64(c);
+      rc = resolve_exact64(c);
       if (rc) return rc;
       HIPCHK(hipStreamSynchronize(c->copy_stream));
       HIPCHK(hipStreamSynchronize(c->stream));
@@ -802,7 +808,7 @@ int staged_upload(kpdi_ctx *c, const void *patterns, size_t row_bytes, const std
     HIPCHK(hipEventRecord(c->stage_filled[b], c->copy_stream));
     c->cnt.h2d_bytes += (double)n * row_bytes;
     HIPCHK(hipStreamWaitEvent(c->stream, c->stage_filled[b], 0));
-    int rc = consume(c->stage[b].p, n, start);
+    rc = consume(c->stage[b].p, n, start);
     if (rc) return rc;
     HIPCHK(hipEventRecord(c->stage_free[b], c->stream));  // the prep kernel has consumed the piece
     start += n;
@@ -864,15 +870,9 @@ static int direct_upload(kpdi_ctx *c, const void *patterns, int dtype, size_t es
   rc = pending_slot(c, dtype, n_chunk, global_start, &slot);
   if (rc || !slot) return rc;
   kpdi_ctx::PendingChunks &p = c->pending;
-  if (!c->copy_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int b = 0; b < 2; ++b) {
-      HIPCHK(hipEventCreateWithFlags(&c->stage_filled[b], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->stage_free[b], hipEventDisableTiming));
-      HIPCHK(hipEventRecord(c->stage_free[b], c->stream));
-    }
-  }
-  if (!p.filled) HIPCHK(hipEventCreateWithFlags(&p.filled, hipEventDisableTiming));
+  rc = ensure_copy_stream(c);
+  if (rc) return rc;
+  HIPCHK(p.filled.ensure());
   // (the rows this buffer held before have been read by their preparation kernel)
   if (p.consumed_set[p.cur]) HIPCHK(hipStreamWaitEvent(c->copy_stream, p.consumed[p.cur], 0));
   HIPCHK(hipMemcpyAsync(slot, patterns, (size_t)n_chunk * c->npix * es, hipMemcpyHostToDevice, c->copy_stream));
