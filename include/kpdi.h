@@ -37,6 +37,12 @@
  *    ndp - all kept pixels zero;
  *    either metric - NaN or +-inf among the kept pixels, or a sum of squares that is not a positive finite float32
  *          (overflow; differences so small that their squares underflow).
+ *  The verdict is the float32 one in EVERY arithmetic: KPDI_COMPUTE_F64 rescores in double from the raw patterns but asks
+ *  of each pattern what the float32 screen asked (csrc/rescore.hip: f32_degenerate) - a float64 pattern whose contrast is
+ *  below float32 resolution (1 + 1e-10 u), or whose centred squares overflow (1e25 u) or underflow (1e-30 u) float32, is
+ *  degenerate there too, although its double arithmetic is ordinary.  Otherwise it would score 0 where the screen decides
+ *  what is rescored and a real score where a chunk is small enough to be rescored completely
+ *  (tests/test_gpu_rescore.py::test_the_float32_verdict_holds_whatever_the_chunk_size).
  *  The reference divides 0 by 0 there (similarity_metrics/_normalized_cross_correlation.py:228-233,
  *  _normalized_dot_product.py:181-194): the prepared row is NaN, every score of it is NaN, and Dask's topk ranks NaN
  *  FIRST (dask/array/chunk.py:167-258) - a degenerate dictionary pattern becomes every experimental pattern's best
@@ -620,6 +626,20 @@ int kpdi_merge64_selftest(kpdi_ctx *ctx, int m, int k, const double *run_s, cons
                           int64_t list_stride, const float *cand_s32, int s32_stride, int s32_col,
                           int enumerated_all, float max_diff, float eps_floor, double *out_s,
                           int32_t *out_i, int32_t *uncertified, int32_t *launch_error);
+/* The float64 rescoring kernel alone (csrc/rescore.hip: rescore_kernel; tests/test_gpu_rescore.py), every field of its
+ * launch the caller's.  exp_raw: m_all x npix of exp_dtype; row_map: m source rows, or NULL (then the first m rows).
+ * dict_raw: n_chunk x npix of dict_dtype, the dictionary patterns global_start .. global_start + n_chunk.  pix_map: k
+ * detector pixels, or NULL (then the first k).  cand_s / cand_i / cand_s64: m x cand_stride; the kernel rescores columns
+ * cand_offset .. cand_offset + n_cand; cand_s64 is uploaded as given and comes back whole.  max_diff_in: what the
+ * running maximum of |f32 score - f64 score| starts from (>= 0); *max_diff_out: what it ends at.  KPDI_EINVAL before
+ * anything reaches the GPU: a dtype code outside the nine, k < 1, a row_map entry outside [0, m_all), a pix_map entry
+ * outside [0, npix), cand_offset + n_cand > cand_stride, k > npix without a pix_map, m > m_all without a row_map. */
+int kpdi_rescore_selftest(kpdi_ctx *ctx, const void *exp_raw, int exp_dtype, int64_t m_all,
+                          const int32_t *row_map, int m, const void *dict_raw, int dict_dtype,
+                          int64_t n_chunk, int64_t global_start, const int32_t *pix_map, int k, int npix,
+                          int metric, const float *cand_s, const int32_t *cand_i, int cand_stride,
+                          int cand_offset, int n_cand, float max_diff_in, double *cand_s64,
+                          float *max_diff_out, int32_t *launch_error);
 /* The queued initialisations' one launch: n <= 8 ranges of words[i] 32-bit words at byte_offset[i] (a multiple of 4)
  * of one device buffer of buffer_words words, uploaded from and read back into `buffer`; value[i], or the shared
  * bound's pattern when bound_used[i] >= 0. */

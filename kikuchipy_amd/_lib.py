@@ -188,6 +188,8 @@ SIGNATURES = {
                                  _vp, _vp, _i, _vp, _vp]),
     "kpdi_merge64_selftest": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _i, _i, _i64, _i64, _vp, _i, _i, _i,
                                    C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
+    "kpdi_rescore_selftest": (_i, [_vp, _vp, _i, _i64, _vp, _i, _vp, _i, _i64, _i64, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i,
+                                   C.c_float, _vp, _vp, _vp]),
     "kpdi_fill_selftest": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i64]),
     "kpdi_orientation_similarity_map": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "kpdi_dtype_size": (_sz, [_i]),
@@ -998,6 +1000,40 @@ class Context:
                                        _ptr(out_s), _ptr(out_i), C.addressof(unc) if cert is not None else None,
                                        C.addressof(err)))
         return out_s, out_i, (unc.value if cert is not None else None), err.value
+
+    def rescore_selftest(self, exp, dic, metric, cand_s, cand_i, cand_s64, cand_offset=0, n_cand=None, global_start=0,
+                         row_map=None, pix_map=None, k=None, max_diff=0.0, exp_dtype=None, dict_dtype=None):
+        """rescore.hip's rescore_kernel alone (kpdi_rescore_selftest).  exp: (m_all, npix), dic: (n_chunk, npix), any of
+        the nine dtypes (exp_dtype / dict_dtype: a code to pass instead of the array's own); cand_s / cand_i / cand_s64:
+        (m, cand_stride), cand_s64 prefilled; k: kept pixels (default: all of pix_map, or npix).  Maps and extents go to
+        the library as given: it refuses what would read outside a buffer (and then cand_s64 is as it was).  Returns (cand_s64 after the launch,
+        max_diff after the launch as float32, launch error)."""
+        exp = np.ascontiguousarray(exp)
+        dic = np.ascontiguousarray(dic)
+        if exp.ndim != 2 or dic.ndim != 2 or exp.shape[1] != dic.shape[1]:
+            raise KpdiError("exp and dic must have shape (rows, npix) with the same npix")
+        cs = np.ascontiguousarray(cand_s, dtype=np.float32)
+        ci = np.ascontiguousarray(cand_i, dtype=np.int32)
+        out = np.require(cand_s64, np.float64, ["C", "W"])  # a writable C-ordered float64 array is filled in place
+        if cs.ndim != 2 or ci.shape != cs.shape or out.shape != cs.shape:
+            raise KpdiError("cand_s, cand_i and cand_s64 must share the shape (m, cand_stride)")
+        m, stride = cs.shape
+        rows = None if row_map is None else np.ascontiguousarray(row_map, dtype=np.int32)
+        pix = None if pix_map is None else np.ascontiguousarray(pix_map, dtype=np.int32)
+        if rows is not None and rows.size != m:
+            raise KpdiError("row_map must have m entries")
+        if k is None:
+            k = exp.shape[1] if pix is None else pix.size
+        if pix is not None and pix.size < k:
+            raise KpdiError("pix_map must have at least k entries")
+        md, err = C.c_float(0.0), C.c_int32(0)
+        check(self._f.rescore_selftest(self._h, _ptr(exp), dtype_code(exp.dtype) if exp_dtype is None else int(exp_dtype),
+                                       exp.shape[0], _ptr(rows), m, _ptr(dic),
+                                       dtype_code(dic.dtype) if dict_dtype is None else int(dict_dtype), dic.shape[0],
+                                       int(global_start), _ptr(pix), int(k), exp.shape[1], int(metric), _ptr(cs), _ptr(ci),
+                                       stride, int(cand_offset), stride - int(cand_offset) if n_cand is None else int(n_cand),
+                                       float(max_diff), _ptr(out), C.addressof(md), C.addressof(err)))
+        return out, np.float32(md.value), err.value
 
     def fill_selftest(self, buffer, ranges):
         """merge.hip's fill_segments_kernel alone (kpdi_fill_selftest).  buffer: uint32 words; ranges: up to eight

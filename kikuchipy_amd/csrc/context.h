@@ -336,6 +336,7 @@ struct kpdi_ctx {
   bool exact64 = false;
   kpdi::DevBuf run64_s, run64_i;                // running float64 best-k [m][keep_n]
   kpdi::DevBuf cand64;                          // float64 scores of the screened candidates [m][columns]
+  kpdi::DevBuf xdeg64;                          // [m]: 1 where rescoring found the experimental pattern degenerate
   kpdi::DevBuf cert64;                          // [0]: bits of max |f32 - f64| over the sweep; [1]: uncertified patterns of a merge
   kpdi::DevBuf gather64_s, gather64_i, final64_s, final64_i;
   kpdi::PinBuf pin_out;                         // float64 results on their way to the caller

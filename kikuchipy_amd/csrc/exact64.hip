@@ -45,6 +45,7 @@ static int exact64_passes(kpdi_ctx *c, int64_t target) {
     r.n_cand = kp;
     r.cand_s64 = c->cand64.as<double>();
     r.max_diff = cert;
+    r.exp_degenerate = c->xdeg64.as<int>();
     HIPCHK(kpdi::launch_rescore(r, c->stream));
     HIPCHK(hipMemsetAsync(cert + 1, 0, sizeof(unsigned), c->stream));
     kpdi::Merge64Launch g{};
@@ -75,6 +76,7 @@ static int exact64_passes(kpdi_ctx *c, int64_t target) {
     // where the k-th and the screened-last scores are closer than the worst case, no proof.
     g.eps_floor = c->sw.f64_statistical ? 1e-6f : (float)((c->k_kept + 2) * 0x1p-24 * 1.01) + 1e-6f;
     g.uncertified = (int *)(cert + 1);
+    g.exp_degenerate = c->xdeg64.as<int>();
     HIPCHK(kpdi::launch_merge64(g, c->stream));
     q.done += kp;
   }
@@ -124,6 +126,7 @@ int sweep_exact64(kpdi_ctx *c, const float *y, int64_t n_chunk, int64_t global_s
   HIPCHK(c->loc_s.reserve(n * sizeof(float)));
   HIPCHK(c->loc_i.reserve(n * sizeof(int)));
   HIPCHK(c->cand64.reserve(n * sizeof(double)));
+  HIPCHK(c->xdeg64.reserve((size_t)std::max(c->m, 1) * sizeof(int)));
   HIPCHK(c->bound_s.reserve((size_t)c->m_pad * sizeof(float)));
   HIPCHK(c->bound_i.reserve((size_t)c->m_pad * sizeof(int)));
   HIPCHK(kpdi::launch_fill_topk(c->bound_s.as<float>(), c->bound_i.as<int>(), c->m_pad, c->stream));

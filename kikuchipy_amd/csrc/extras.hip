@@ -650,6 +650,76 @@ int kpdi_merge64_selftest(kpdi_ctx *c, int m, int k, const double *run_s, const 
   return KPDI_OK;
 }
 
+// rescore_kernel on caller-made patterns, maps and candidate lists (tests/test_gpu_rescore.py): every field of
+// RescoreLaunch is the caller's; every index the kernel can form from them is checked here, so no launch reads or writes
+// outside the uploaded buffers (a candidate index outside the chunk is the kernel's own business: it scores -inf).
+int kpdi_rescore_selftest(kpdi_ctx *c, const void *exp_raw, int exp_dtype, int64_t m_all, const int32_t *row_map, int m,
+                          const void *dict_raw, int dict_dtype, int64_t n_chunk, int64_t global_start,
+                          const int32_t *pix_map, int k, int npix, int metric, const float *cand_s, const int32_t *cand_i,
+                          int cand_stride, int cand_offset, int n_cand, float max_diff_in, double *cand_s64,
+                          float *max_diff_out, int32_t *launch_error) {
+  if (!c || !exp_raw || !dict_raw || !cand_s || !cand_i || !cand_s64 || !max_diff_out || !launch_error)
+    return fail(KPDI_EINVAL, "NULL argument");
+  if (exp_dtype < KPDI_U8 || exp_dtype > KPDI_F16 || dict_dtype < KPDI_U8 || dict_dtype > KPDI_F16)
+    return fail(KPDI_EINVAL, "dtype codes %d / %d: not among the nine of kpdi.h", exp_dtype, dict_dtype);
+  if (metric != KPDI_METRIC_NCC && metric != KPDI_METRIC_NDP) return fail(KPDI_EINVAL, "unknown metric %d", metric);
+  if (k < 1) return fail(KPDI_EINVAL, "k must be at least 1");
+  if (npix < 1 || m < 1 || m_all < 1 || n_chunk < 1 || global_start < 0 || global_start + n_chunk > (int64_t)INT_MAX)
+    return fail(KPDI_EINVAL, "bad shape");
+  if (m_all * npix > (1 << 24) || n_chunk * npix > (1 << 24) || (int64_t)m * cand_stride > (1 << 24) || k > (1 << 24))
+    return fail(KPDI_EINVAL, "too large for a self-test");
+  if (!pix_map && k > npix) return fail(KPDI_EINVAL, "k = %d kept pixels of %d need a pix_map", k, npix);
+  if (!row_map && m > m_all) return fail(KPDI_EINVAL, "m = %d rows of %lld need a row_map", m, (long long)m_all);
+  if (cand_offset < 0 || n_cand < 1 || (int64_t)cand_offset + n_cand > cand_stride)
+    return fail(KPDI_EINVAL, "need cand_offset >= 0, n_cand >= 1 and cand_offset + n_cand <= cand_stride");
+  if (!(max_diff_in >= 0.f)) return fail(KPDI_EINVAL, "max_diff is kept as the bits of a non-negative float");
+  if (row_map)
+    for (int r = 0; r < m; ++r)
+      if (row_map[r] < 0 || row_map[r] >= m_all)
+        return fail(KPDI_EINVAL, "row_map[%d] = %d is outside [0, %lld)", r, row_map[r], (long long)m_all);
+  if (pix_map)
+    for (int i = 0; i < k; ++i)
+      if (pix_map[i] < 0 || pix_map[i] >= npix)
+        return fail(KPDI_EINVAL, "pix_map[%d] = %d is outside [0, %d)", i, pix_map[i], npix);
+  int rc = use_device(c);
+  if (rc) return rc;
+  Upload ue, ud, ur, up, us, ui, uo, um;
+  const size_t n_cand_all = (size_t)m * cand_stride;
+  HIPCHK(ue.put(exp_raw, (size_t)m_all * npix * kpdi_dtype_size(exp_dtype), c->stream));
+  HIPCHK(ud.put(dict_raw, (size_t)n_chunk * npix * kpdi_dtype_size(dict_dtype), c->stream));
+  if (row_map) HIPCHK(ur.put(row_map, (size_t)m * sizeof(int), c->stream));
+  if (pix_map) HIPCHK(up.put(pix_map, (size_t)k * sizeof(int), c->stream));
+  HIPCHK(us.put(cand_s, n_cand_all * sizeof(float), c->stream));
+  HIPCHK(ui.put(cand_i, n_cand_all * sizeof(int), c->stream));
+  HIPCHK(uo.put(cand_s64, n_cand_all * sizeof(double), c->stream));
+  HIPCHK(um.put(&max_diff_in, sizeof(float), c->stream));
+  kpdi::RescoreLaunch r{};
+  r.exp_raw = ue.d.p;
+  r.exp_dtype = exp_dtype;
+  r.row_map = row_map ? ur.d.as<int>() : nullptr;
+  r.dict_raw = ud.d.p;
+  r.dict_dtype = dict_dtype;
+  r.n_chunk = n_chunk;
+  r.global_start = global_start;
+  r.pix_map = pix_map ? up.d.as<int>() : nullptr;
+  r.k = k;
+  r.npix = npix;
+  r.metric = metric;
+  r.m = m;
+  r.cand_s = us.d.as<float>();
+  r.cand_i = ui.d.as<int>();
+  r.cand_stride = cand_stride;
+  r.cand_offset = cand_offset;
+  r.n_cand = n_cand;
+  r.cand_s64 = uo.d.as<double>();
+  r.max_diff = um.d.as<unsigned>();
+  *launch_error = (int32_t)kpdi::launch_rescore(r, c->stream);
+  HIPCHK(hipMemcpyAsync(cand_s64, uo.d.p, n_cand_all * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(max_diff_out, um.d.p, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return KPDI_OK;
+}
+
 int kpdi_fill_selftest(kpdi_ctx *c, int n, const int64_t *words, const uint32_t *value, const int32_t *bound_used,
                        const int64_t *byte_offset, uint32_t *buffer, int64_t buffer_words) {
   if (!c || !words || !value || !bound_used || !byte_offset || !buffer) return fail(KPDI_EINVAL, "NULL argument");

@@ -230,6 +230,7 @@ struct RescoreLaunch {
   int cand_stride, cand_offset, n_cand;
   double *cand_s64;      // out, same layout as cand_s
   unsigned *max_diff;    // bits of the largest |f32 score - f64 score| seen (atomic max)
+  int *exp_degenerate;   // out [m], or nullptr: 1 where the experimental pattern is degenerate (every score of it is +0)
 };
 hipError_t launch_rescore(const RescoreLaunch &a, hipStream_t s);
 
@@ -250,6 +251,9 @@ struct Merge64Launch {
   const unsigned *max_diff;
   float eps_floor;
   int *uncertified;      // counter (atomic add)
+  // [m] from rescore_kernel, or nullptr: a degenerate experimental pattern scores exactly +0 against EVERY dictionary
+  // pattern in both arithmetics, so its best-k is the lowest indices - what the screen hands over - and needs no margin
+  const int *exp_degenerate;
 };
 hipError_t launch_merge64(const Merge64Launch &a, hipStream_t s);
 hipError_t launch_fill_topk64(double *scores, int *idx, int64_t n, hipStream_t s);

@@ -13,7 +13,9 @@
 // >= 1e-6); if the running k-th best f64 score exceeds that, no unscreened candidate can belong to the
 // top k.  Patterns that fail the test get further screening passes (api.hip); what is still uncertified
 // after those is counted and reported (kpdi_counters.uncertified_patterns) - it takes more than 100
-// dictionary patterns within eps of the k-th best.
+// dictionary patterns within eps of the k-th best.  A DEGENERATE experimental pattern (include/kpdi.h) ties with every
+// dictionary pattern at exactly +0 in both arithmetics: its best-k is the lowest indices, which is what the screen hands
+// over, so rescore_kernel flags it and merge64_kernel certifies it without a margin.
 //
 // Scores agree with a float64 evaluation of the reference's formula to ~1e-15 (summation order differs).
 #include "prep_device.h"
@@ -42,12 +44,26 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
+// A pattern is degenerate when the float32 screen says so (include/kpdi.h "Degenerate patterns": the verdict is taken
+// on the kept pixels cast to float32, whatever their dtype), read off what one pass in double leaves behind.  lo / hi:
+// the extremes of the kept pixels cast to float32 (the cast is monotone: the extremes of the doubles, cast); mean:
+// their mean (0 under `ndp`); norm2: the sum of squares the pattern is divided by the root of.  `ncc`: lo == hi is
+// the exact test for a constant pattern.  Either metric: squaring is monotone, so the float32 squares of the centred
+// pixels sum to more than zero exactly when the largest of them does not underflow, and they overflow when that one
+// or their sum does.  NaN pixels are skipped by fmin / fmax and arrive through norm2, +-inf through lo / hi.
+__device__ __forceinline__ bool f32_degenerate(float lo, float hi, double mean, double norm2, bool ncc) {
+  const float mf = (float)mean;
+  const float vmax = fmaxf(hi - mf, mf - lo);
+  return degenerate_pattern(vmax * vmax, lo, hi, ncc) || degenerate_pattern((float)norm2, 0.f, 1.f, false);
+}
+
 constexpr int RESCORE_THREADS = 256;
 
 // One workgroup per experimental pattern; wave w rescores candidates w, w + 4, ...
 __global__ __launch_bounds__(RESCORE_THREADS) void rescore_kernel(RescoreLaunch a) {
   __shared__ double red[RESCORE_THREADS / 64];
-  __shared__ double xstat[3];
+  __shared__ double res[RESCORE_THREADS / 64];
+  __shared__ float lim[2 * (RESCORE_THREADS / 64)];
   __shared__ float diff_red[RESCORE_THREADS / 64];
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t xrow = (size_t)(a.row_map ? a.row_map[m] : m) * a.npix;
@@ -61,35 +77,32 @@ __global__ __launch_bounds__(RESCORE_THREADS) void rescore_kernel(RescoreLaunch 
   __syncthreads();
   const double mx = centre ? ((red[0] + red[1]) + (red[2] + red[3])) / (double)a.k : 0.0;
   __syncthreads();
-  // (x0 = the first kept pixel: sum (x - x0)^2 is EXACTLY zero for a constant pattern and for no other - the exact
-  // test of include/kpdi.h "Degenerate patterns"; an all-zero pattern under `ndp` has sxx == 0)
-  const double x0 = raw_value(a.exp_raw, a.exp_dtype, xrow + (a.pix_map ? a.pix_map[0] : 0));
-  double q = 0.0, r1 = 0.0, qc = 0.0;
+  // (the extremes of the kept pixels: what the float32 screen's verdict needs, f32_degenerate above)
+  double q = 0.0, r1 = 0.0, xmin = INFINITY, xmax = -INFINITY;
   for (int i = tid; i < a.k; i += RESCORE_THREADS) {
     const double raw = raw_value(a.exp_raw, a.exp_dtype, xrow + (a.pix_map ? a.pix_map[i] : i));
     const double v = raw - mx;
     q += v * v;
     r1 += v;
-    qc += (raw - x0) * (raw - x0);
+    xmin = fmin(xmin, raw);
+    xmax = fmax(xmax, raw);
   }
   q = wave_sum_f64(q);
   r1 = wave_sum_f64(r1);
-  qc = wave_sum_f64(qc);
+  const float xlo_w = wave_min((float)xmin), xhi_w = wave_max((float)xmax);
   if (lane == 0) {
     red[wave] = q;
-    diff_red[wave] = 0.f;
+    res[wave] = r1;
+    lim[wave] = xlo_w;
+    lim[RESCORE_THREADS / 64 + wave] = xhi_w;
   }
   __syncthreads();
-  if (tid == 0) xstat[1] = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  if (lane == 0) red[wave] = r1;
-  __syncthreads();
-  if (tid == 0) xstat[2] = (red[0] + red[1]) + (red[2] + red[3]);  // sum of the centred pixels: ~1e-13, not 0
-  __syncthreads();
-  if (lane == 0) red[wave] = qc;
-  __syncthreads();
-  const bool x_constant = centre && !((red[0] + red[1]) + (red[2] + red[3]) > 0.0);  // (NaN: not > 0 -> degenerate)
-  const double sxx = xstat[1], sx_res = xstat[2];
+  const double sxx = (red[0] + red[1]) + (red[2] + red[3]);
+  const double sx_res = (res[0] + res[1]) + (res[2] + res[3]);  // sum of the centred pixels: ~1e-13, not 0
+  const float xlo = fminf(fminf(lim[0], lim[1]), fminf(lim[2], lim[3]));
+  const float xhi = fmaxf(fmaxf(lim[4], lim[5]), fmaxf(lim[6], lim[7]));
+  const bool x_degenerate = f32_degenerate(xlo, xhi, mx, sxx, centre);
+  if (tid == 0 && a.exp_degenerate) a.exp_degenerate[m] = x_degenerate;
   // ---- candidates: ONE pass over a dictionary row.  With y0 = its first kept pixel (a shift that keeps the
   // one-pass variance free of cancellation) and x' = x - mean(x):
   //   sum (y - my)^2 = sum (y - y0)^2 - (sum (y - y0))^2 / K
@@ -104,25 +117,30 @@ __global__ __launch_bounds__(RESCORE_THREADS) void rescore_kernel(RescoreLaunch 
     if (idx != INT_MAX && local >= 0 && local < a.n_chunk) {
       const size_t yrow = (size_t)local * a.npix;
       const double y0 = centre ? raw_value(a.dict_raw, a.dict_dtype, yrow + (a.pix_map ? a.pix_map[0] : 0)) : 0.0;
-      double s1 = 0.0, s2 = 0.0, sxy = 0.0;
+      double s1 = 0.0, s2 = 0.0, sxy = 0.0, ymin = INFINITY, ymax = -INFINITY;
       for (int i = lane; i < a.k; i += 64) {
         const int p = a.pix_map ? a.pix_map[i] : i;
         const double x = raw_value(a.exp_raw, a.exp_dtype, xrow + p) - mx;
-        const double y = raw_value(a.dict_raw, a.dict_dtype, yrow + p) - y0;
+        const double yraw = raw_value(a.dict_raw, a.dict_dtype, yrow + p);
+        const double y = yraw - y0;
         sxy += x * y;
         s1 += y;
         s2 += y * y;
+        ymin = fmin(ymin, yraw);
+        ymax = fmax(ymax, yraw);
       }
       sxy = wave_sum_f64(sxy);
       s1 = wave_sum_f64(s1);
       s2 = wave_sum_f64(s2);
+      const float ylo = wave_min((float)ymin), yhi = wave_max((float)ymax);
       const double syy = centre ? s2 - s1 * s1 / (double)a.k : s2;
       if (centre) sxy -= (s1 / (double)a.k) * sx_res;
       // degenerate patterns (zero variance / all zeros / NaN or inf in the data: include/kpdi.h) score exactly 0, as
-      // in the f32 path, which prepares them as all-zero rows; the reference divides 0 by 0 there
-      // (s2 = sum (y - y0)^2: exactly zero for a constant dictionary pattern, and only then)
-      const bool degenerate = x_constant || (centre && !(s2 > 0.0)) || degenerate_pattern(sxx, 0.0, 1.0, false) ||
-                              degenerate_pattern(syy, 0.0, 1.0, false);
+      // in the f32 path, which prepares them as all-zero rows; the reference divides 0 by 0 there.  The verdict is
+      // the float32 screen's, on both sides (f32_degenerate): were it taken on the doubles, a pattern that only
+      // float32 calls degenerate would score 0 where the screen ranks it and a real score where a small chunk is
+      // rescored completely - a result that depends on chunking
+      const bool degenerate = x_degenerate || f32_degenerate(ylo, yhi, centre ? y0 + s1 / (double)a.k : 0.0, syy, centre);
       score = degenerate ? 0.0 : sxy / (sqrt(sxx) * sqrt(syy));
       if (!(score == score)) score = 0.0;
       if (score > -INFINITY) worst = fmaxf(worst, fabsf((float)(score - (double)s32)));
@@ -186,7 +204,7 @@ __global__ __launch_bounds__(MERGE64_THREADS) void merge64_kernel(Merge64Launch 
     }
     // certification, by whoever holds the k-th best
     if (rank == a.k - 1 && a.uncertified) {
-      bool ok = a.enumerated_all != 0;
+      bool ok = a.enumerated_all != 0 || (a.exp_degenerate && a.exp_degenerate[m]);
       if (!ok) {
         const float last32 = a.cand_s32[(size_t)m * a.s32_stride + a.s32_col];
         const float eps = fmaxf(8.f * __uint_as_float(*a.max_diff), a.eps_floor);

@@ -360,6 +360,8 @@ def _run(experimental, dictionary, metric, keep_n, n_per_iteration, resident, di
             pass
     time_start = time.time()
     f64 = metric.effective_compute == "f64"
+    # (before the sweep: a chunk's verdict is counted when the next call looks at it, most of them long before finalize)
+    uncertified_before = _uncertified(ctx) if f64 else 0
     try:
         if resident is not None:
             ctx.sweep_held()
@@ -380,7 +382,6 @@ def _run(experimental, dictionary, metric, keep_n, n_per_iteration, resident, di
                 bar.update(1)
             elif callable(progress) and rank == 0:
                 progress(n_done, len(bounds))
-        uncertified_before = _uncertified(ctx) if f64 else 0
         scores, simulation_indices = ctx.finalize(keep_n)
     finally:
         if bar is not None:

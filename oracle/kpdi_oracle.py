@@ -64,6 +64,9 @@ def degenerate_rows(norm2, constant=None):
     of - not a positive finite number (all zeros, NaN / inf in the data); `constant` (n,) bool, `ncc` only: all kept
     pixels of the row are EQUAL (minimum == maximum, an exact test: no contrast floor - one pixel off by one count on a
     60 000-count background is an ordinary pattern, `_normalized_cross_correlation.py:228-233` correlates it)."""
+    # (taken in the dtype the oracle computes in.  The library takes the verdict on the float32 cast in EVERY arithmetic
+    # (include/kpdi.h): with dtype=float64 the two differ for patterns whose contrast is below float32 resolution or whose
+    # centred squares overflow / underflow float32 - tests/test_gpu_rescore.py carries that rule in its own reference)
     with np.errstate(invalid="ignore", over="ignore"):
         norm2 = np.asarray(norm2, dtype=np.float64)
         bad = ~((norm2 > 0) & (norm2 < np.inf))

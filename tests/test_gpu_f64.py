@@ -1,7 +1,9 @@
 """`dtype=float64` (reference: _similarity_metric.py:244-253, _normalized_cross_correlation.py:88-183 in
 float64): the f32 path screens candidates, csrc/rescore.hip rescores them in double from the raw patterns,
 keeps the best-k in double and certifies it.  Checked against the oracle evaluated in float64
-(oracle/kpdi_oracle.py with dtype=float64 = the reference's arithmetic): scores to 1e-12, indices exactly."""
+(oracle/kpdi_oracle.py with dtype=float64 = the reference's arithmetic): scores to 1e-12, indices exactly.
+The rescoring kernel's own arithmetic - every raw dtype, reduction length, window edge, max_diff, the degeneracy verdict -
+is tested on its own in tests/test_gpu_rescore.py."""
 import numpy as np
 import pytest
 
