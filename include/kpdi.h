@@ -357,6 +357,31 @@ int kpdi_decomposition_model(kpdi_ctx *ctx, const void *loadings, const void *fa
                              int mean_kind, int dtype_out);
 int kpdi_change_dtype(kpdi_ctx *ctx, int dtype_out);
 
+/* ---- selecting patterns, rows and columns (EBSD.inav / isig / crop / extract_grid, signals/ebsd.py:267-378; deepcopy) ----
+ * kpdi_select_patterns: out[i, r, c] = in[pattern_index[i], row0 + r * row_step, col0 + c * col_step] for i < n_out,
+ *   r < n_rows, c < n_cols, on the resident patterns of `src` (the six dtypes of kpdi_rescale_intensity), a byte-exact
+ *   copy AFTER the recorded background steps.  `pattern_index` is a host array of n_out entries in [0, m_all), in any order
+ *   and with repeats, or NULL for every pattern in order (n_out must then be m_all).
+ *   dst == src: the selection replaces the resident patterns; the problem's detector shape becomes (n_rows, n_cols);
+ *     prepared rows, the running best-k and the navigation mask are forgotten; metric, arithmetic and keep_n stay, and so
+ *     does a signal mask when the shape does not change.
+ *   dst != src (same device): `src` is left as it is, its recorded steps stay recorded (they run on dst's copy).  `dst`
+ *     receives the patterns and their dtype without a navigation mask, and, unless it already has a problem of the shape
+ *     (n_rows, n_cols), that shape with src's metric, arithmetic and keep_n and no signal mask.  With NULL, the whole
+ *     detector and steps of 1 this is a device-to-device copy of the set.
+ *   KPDI_EINVAL before anything is launched or freed (both resident sets stay as they were): no resident patterns in
+ *   `src`, n_out < 1, an index outside [0, m_all), a step < 1, rows or columns that leave the detector, contexts on
+ *   different devices, and - when the detector shape of `dst` would change - a signal mask set or dictionary chunks held
+ *   there.  Kernel: csrc/select.hip, its three paths: csrc/select_plan.h.
+ * kpdi_set_navigation_mask: `nav_mask` (m_all bytes, non-zero = the pattern is not matched; NULL: none) becomes the
+ *   navigation mask of the resident patterns, as if it had come with kpdi_set_experimental of the patterns as
+ *   kpdi_get_experimental returns them: recorded background steps run first, on their own (not fused into the
+ *   preparation of the next sweep), so the scores of that sweep have the bits of a sweep after such an upload; prepared
+ *   rows and the running best-k are forgotten. */
+int kpdi_select_patterns(kpdi_ctx *src, kpdi_ctx *dst, const int64_t *pattern_index, int64_t n_out, int row0, int row_step,
+                         int n_rows, int col0, int col_step, int n_cols);
+int kpdi_set_navigation_mask(kpdi_ctx *ctx, const uint8_t *nav_mask);
+
 /* ---- kinematical master pattern in the stereographic projection (KikuchiPatternSimulator.calculate_master_pattern,
  * simulations/kikuchi_pattern_simulator.py:162-199, get_pattern :685-700) ---------------------------------------------------
  * Independent of the resident patterns.  `unit_vectors` (m x 3), `theta` (m Bragg angles, rad) and `intensity` (m) are host

@@ -154,6 +154,8 @@ SIGNATURES = {
     "kpdi_decomposition_apply": (_i, [_vp, _i, _i, _vp, _i, _vp]),
     "kpdi_decomposition_model": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i]),
     "kpdi_change_dtype": (_i, [_vp, _i]),
+    "kpdi_select_patterns": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i]),
+    "kpdi_set_navigation_mask": (_i, [_vp, _vp]),
     "kpdi_kinematical_master_pattern": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
     "kpdi_geometrical_visibility": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "kpdi_geometrical_coordinates": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.c_double,
@@ -552,6 +554,32 @@ class Context:
         dt = np.dtype(dtype_out)
         check(self._f.change_dtype(self._h, dtype_code(dt)))
         self._exp_dtype = dt
+
+    def select_patterns(self, pattern_index=None, rows=None, cols=None, into=None):
+        """out[i, r, c] = in[pattern_index[i], rows[r], cols[c]] of the resident patterns (after the recorded background
+        steps), byte for byte.  `pattern_index`: integers in [0, m_all) or None (every pattern in order); `rows`, `cols`:
+        (first, step, count) or None (the whole axis).  `into` None: the selection replaces the resident patterns and the
+        problem takes its detector shape; another `Context` on this device: that one receives it and this one stays as
+        it is (include/kpdi.h, kpdi_select_patterns)."""
+        dst = self if into is None else into
+        sy, sx = getattr(self, "_detector", (0, 0))  # (nothing set yet: the library refuses the call)
+        r0, rs, nr = (0, 1, sy) if rows is None else (int(v) for v in rows)
+        c0, cs, nc = (0, 1, sx) if cols is None else (int(v) for v in cols)
+        idx = None if pattern_index is None else np.ascontiguousarray(pattern_index, dtype=np.int64).ravel()
+        n_out = int(getattr(self, "_exp_shape", (0,))[0]) if idx is None else int(idx.size)
+        check(self._f.select_patterns(self._h, dst._h, _ptr(idx), n_out, r0, rs, nr, c0, cs, nc))
+        if dst is not self and getattr(dst, "_detector", None) != (nr, nc):  # dst took src's problem with the new shape
+            dst._keep_n, dst._compute = self._keep_n, self._compute
+        dst._detector = (nr, nc)
+        dst._exp_shape, dst._exp_dtype = (n_out, nr, nc), self._exp_dtype
+
+    def set_navigation_mask(self, navigation_mask=None):
+        """The navigation mask (True = not matched; None: no mask) of the resident patterns, without a new upload; the
+        recorded background steps run first (include/kpdi.h, kpdi_set_navigation_mask)."""
+        nm = _mask_bytes(navigation_mask)
+        if nm is not None and nm.size != int(self._exp_shape[0]):
+            raise KpdiError(f"navigation mask has {nm.size} elements, there are {self._exp_shape[0]} patterns")
+        check(self._f.set_navigation_mask(self._h, _ptr(nm)))
 
     def decomposition_gram(self, centre=CENTRE_NONE):
         """The float64 Gram matrix of the centred resident patterns over their shorter side: (gram (side, side), the

@@ -104,26 +104,10 @@ int use_device(kpdi_ctx *c, bool keep_pending) {
   return KPDI_OK;
 }
 
-static int set_experimental_common(kpdi_ctx *c, const void *src, bool src_on_device, int dtype, int64_t m_all,
-                            const uint8_t *nav_mask) {
-  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
-  int rc = use_device(c);
-  if (rc) return rc;
-  if (!c->have_problem) return fail(KPDI_EINVAL, "kpdi_set_problem must be called before kpdi_set_experimental");
-  const size_t es = kpdi::dtype_size(dtype);
-  if (es == 0) return fail(KPDI_EINVAL, "unknown dtype %d", dtype);
-  if (m_all <= 0) return fail(KPDI_EINVAL, "need at least one experimental pattern");
-  if (!src) return fail(KPDI_EINVAL, "patterns pointer is NULL");
-  const size_t bytes = (size_t)m_all * c->npix * es;
-  HIPCHK(c->exp_raw.reserve(bytes));
-  HIPCHK(hipMemcpyAsync(c->exp_raw.p, src, bytes, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                        c->stream));
-  if (!src_on_device) c->cnt.h2d_bytes += (double)bytes;
-  c->exp_dtype = dtype;
-  c->m_all = m_all;
+// c->m_all patterns are (about to be) resident: `nav_mask` decides which of them are matched
+int set_navigation_mask(kpdi_ctx *c, const uint8_t *nav_mask) {
+  const int64_t m_all = c->m_all;
   c->have_nav_mask = nav_mask != nullptr;
-  c->pend = kpdi_ctx::PendingPre{};  // recorded steps belonged to the previous set
-  if (m_all >= (int64_t)INT_MAX) return fail(KPDI_EINVAL, "too many experimental patterns");
   if (nav_mask) {
     std::vector<int> rows, inv((size_t)m_all, -1);  // kept pattern -> source row; source row -> kept pattern or -1
     rows.reserve((size_t)m_all);
@@ -143,6 +127,30 @@ static int set_experimental_common(kpdi_ctx *c, const void *src, bool src_on_dev
     c->m = (int)m_all;
   }
   c->m_pad = kpdi::round_up(std::max(c->m, 1), kpdi::TILE_EXP);
+  return KPDI_OK;
+}
+
+static int set_experimental_common(kpdi_ctx *c, const void *src, bool src_on_device, int dtype, int64_t m_all,
+                            const uint8_t *nav_mask) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  int rc = use_device(c);
+  if (rc) return rc;
+  if (!c->have_problem) return fail(KPDI_EINVAL, "kpdi_set_problem must be called before kpdi_set_experimental");
+  const size_t es = kpdi::dtype_size(dtype);
+  if (es == 0) return fail(KPDI_EINVAL, "unknown dtype %d", dtype);
+  if (m_all <= 0) return fail(KPDI_EINVAL, "need at least one experimental pattern");
+  if (!src) return fail(KPDI_EINVAL, "patterns pointer is NULL");
+  const size_t bytes = (size_t)m_all * c->npix * es;
+  HIPCHK(c->exp_raw.reserve(bytes));
+  HIPCHK(hipMemcpyAsync(c->exp_raw.p, src, bytes, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                        c->stream));
+  if (!src_on_device) c->cnt.h2d_bytes += (double)bytes;
+  c->exp_dtype = dtype;
+  c->m_all = m_all;
+  c->pend = kpdi_ctx::PendingPre{};  // recorded steps belonged to the previous set
+  if (m_all >= (int64_t)INT_MAX) return fail(KPDI_EINVAL, "too many experimental patterns");
+  rc = set_navigation_mask(c, nav_mask);
+  if (rc) return rc;
   c->have_exp = true;
   c->exp_prepared = false;
   c->run_valid = false;

@@ -245,6 +245,8 @@ struct kpdi_ctx {
   // kpdi_*_intensity: the patterns in a new dtype, kpdi_average_neighbour_patterns: the averaged patterns (swapped with
   // exp_raw); range partials
   kpdi::DevBuf int_out, int_ws;
+  // kpdi_select_patterns: the caller's index list (the selected patterns go through int_out)
+  kpdi::DevBuf sel_idx;
   // kpdi_decomposition_*: the Gram matrix or a product, the means (and the partial sums of the mean pattern), and the
   // caller's basis / loadings / factors
   kpdi::DevBuf dec_out, dec_mean, dec_in, dec_in2;
@@ -493,6 +495,8 @@ void dtype_range(int dtype, float *omin, float *omax);
 int use_device(kpdi_ctx *c, bool keep_pending = false);
 int results_to_host(kpdi_ctx *c, void *dst, const void *d_src, size_t bytes);
 void set_detector_layout(kpdi_ctx *c, int sy, int sx, bool have_mask, std::vector<int> keep);
+// the navigation mask (m_all bytes, or nullptr: none) of the resident patterns: which of them are matched
+int set_navigation_mask(kpdi_ctx *c, const uint8_t *nav_mask);
 
 // what the prep kernels are told: `ndp` is evaluated in its centred form (prep.hip) except in the float16 form
 inline int prep_metric(const kpdi_ctx *c) { return c->metric == KPDI_METRIC_NDP && c->compute != KPDI_COMPUTE_F16 ? 2 : c->metric; }

@@ -8,6 +8,7 @@
 #include "clahe_plan.h"
 #include "neighbours_plan.h"
 #include "downsample_plan.h"
+#include "select_plan.h"
 #include "decomp_plan.h"
 #include "kinematical_plan.h"
 #include "geometrical_plan.h"
@@ -464,6 +465,17 @@ struct DsLaunch {
 // the plan launch_downsample follows (KPDI_DOWNSAMPLE_PATH=1, read at each call, forces path 1)
 DsPlan downsample_launch_plan(int dtype, int sy, int sx, int factor, int64_t n);
 hipError_t launch_downsample(const DsLaunch &a, hipStream_t s);
+
+// ---- selection of patterns, rows and columns (select.hip) --------------------------------
+struct SelLaunch {
+  const void *src;                 // m x sy x sx elements of `esize` bytes, device, only read
+  void *dst;                       // n_out x n_rows x n_cols elements, device; not `src`
+  const int64_t *index;            // [n_out] source pattern of every output pattern (each in [0, m)), device; nullptr: identity
+  int64_t n_out;
+  int esize, sy, sx;
+  int row0, row_step, n_rows, col0, col_step, n_cols;
+};
+hipError_t launch_select(const SelLaunch &a, hipStream_t s);  // the plan it follows: select_plan.h
 
 // ---- the dynamic background itself (preproc.hip) ---------------------------------------
 struct DbLaunch {

@@ -1,8 +1,8 @@
 // pattern_ops.hip - host side of libkpdi.so, the ops on the resident experimental patterns: background removal,
 // read-back, image quality, region sums, FFT filter, intensity rescaling / normalisation and range, adaptive histogram
-// equalization, the neighbour ops, downsampling, the dynamic background, decomposition and dtype changes - on top of the
-// kernels in preproc.hip, iq.hip, regionsum.hip, fftfilter.hip, intensity.hip, clahe.hip, neighbours.hip, downsample.hip
-// and decomp.hip.  Every op checks its arguments, then runs the recorded background steps (start_pattern_op).
+// equalization, the neighbour ops, downsampling, the dynamic background, decomposition, dtype changes and selections - on
+// top of the kernels in preproc.hip, iq.hip, regionsum.hip, fftfilter.hip, intensity.hip, clahe.hip, neighbours.hip,
+// downsample.hip, decomp.hip and select.hip.  Every op checks its arguments, then runs the recorded background steps (start_pattern_op).
 #include "context.h"
 
 using namespace kpdi;
@@ -824,6 +824,190 @@ int kpdi_change_dtype(kpdi_ctx *c, int dtype_out) {
   hipError_t e = kpdi::launch_change_dtype(c->exp_raw.p, c->exp_dtype, c->int_out.p, dtype_out, count, c->stream);
   if (e != hipSuccess) return fail(KPDI_EHIP, "dtype change kernel: %s (dtype %d -> %d)", hipGetErrorString(e), c->exp_dtype, dtype_out);
   kpdi::adopt_output(c, dtype_out);
+  return KPDI_OK;
+}
+
+}  // extern "C"
+
+namespace kpdi {
+
+// what kpdi_select_patterns was asked for, checked against the source detector
+struct SelRequest {
+  const int64_t *index;  // host, or nullptr (identity)
+  int64_t n_out;
+  int row0, row_step, n_rows, col0, col_step, n_cols;
+  bool moves(const kpdi_ctx *c) const {  // does anything but "every pattern, whole, in order"
+    return index || row0 || col0 || row_step != 1 || col_step != 1 || n_rows != c->sy || n_cols != c->sx;
+  }
+};
+
+// the selection kernel on c's stream, from `from` (patterns of sy x sx elements of `esize` bytes) into `to`; the index
+// list goes up first
+static int run_select(kpdi_ctx *c, const void *from, void *to, int esize, int sy, int sx, const SelRequest &r) {
+  kpdi::SelLaunch a{};
+  if (r.index) {
+    const size_t bytes = (size_t)r.n_out * sizeof(int64_t);
+    HIPCHK(c->sel_idx.reserve(bytes));
+    HIPCHK(hipMemcpyAsync(c->sel_idx.p, r.index, bytes, hipMemcpyHostToDevice, c->stream));
+    c->cnt.h2d_bytes += (double)bytes;
+    a.index = c->sel_idx.as<int64_t>();
+  }
+  a.src = from;
+  a.dst = to;
+  a.n_out = r.n_out;
+  a.esize = esize;
+  a.sy = sy;
+  a.sx = sx;
+  a.row0 = r.row0;
+  a.row_step = r.row_step;
+  a.n_rows = r.n_rows;
+  a.col0 = r.col0;
+  a.col_step = r.col_step;
+  a.n_cols = r.n_cols;
+  {
+    ScopedTimer t(c, &c->ev_pre);
+    hipError_t e = kpdi::launch_select(a, c->stream);
+    if (e != hipSuccess)
+      return fail(KPDI_EHIP, "selection kernel: %s (%d-byte elements, %dx%d -> %dx%d)", hipGetErrorString(e), esize, sy, sx,
+                  r.n_rows, r.n_cols);
+  }
+  if (r.index) HIPCHK(hipStreamSynchronize(c->stream));  // the caller's list is read
+  return KPDI_OK;
+}
+
+// c's resident patterns are now `n` patterns without a navigation mask
+static int adopt_selection(kpdi_ctx *c, int64_t n) {
+  c->m_all = n;
+  int rc = set_navigation_mask(c, nullptr);
+  if (rc) return rc;
+  patterns_changed(c);
+  return KPDI_OK;
+}
+
+// the selection replaces c's resident patterns: a gather cannot run in place, so it goes through int_out
+static int select_in_place(kpdi_ctx *c, const SelRequest &r) {
+  int rc = start_pattern_op(c);
+  if (rc) return rc;
+  if (r.moves(c)) {
+    const int es = (int)kpdi::dtype_size(c->exp_dtype);
+    HIPCHK(c->int_out.reserve((size_t)r.n_out * r.n_rows * r.n_cols * es));
+    rc = run_select(c, c->exp_raw.p, c->int_out.p, es, c->sy, c->sx, r);
+    if (rc) return rc;
+    std::swap(c->exp_raw, c->int_out);
+    if (r.n_rows != c->sy || r.n_cols != c->sx) kpdi::set_detector_layout(c, r.n_rows, r.n_cols, false, {});
+  }
+  return adopt_selection(c, r.n_out);
+}
+
+// the selection of src's patterns AS THEY ARE IN HBM (recorded steps not applied) becomes dst's resident set, on dst's
+// stream; src's stream is idle.  dst takes the selection's shape as its problem (metric, arithmetic and keep_n of src)
+// unless it already has a problem of that shape.
+static int select_into(kpdi_ctx *src, kpdi_ctx *dst, const SelRequest &r) {
+  dst->pend = kpdi_ctx::PendingPre{};  // recorded steps belonged to the previous set
+  if (!dst->have_problem || dst->sy != r.n_rows || dst->sx != r.n_cols) {
+    dst->have_exp = false;
+    int rc = kpdi_set_problem(dst, r.n_rows, r.n_cols, nullptr, src->metric, src->exact64 ? KPDI_COMPUTE_F64 : src->compute,
+                              src->keep_n);
+    if (rc) return rc;
+  }
+  const int es = (int)kpdi::dtype_size(src->exp_dtype);
+  HIPCHK(dst->exp_raw.reserve((size_t)r.n_out * r.n_rows * r.n_cols * es));
+  int rc = run_select(dst, src->exp_raw.p, dst->exp_raw.p, es, src->sy, src->sx, r);
+  if (rc) return rc;
+  dst->exp_dtype = src->exp_dtype;
+  dst->have_exp = true;
+  rc = adopt_selection(dst, r.n_out);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(dst->stream));  // src may change its patterns as soon as this returns
+  return KPDI_OK;
+}
+
+}  // namespace kpdi
+
+extern "C" {
+
+int kpdi_select_patterns(kpdi_ctx *src, kpdi_ctx *dst, const int64_t *pattern_index, int64_t n_out, int row0, int row_step,
+                         int n_rows, int col0, int col_step, int n_cols) {
+  if (!dst) return fail(KPDI_EINVAL, "dst is NULL");
+  int rc = kpdi::check_patterns(src, "a selection");
+  if (rc) return rc;
+  const int sy = src->sy, sx = src->sx;
+  if (n_out < 1 || n_out >= (int64_t)INT_MAX) return fail(KPDI_EINVAL, "a selection of %lld patterns", (long long)n_out);
+  if (row_step < 1 || col_step < 1) return fail(KPDI_EINVAL, "steps (%d, %d) must be >= 1", row_step, col_step);
+  if (!kpdi::sel_range_ok(row0, row_step, n_rows, sy))
+    return fail(KPDI_EINVAL, "%d rows from row %d in steps of %d leave the %d x %d detector", n_rows, row0, row_step, sy, sx);
+  if (!kpdi::sel_range_ok(col0, col_step, n_cols, sx))
+    return fail(KPDI_EINVAL, "%d columns from column %d in steps of %d leave the %d x %d detector", n_cols, col0, col_step, sy,
+                sx);
+  if (!pattern_index && n_out != src->m_all)
+    return fail(KPDI_EINVAL, "without an index list n_out = %lld must be the number of resident patterns, %lld",
+                (long long)n_out, (long long)src->m_all);
+  if (pattern_index)
+    for (int64_t i = 0; i < n_out; ++i)
+      if (pattern_index[i] < 0 || pattern_index[i] >= src->m_all)
+        return fail(KPDI_EINVAL, "pattern_index[%lld] = %lld is outside [0, %lld)", (long long)i, (long long)pattern_index[i],
+                    (long long)src->m_all);
+  const int es = (int)kpdi::dtype_size(src->exp_dtype);
+  if (kpdi::select_plan(es, sy, sx, n_out, row0, row_step, n_rows, col0, col_step, n_cols).path < 0)
+    return fail(KPDI_EINVAL, "selection from %d x %d patterns: no kernel path takes this shape", sy, sx);
+  if (dst != src && dst->device != src->device)
+    return fail(KPDI_EINVAL, "the contexts are on devices %d and %d: a selection stays on one device", src->device, dst->device);
+  const kpdi::SelRequest req{pattern_index, n_out, row0, row_step, n_rows, col0, col_step, n_cols};
+  // recorded steps run before the selection.  Into another context they run THERE, on a copy of the whole set (src keeps
+  // its patterns and its steps as they are), so dst passes through src's shape on its way
+  const bool via_copy = dst != src && (src->pend.st || src->pend.dy) && req.moves(src);
+  if (dst->have_problem) {
+    const bool reshaped = dst->sy != n_rows || dst->sx != n_cols || (via_copy && (dst->sy != sy || dst->sx != sx));
+    if (reshaped && dst->have_sig_mask)
+      return fail(KPDI_EINVAL, "a signal mask is set for the %d x %d detector: call kpdi_set_problem without it, select, then "
+                               "set the mask of the new shape", dst->sy, dst->sx);
+    if (reshaped && (!dst->held.empty() || dst->pending_hold.rows > 0))
+      return fail(KPDI_EINVAL, "dictionary chunks are held for the %d x %d detector: release them before selecting", dst->sy,
+                  dst->sx);
+  }
+  rc = use_device(src);
+  if (rc) return rc;
+  if (dst == src) return kpdi::select_in_place(src, req);
+  rc = use_device(dst);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(src->stream));  // dst's stream reads what src's wrote
+  if (!src->pend.st && !src->pend.dy) return kpdi::select_into(src, dst, req);
+  // every pattern, whole, with the recorded steps: they run when dst's patterns are next needed (or right below)
+  const kpdi::SelRequest all{nullptr, src->m_all, 0, 1, sy, 0, 1, sx};
+  // a dst that already has a problem of the selection's shape keeps its metric, arithmetic and keep_n (kpdi.h): the
+  // detour through src's shape below takes src's, so they are put back at the end (no signal mask can be lost: with
+  // one, a dst whose shape differs from src's was refused above)
+  const bool own_problem = via_copy && dst->have_problem && dst->sy == n_rows && dst->sx == n_cols && (sy != n_rows || sx != n_cols);
+  const int own_metric = dst->metric, own_compute = dst->exact64 ? KPDI_COMPUTE_F64 : dst->compute, own_keep_n = dst->keep_n;
+  rc = kpdi::select_into(src, dst, all);
+  if (rc) return rc;
+  dst->pend = src->pend;
+  if (src->pend.st) {
+    HIPCHK(dst->bg.reserve((size_t)src->npix * sizeof(float)));
+    HIPCHK(hipMemcpyAsync(dst->bg.p, src->bg.p, (size_t)src->npix * sizeof(float), hipMemcpyDeviceToDevice, dst->stream));
+  }
+  if (src->pend.dy) {
+    HIPCHK(dst->taps.reserve(src->taps.cap));
+    HIPCHK(hipMemcpyAsync(dst->taps.p, src->taps.p, src->taps.cap, hipMemcpyDeviceToDevice, dst->stream));
+  }
+  HIPCHK(hipStreamSynchronize(dst->stream));
+  if (!via_copy) return KPDI_OK;
+  rc = kpdi::select_in_place(dst, req);
+  if (rc || !own_problem) return rc;
+  return kpdi_set_problem(dst, n_rows, n_cols, nullptr, own_metric, own_compute, own_keep_n);  // (keeps the patterns)
+}
+
+int kpdi_set_navigation_mask(kpdi_ctx *c, const uint8_t *nav_mask) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!c->have_exp) return fail(KPDI_EINVAL, "kpdi_set_experimental has not been called");
+  // recorded background steps run now, on their own: the sweep that follows then prepares from the STORED patterns, as
+  // it does after an upload of processed patterns, with the same preparation kernel (the preparation fused into the
+  // background kernel sums a pattern in another order: float patterns would score differently in the last bits)
+  int rc = kpdi::start_pattern_op(c);
+  if (rc) return rc;
+  rc = kpdi::set_navigation_mask(c, nav_mask);
+  if (rc) return rc;
+  kpdi::patterns_changed(c);
   return KPDI_OK;
 }
 

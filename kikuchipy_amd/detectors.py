@@ -318,6 +318,29 @@ class EBSDDetector:
         """`(~detector.sample_to_detector).to_matrix()`: the transpose."""
         return np.ascontiguousarray(self.sample_to_detector.T)
 
+    def crop(self, extent):
+        """A new detector cropped to `extent` = (top, bottom, left, right) in pixels, its PC values updated
+        (detectors/_ebsd_detector.py:986-1032): the extent is clamped to the detector; it must be integers with
+        bottom > top and right > left after that.  (The reference builds the new detector without `twist`; here it is
+        carried over like the other angles.)"""
+        refusal = "Extent (top, bottom, left, right) must be integers and given so that bottom > top and right > left"
+        # one pass over the two axes: (first, end) of the extent on an axis of `size` pixels, cut to [0, size]
+        kept = []
+        for size, (first, end) in zip(self.shape, (extent[0:2], extent[2:4])):
+            if len(extent) != 4 or not (isinstance(first, int) and isinstance(end, int)):
+                raise ValueError(refusal)
+            first, end = (0 if first < 0 else first), (size if end > size else end)
+            if end <= first:
+                raise ValueError(refusal)
+            kept.append((first, end - first))
+        (top, rows), (left, cols) = kept
+        ny, nx = self.shape
+        pc = np.stack([(self._pc[..., 0] * nx - left) / cols,
+                       (self._pc[..., 1] * ny - top) / rows,
+                       self._pc[..., 2] * ny / rows], axis=-1)
+        return EBSDDetector((rows, cols), self.px_size, self._binning, self.tilt, self.azimuthal, self.twist,
+                            self.sample_tilt, pc, "bruker")
+
     def deepcopy(self):
         return EBSDDetector(self.shape, self.px_size, self._binning, self.tilt, self.azimuthal, self.twist,
                             self.sample_tilt, self._pc.copy(), "bruker")

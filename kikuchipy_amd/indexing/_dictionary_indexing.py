@@ -257,7 +257,11 @@ def dictionary_indexing(
         if dictionary_rotations is None:
             dictionary_rotations = resident.rotations
         phase_name = phase_name or resident.phase_name
-    experimental = experimental if _is_lazy(experimental) else np.asarray(experimental)
+    from kikuchipy_amd.pattern._pattern import ResidentPatterns
+
+    # (the patterns of a resident EBSD signal are matched where they are: similarity_metrics.prepare_experimental)
+    if not _is_lazy(experimental) and not isinstance(experimental, ResidentPatterns):
+        experimental = np.asarray(experimental)
     if experimental.ndim < 2 or experimental.ndim > 4:
         raise ValueError("experimental patterns must have 0, 1 or 2 navigation axes and 2 signal axes")
     if dictionary.ndim != 3:

@@ -473,18 +473,30 @@ class _HipMetric(SimilarityMetric):
                 "and the scores are returned as float64 values of it - within the parity contract of the "
                 "reference's float64 evaluation, not a float64 computation (compute=None or 'f64' is one)",
                 UserWarning, stacklevel=2)
-        if hasattr(patterns, "compute"):
-            patterns = patterns.compute()
-        patterns = np.asarray(patterns)
-        if patterns.ndim < 2:
-            raise ValueError("experimental patterns need at least the two detector axes")
-        sig_shape = patterns.shape[-2:]
-        n = self.n_experimental_patterns
-        if n is None:
-            n = max(int(np.prod(patterns.shape[:-2])), 1)
-        patterns = patterns.reshape((n,) + sig_shape)
-        self._set_problem(sig_shape, 1)
-        self._engine().set_experimental(patterns, self.navigation_mask)
+        from kikuchipy_amd.pattern._pattern import ResidentPatterns
+
+        if isinstance(patterns, ResidentPatterns):
+            # the patterns of a resident EBSD signal: already in this engine's HBM.  The problem takes the signal mask
+            # (which keeps them), the navigation mask is set beside them: nothing is uploaded
+            if self._engine() is not patterns.context:
+                raise ValueError("resident patterns are matched on the context that holds them: make the metric with "
+                                 "`context=signal.context`")
+            sig_shape = patterns.shape[-2:]
+            self._set_problem(sig_shape, 1)
+            self._engine().set_navigation_mask(self.navigation_mask)
+        else:
+            if hasattr(patterns, "compute"):
+                patterns = patterns.compute()
+            patterns = np.asarray(patterns)
+            if patterns.ndim < 2:
+                raise ValueError("experimental patterns need at least the two detector axes")
+            sig_shape = patterns.shape[-2:]
+            n = self.n_experimental_patterns
+            if n is None:
+                n = max(int(np.prod(patterns.shape[:-2])), 1)
+            patterns = patterns.reshape((n,) + sig_shape)
+            self._set_problem(sig_shape, 1)
+            self._engine().set_experimental(patterns, self.navigation_mask)
         self._engine_m = self._engine().n_experimental
         n_pix = int(np.prod(sig_shape))
         if self.signal_mask is not None:

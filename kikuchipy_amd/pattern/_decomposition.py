@@ -144,14 +144,14 @@ def decomposition_stack(patterns, output_dimension=None, centre=None, *, context
 def _decompose(patterns, checked, centre, context):
     """`decomposition_stack` after its checks (`checked`: what `check_decomposition` returned)."""
     code, m, c = checked
-    ctx = _pattern._context(context, 0)
+    ctx = patterns.context if isinstance(patterns, _pattern.ResidentPatterns) else _pattern._context(context, 0)
     try:
         _pattern._upload(ctx, patterns)
         gram, mean, transposed = ctx.decomposition_gram(code)
         factors, loadings, variance, ratio = results_from_gram(
             gram, transposed, lambda basis, t: ctx.decomposition_apply(basis, code, t), m, c)
     finally:
-        if context is None:
+        if context is None and not isinstance(patterns, _pattern.ResidentPatterns):
             ctx.close()
     return LearningResults(factors, loadings, variance, ratio, mean, centre, c, tuple(patterns.shape))
 
@@ -205,11 +205,13 @@ def decomposition_model_stack(patterns, learning_results, components=None, dtype
 def _model(patterns, checked, learning_results, dtype_out, context):
     """`decomposition_model_stack` after its checks (`checked`: what `check_model` returned)."""
     factors, loadings = checked
-    ctx = _pattern._context(context, 0)
+    ctx = patterns.context if isinstance(patterns, _pattern.ResidentPatterns) else _pattern._context(context, 0)
     try:
         _pattern._upload(ctx, patterns)
         ctx.decomposition_model(loadings, factors, learning_results.mean, CENTRES[learning_results.centre], dtype_out)
+        if isinstance(patterns, _pattern.ResidentPatterns):
+            return patterns.result()
         return ctx.get_experimental().reshape(patterns.shape)
     finally:
-        if context is None:
+        if context is None and not isinstance(patterns, _pattern.ResidentPatterns):
             ctx.close()

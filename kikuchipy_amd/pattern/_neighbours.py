@@ -69,13 +69,15 @@ def neighbour_row_blocks(ny, wy, n_members):
 
 def _as_map(patterns):
     """(flat (ny * nx, sy, sx), ny, nx, navigation shape) of (ny, nx, sy, sx) or (n, sy, sx) patterns."""
-    patterns = np.asarray(patterns)
+    patterns = _pattern.as_patterns(patterns)
     if patterns.ndim not in (3, 4):
         raise ValueError("Signal must have at least one navigation dimension")
     if patterns.dtype.type not in _pattern._SUPPORTED:
         raise ValueError(f"pattern dtype {patterns.dtype} is not supported by the GPU pre-processing kernels")
     nav = patterns.shape[:-2]
     ny, nx = (nav[0], 1) if len(nav) == 1 else nav
+    if isinstance(patterns, _pattern.ResidentPatterns):
+        return patterns.flat(), int(ny), int(nx), nav
     return np.ascontiguousarray(patterns).reshape((-1,) + patterns.shape[-2:]), int(ny), int(nx), nav
 
 
@@ -100,6 +102,9 @@ def _run(flat, ny, nx, wy, op, context, device, contexts):
 
         with ThreadPoolExecutor(len(blocks)) as pool:
             return join(list(pool.map(one, zip(contexts, blocks))))
+    if isinstance(flat, _pattern.ResidentPatterns):  # where they are, on their own context
+        _pattern._upload(flat.context if context is None else context, flat)
+        return join([op(flat.context, ny, 0, ny, 0)])
     ctx = contexts[0] if contexts else _pattern._context(context, device)
     try:
         _pattern._upload(ctx, flat)
@@ -117,23 +122,30 @@ def average_neighbour_patterns_stack(patterns, window="circular", window_shape=(
     with the reference's NumPy evaluation for integer-valued windows.  A window of shape (1,) or (1, 1) warns and
     returns a copy; a point whose window sum is 0 raises; a constant averaged pattern becomes 0 (integer dtypes) or NaN
     (float dtypes), as in `rescale_intensity`.  On a single `context` the averaged patterns stay resident."""
-    patterns = np.asarray(patterns)
+    patterns = _pattern.as_patterns(patterns)
     flat, ny, nx, nav = _as_map(patterns)
     win = averaging_window(window, window_shape, **kwargs)
     if win.shape in [(1,), (1, 1)]:
         warnings.warn(f"A window of shape {win.shape} was passed, no averaging is therefore performed")
-        return patterns.copy()
+        if not isinstance(patterns, _pattern.ResidentPatterns):
+            return patterns.copy()
+        if patterns.keep:
+            return patterns
+        return patterns.host()
     w = window_on_map(win, nav)
     sums = neighbour_window_sums(w, ny, nx)
     if not sums.all():
         q = np.argwhere(sums == 0)[0]
         raise ValueError(f"The window sum of map point {tuple(int(v) for v in q)} is 0: its average is undefined")
 
+    kept = isinstance(patterns, _pattern.ResidentPatterns) and patterns.keep
+
     def op(c, rows, row0, row1, lo):
         c.average_neighbour_patterns(rows, nx, w, sums[lo:lo + rows], row0, row1)
-        return c.get_experimental()[row0 * nx:row1 * nx]
+        return np.empty(0) if kept else c.get_experimental()[row0 * nx:row1 * nx]
 
-    return _run(flat, ny, nx, w.shape[0], op, context, device, contexts).reshape(patterns.shape)
+    out = _run(flat, ny, nx, w.shape[0], op, context, device, contexts)
+    return patterns if kept else out.reshape(patterns.shape)
 
 
 def dot_product_window(window, nav_shape):
@@ -162,7 +174,7 @@ def _dot_dtype(dtype_out):
 
 
 def _dot_products(patterns, window, zero_mean, normalize, dtype_out, matrices, average, context, device, contexts):
-    patterns = np.asarray(patterns)
+    patterns = _pattern.as_patterns(patterns)
     nav = patterns.shape[:-2]
     window = dot_product_window(window, nav)
     dt = _dot_dtype(dtype_out)

@@ -35,7 +35,59 @@ def _context(context, device):
     return context if context is not None else _lib.Context(device)
 
 
+class ResidentPatterns:
+    """The patterns of a resident `EBSD` signal (`EBSD.to_device`): they live in the HBM of `context` as its experimental
+    set, which nothing else may upload into.  Stands in for the host array in every stack function of this package:
+    `shape`, `dtype` and `ndim` follow the context (an op may change the detector shape or the dtype), `_upload` finds
+    the patterns in place, and with `keep` a function that would download the processed patterns returns this object
+    instead - they stay where they are."""
+
+    def __init__(self, context, navigation_shape, keep=False):
+        self.context = context
+        self.navigation_shape = tuple(int(n) for n in navigation_shape)
+        self.keep = keep
+
+    def kept(self, keep=True):
+        return ResidentPatterns(self.context, self.navigation_shape, keep)
+
+    def flat(self):
+        """As a stack (n, sy, sx)."""
+        return ResidentPatterns(self.context, (int(self.context._exp_shape[0]),), self.keep)
+
+    shape = property(lambda self: self.navigation_shape + tuple(self.context._detector))
+    dtype = property(lambda self: np.dtype(self.context._exp_dtype))
+    ndim = property(lambda self: len(self.navigation_shape) + 2)
+    size = property(lambda self: int(np.prod(self.shape)))
+
+    def host(self):
+        """A host copy (the recorded background steps run first)."""
+        return self.context.get_experimental().reshape(self.shape)
+
+    def result(self, collect=None):
+        """What a stack function returns after its op ran on the context: this object (`keep`), else what `collect`
+        (default: a download of the patterns) gives, one row per pattern, in the navigation shape."""
+        if collect is None:
+            if self.keep:
+                return self
+            collect = _download
+        out = collect(self.context)
+        return out.reshape(self.navigation_shape + out.shape[1:])
+
+
+def as_patterns(patterns):
+    """`np.asarray`, except that resident patterns pass through."""
+    return patterns if isinstance(patterns, ResidentPatterns) else np.asarray(patterns)
+
+
 def _upload(ctx, patterns):
+    if isinstance(patterns, ResidentPatterns):
+        if ctx is not patterns.context:
+            raise ValueError("resident patterns are processed on the context that holds them")
+        if patterns.dtype.type not in _SUPPORTED:
+            raise ValueError(f"pattern dtype {patterns.dtype} is not supported by the GPU pre-processing kernels")
+        sy, sx = patterns.shape[-2:]
+        ctx.set_problem(sy, sx, None, _lib.METRIC_NCC, 1)  # (keeps the patterns; a signal mask of an indexing run goes)
+        return patterns.shape
     patterns = np.asarray(patterns)
     if patterns.ndim < 2:
         raise ValueError("patterns need at least the two detector axes")
@@ -56,7 +108,12 @@ def _process(patterns, record, context, device, contexts, collect=_download):
     """Upload -> `record(ctx)` (the recorded step) -> `collect(ctx)` (one row per pattern), on one context or -
     `contexts`: one per GPU, the members of a `_lib.Group` - block-wise: the patterns are independent, every GPU takes a
     contiguous block of them over its own host link from a host thread of its own (the library calls release the GIL);
-    the blocks are concatenated and given the patterns' leading shape."""
+    the blocks are concatenated and given the patterns' leading shape.  `ResidentPatterns` are processed where they are,
+    without the upload - and without the download when they are to be kept."""
+    if isinstance(patterns, ResidentPatterns):
+        _upload(patterns.context if context is None else context, patterns)
+        record(patterns.context)
+        return patterns.result(None if collect is _download else collect)
     patterns = np.asarray(patterns)
     lead = patterns.shape[:-2]
     if contexts and len(contexts) > 1 and patterns.ndim > 2 and int(np.prod(patterns.shape[:-2])) >= len(contexts):
@@ -115,7 +172,7 @@ def remove_static_background(patterns, static_bg, operation="subtract", scale_bg
     shape, as in the reference."""
     if operation not in _OPS:
         raise ValueError(f"operation '{operation}' must be either 'subtract' or 'divide'")
-    patterns = np.asarray(patterns)
+    patterns = as_patterns(patterns)
     bg = check_static_background(patterns.dtype, patterns.shape[-2:], static_bg)
     return _process(patterns, lambda c: c.remove_static_background(bg, _OPS[operation], scale_bg), context, device, contexts)
 
@@ -129,7 +186,7 @@ def remove_dynamic_background(patterns, operation="subtract", filter_domain="fre
         raise ValueError(f"{filter_domain} must be either of {list(_DOMAINS)}")
     if operation not in _OPS:
         raise ValueError(f"operation '{operation}' must be either 'subtract' or 'divide'")
-    patterns = np.asarray(patterns)
+    patterns = as_patterns(patterns)
     if std is None:
         std = patterns.shape[-1] / 8
     return _process(patterns, lambda c: c.remove_dynamic_background(_OPS[operation], _DOMAINS[filter_domain], std, truncate),
@@ -160,7 +217,7 @@ def get_image_quality(patterns, normalize=True, frequency_vectors=None, inertia_
     all-zero pattern without `normalize`, and, with `normalize`, a pattern whose values are all exactly equal.  For
     float patterns of equal values whose float32 mean is not exact the reference divides round-off by round-off and
     returns noise instead; here such a pattern is NaN too."""
-    patterns = np.asarray(patterns)
+    patterns = as_patterns(patterns)
     if patterns.ndim < 2:
         raise ValueError("patterns need at least the two detector axes")
     sig = patterns.shape[-2:]
@@ -184,7 +241,7 @@ def region_sums(patterns, rects, *, context=None, device=0, contexts=None):
     (csrc/regionsum.hip): an array of shape `patterns.shape[:-2] + (n_rects,)`, uint64 for uint8 / uint16 patterns,
     int64 for int8 / int16 (both exact), float32 / float64 for patterns of these (summed in float64 in a fixed order
     and rounded once; NaN counts as 0).  The same bits whichever way `contexts` split the patterns."""
-    patterns = np.asarray(patterns)
+    patterns = as_patterns(patterns)
     if patterns.ndim < 2:
         raise ValueError("patterns need at least the two detector axes")
     r = np.asarray(rects)
@@ -235,7 +292,7 @@ def fft_filter_stack(patterns, transfer_function, function_domain, shift=False, 
     0 / 0), becomes 0 for integer dtypes and NaN for float dtypes.
 
     Not the reference's `pattern.fft_filter`, which returns one unrescaled float pattern."""
-    patterns = np.asarray(patterns)
+    patterns = as_patterns(patterns)
     if patterns.ndim < 2:
         raise ValueError("patterns need at least the two detector axes")
     domain, table = fft_filter_table(transfer_function, function_domain, shift, patterns.shape[-2:])
@@ -293,7 +350,7 @@ def _process_relative(patterns, rescale, context, device, contexts):
     `data.min()` / `data.max()`.  One context: upload, reduce, rescale, download.  Several (`contexts`, block-wise as
     `_process`): every member uploads its block and reduces it, the host combines the ranges, then every member
     rescales and downloads its block."""
-    patterns = np.asarray(patterns)
+    patterns = as_patterns(patterns)
     lead = patterns.shape[:-2]
     if not (contexts and len(contexts) > 1 and patterns.ndim > 2 and int(np.prod(lead)) >= len(contexts)):
         return _process(patterns, lambda c: rescale(c, c.intensity_range()), context, device, contexts)
@@ -355,7 +412,7 @@ def rescale_intensity_stack(patterns, in_range=None, out_range=None, dtype_out=N
     """`rescale_intensity` of every pattern of (..., sy, sx), what `EBSD.rescale_intensity` maps: `relative` takes
     (imin, imax) as the global min / max of all patterns (NaN if any is NaN) unless `percentiles` are given; returns a
     new array of `dtype_out` (default: the patterns' dtype) and the input's shape."""
-    patterns = np.asarray(patterns)
+    patterns = as_patterns(patterns)
     if patterns.ndim < 2:
         raise ValueError("patterns need at least the two detector axes")
     dt = intensity_dtype_out(dtype_out, patterns.dtype)
@@ -371,7 +428,7 @@ def normalize_intensity_stack(patterns, num_std=1, divide_by_square_root=False, 
                               device=0, contexts=None):
     """`normalize_intensity` of every pattern of (..., sy, sx), what `EBSD.normalize_intensity` maps; `dtype_out`
     defaults to the patterns' dtype, as there."""
-    patterns = np.asarray(patterns)
+    patterns = as_patterns(patterns)
     if patterns.ndim < 2:
         raise ValueError("patterns need at least the two detector axes")
     dt = intensity_dtype_out(dtype_out, patterns.dtype)
@@ -401,7 +458,7 @@ def downsample_stack(patterns, factor, dtype_out=None, *, context=None, device=0
     (..., sy / factor, sx / factor) of `dtype_out`.  The reference's `_downsample2d` (pattern/_pattern.py:776-807) bit
     for bit: float32 sums in its order, float32 rescaling, `astype`.  A pattern holding a NaN, or whose binned image is
     constant (the reference's 0 / 0), becomes NaN for float `dtype_out` and 0 for integer ones (csrc/downsample.hip)."""
-    patterns = np.asarray(patterns)
+    patterns = as_patterns(patterns)
     if patterns.ndim < 2:
         raise ValueError("patterns need at least the two detector axes")
     factor = check_binning_factor(factor, patterns.shape[-2:])
@@ -420,7 +477,7 @@ def get_dynamic_background_stack(patterns, filter_domain="frequency", std=None, 
     in `dtype_out`.  `std` defaults to an eighth of the pattern width."""
     if filter_domain not in _DOMAINS:
         raise ValueError(f"{filter_domain} must be either of {list(_DOMAINS)}")
-    patterns = np.asarray(patterns)
+    patterns = as_patterns(patterns)
     if patterns.ndim < 2:
         raise ValueError("patterns need at least the two detector axes")
     dt = intensity_dtype_out(dtype_out, patterns.dtype)
@@ -464,6 +521,8 @@ def clahe_arguments(patterns, kernel_size, clip_limit, nbins):
     always empty bins take part in the clip redistribution."""
     ky, kx = kernel_size
     if patterns.dtype.kind == "f" and patterns.size:
+        if isinstance(patterns, ResidentPatterns):
+            patterns = patterns.host()  # (the per-pattern extrema decide: one download)
         flat = patterns.reshape(-1, patterns.shape[-2] * patterns.shape[-1])
         mn, mx = flat.min(axis=1), flat.max(axis=1)  # NaN in a pattern: no check for it, as np.min gives NaN there
         if np.any((mn < -1.0) | (mx > 1.0)):
@@ -509,7 +568,7 @@ def adaptive_histogram_equalization_stack(patterns, kernel_size=None, clip_limit
     """`adaptive_histogram_equalization` of every pattern of (..., sy, sx), what
     `EBSD.adaptive_histogram_equalization` maps: `kernel_size` as `clahe_kernel_size` derives it (None: the reference's
     (sx // 4, sy // 4)); returns a new array of the input's dtype and shape."""
-    patterns = np.asarray(patterns)
+    patterns = as_patterns(patterns)
     if patterns.ndim < 2:
         raise ValueError("patterns need at least the two detector axes")
     args = clahe_arguments(patterns, clahe_kernel_size(kernel_size, patterns.shape[-2:]), clip_limit, nbins)

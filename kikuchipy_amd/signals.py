@@ -12,12 +12,13 @@ the reference's:
 * `EBSD.refine_orientation` / `refine_projection_center` /
   `refine_orientation_projection_center`   signals/ebsd.py:1986-2700
 
-Like the reference's methods, each call hands back host data (`self.data` is
-replaced by the pre-processed array); callers that want the whole chain
-static -> dynamic -> indexing to stay in HBM use the C ABI / `_lib.Context`
-directly (`kpdi_remove_*_background` work in place on the resident patterns
-that `kpdi_push_dictionary_chunk` then matches), as `bench.py --workload
-config3` does.
+A signal is host-backed by default: like the reference's methods, each call then hands back host data (`self.data`
+is replaced by the processed array), which costs an upload and a download per call.  `EBSD.to_device()` makes the
+signal resident instead: the patterns live in the HBM of the signal's engine context, every method above and every
+pre-processing method works on them where they are (`inplace=True` moves no pattern at all, `inplace=False` copies
+device to device into a new resident signal), selections (`inav`, `isig`, `crop`, `extract_grid`) run as a gather on
+the GPU, `dictionary_indexing` matches them without an upload, and `data` downloads lazily.  Who owns the buffer and
+what invalidates the host copy: DESIGN.md section 20.
 """
 
 import copy
@@ -25,7 +26,7 @@ import warnings
 
 import numpy as np
 
-from kikuchipy_amd import _lib
+from kikuchipy_amd import _lib, _selection
 from kikuchipy_amd.indexing._dictionary_indexing import dictionary_indexing as _dictionary_indexing
 from kikuchipy_amd.pattern import _decomposition, _neighbours, _pattern
 from kikuchipy_amd.simulations import DTYPE_RANGE, ProjectedDictionary
@@ -35,7 +36,7 @@ from kikuchipy_amd.simulations import DTYPE_RANGE, ProjectedDictionary
 # points per GPU; below, the set-up of a group costs more than it saves)
 REFINE_GROUP_MIN_POINTS = 2048
 # ... and a background removal from this many patterns on (a block of the patterns per GPU, each over its own host link:
-# the call is transfer-bound - patterns up, patterns down)
+# a host-backed call is transfer-bound - patterns up, patterns down)
 PREPROCESS_GROUP_MIN_POINTS = 16384
 
 
@@ -149,6 +150,7 @@ class EBSD:
         is free to shard the dictionary over every visible GPU); devices: "all" / a list of ids for
         `dictionary_indexing` (see `kikuchipy_amd.dictionary_indexing`); `detector`, `static_background`, `xmap`: the
         reference's custom attributes (signals/ebsd.py:188-199) - without a detector, one of the signal's shape."""
+        self._resident = None  # the patterns in HBM (pattern._pattern.ResidentPatterns) once `to_device()` was called
         self.data = data
         self._detector = None
         ndim = data.ndim if hasattr(data, "ndim") else np.ndim(data)  # lazy data is not touched
@@ -203,7 +205,7 @@ class EBSD:
     @static_background.setter
     def static_background(self, value):
         if value is not None:
-            if getattr(value, "dtype", None) != self.data.dtype:
+            if getattr(value, "dtype", None) != self._data_dtype:
                 warnings.warn("Background pattern has different data type from patterns")
             if tuple(getattr(value, "shape", ())) != self._signal_shape_rc:
                 warnings.warn("Background pattern has different shape from patterns")
@@ -223,7 +225,9 @@ class EBSD:
     # ------------------------------------------------------------------ engines
     def close(self):
         """Destroy the engines this signal keeps from call to call (its own context, its groups over several GPUs -
-        their host threads and communicators); they are made again when needed.  `with EBSD(...) as s:` calls it."""
+        their host threads and communicators); they are made again when needed.  `with EBSD(...) as s:` calls it.  A
+        resident signal brings its patterns to the host first."""
+        self.to_host()  # (a resident signal's patterns would go with its context)
         for g in self._groups.values():
             g.close()
         self._groups = {}
@@ -237,14 +241,132 @@ class EBSD:
     def __exit__(self, *exc):
         self.close()
 
+    # ------------------------------------------------------------------ where the patterns live
+    @property
+    def data(self):
+        """The patterns as a host array.  On a resident signal the first read downloads them (after the recorded
+        background steps) and the array is kept until the next method changes the patterns; assigning `data` makes the
+        signal host-backed again."""
+        if self._resident is not None and self._host is None:
+            self._host = self._resident.host()
+        return self._host
+
+    @data.setter
+    def data(self, value):
+        self._host = value
+        self._resident = None
+
+    @property
+    def is_resident(self):
+        """Whether the patterns live in the HBM of this signal's context (`to_device`) or on the host (the default)."""
+        return self._resident is not None
+
+    def to_device(self):
+        """Make the signal resident: one upload into this signal's engine context, which from now on owns the patterns -
+        every method works on them there, nothing else uploads into that context.  Returns `self`."""
+        if self._resident is None:
+            if hasattr(self._host, "compute"):
+                raise ValueError("lazy data cannot be made resident: compute it first")
+            data = np.asarray(self._host)
+            _pattern._upload(self.context, data)
+            self._resident = _pattern.ResidentPatterns(self.context, data.shape[:-2])
+            self._host = data  # (still what the device holds: kept as the host copy)
+        return self
+
+    def to_host(self):
+        """Make the signal host-backed: one download, unless the host copy is current.  Returns `self`."""
+        if self._resident is not None:
+            self.data = self.data
+        return self
+
+    def _patterns_changed(self):
+        """A method changed the resident patterns: the host copy is stale."""
+        self._host = None
+
+    @property
+    def _data_shape(self):
+        return tuple(self._resident.shape if self._resident is not None else self._host.shape)
+
+    @property
+    def _data_dtype(self):
+        return self._resident.dtype if self._resident is not None else self._host.dtype
+
+    def _own_device_only(self, devices, comm=None):
+        """A resident signal works on the device that holds it: what a CALL names must be that device (the `devices`
+        the signal was constructed with describe where a host-backed signal may spread, and are not consulted)."""
+        own = self._device or 0
+        ids = _lib.resolve_devices(devices)
+        if comm is not None or (ids is not None and list(ids) != [own]):
+            raise ValueError(f"a resident signal works on its own device ({own}): `devices` / `comm` cannot spread it over "
+                             "others (multi-GPU residency is not implemented); call to_host() first")
+
+    def _resident_twin(self, navigation_shape, fill):
+        """A new resident signal on this signal's device with this one's custom attributes (deep copies), whose context
+        `fill(context)` fills with patterns."""
+        placeholder = np.broadcast_to(np.zeros((), dtype=self._data_dtype), tuple(navigation_shape) + (1, 1))
+        out = EBSD(placeholder, None if self._static_background is None else np.array(self._static_background),
+                   copy.deepcopy(self._xmap), self.step_sizes, self.scan_unit, self._device, self._devices)
+        out._detector = None if self._detector is None else self._detector.deepcopy()
+        if hasattr(self, "original_metadata"):
+            out.original_metadata = self.original_metadata
+        try:
+            fill(out.context)
+        except BaseException:
+            out._discard()
+            raise
+        out._resident = _pattern.ResidentPatterns(out.context, navigation_shape)
+        out._host = None
+        return out
+
+    def _discard(self):
+        """Close this signal's engines without bringing anything back."""
+        self._resident = None
+        self.close()
+
+    def _transform(self, inplace, devices, run):
+        """What every pre-processing method ends with.  `run(patterns, engines)` calls the stack function with
+        `**engines` (context / contexts).  Host-backed: upload, op, download; the result replaces `data` or goes into a
+        new signal.  Resident: the op runs on the patterns where they are - of this signal (`inplace`), or of a
+        device-to-device copy, which is returned."""
+        if self._resident is not None:
+            self._own_device_only(devices)
+            target = self if inplace else self.deepcopy()
+            try:
+                run(target._resident.kept(), dict(context=target.context, contexts=None))
+            except BaseException:
+                if target is not self:
+                    target._discard()
+                raise
+            target._patterns_changed()
+            return None if inplace else target
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        out = run(np.asarray(self.data), dict(context=None if contexts else self.context, contexts=contexts))
+        if inplace:
+            self.data = out
+            return None
+        return self._like(out)
+
+    def _read(self, devices, run, flat=False):
+        """What every read-only method ends with: `run(patterns, engines)` on the host array or on the resident
+        patterns (`flat`: as a stack of patterns)."""
+        if self._resident is not None:
+            self._own_device_only(devices)
+            p = self._resident.flat() if flat else self._resident.kept(False)
+            return run(p, dict(context=self.context, contexts=None))
+        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+        data = np.asarray(self.data)
+        if flat:
+            data = data.reshape((-1,) + data.shape[-2:])
+        return run(data, dict(context=None if contexts else self.context, contexts=contexts))
+
     # ------------------------------------------------------------------ shapes
     @property
     def _navigation_shape_rc(self):
-        return tuple(self.data.shape[:-2])
+        return self._data_shape[:-2]
 
     @property
     def _signal_shape_rc(self):
-        return tuple(self.data.shape[-2:])
+        return self._data_shape[-2:]
 
     @property
     def navigation_size(self):
@@ -259,6 +381,11 @@ class EBSD:
         return _Axes(self._navigation_shape_rc[::-1], self._signal_shape_rc[::-1])
 
     def deepcopy(self):
+        """A copy that shares nothing with this signal; of a resident signal a resident one (a device-to-device copy
+        into a context of its own)."""
+        if self._resident is not None:
+            src = self._resident
+            return self._resident_twin(src.navigation_shape, lambda c: src.context.select_patterns(into=c))
         out = EBSD(np.array(self.data, copy=True),
                    None if self.static_background is None else np.array(self.static_background),
                    self.xmap, self.step_sizes, self.scan_unit, self._device, self._devices)
@@ -325,26 +452,16 @@ class EBSD:
             static_bg = self.static_background
             if not isinstance(static_bg, np.ndarray) and not hasattr(static_bg, "compute"):
                 raise ValueError("`EBSD.static_background` is not a valid array")
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        out = _pattern.remove_static_background(np.asarray(self.data), static_bg, operation, scale_bg,
-                                                context=None if contexts else self.context, contexts=contexts)
-        if inplace:
-            self.data = out
-            return None
-        return self._like(out)
+        return self._transform(inplace, devices, lambda p, engines: _pattern.remove_static_background(
+            p, static_bg, operation, scale_bg, **engines))
 
     def remove_dynamic_background(self, operation="subtract", filter_domain="frequency", std=None, truncate=4.0,
                                   show_progressbar=None, inplace=True, lazy_output=None, *, devices=None):
         """signals/ebsd.py:575-696; `show_progressbar` / `lazy_output` as in `remove_static_background`."""
         if lazy_output and inplace:
             raise ValueError("'lazy_output=True' requires 'inplace=False'")
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        out = _pattern.remove_dynamic_background(np.asarray(self.data), operation, filter_domain, std,
-                                                 truncate, context=None if contexts else self.context, contexts=contexts)
-        if inplace:
-            self.data = out
-            return None
-        return self._like(out)
+        return self._transform(inplace, devices, lambda p, engines: _pattern.remove_dynamic_background(
+            p, operation, filter_domain, std, truncate, **engines))
 
     def fft_filter(self, transfer_function, function_domain, shift=False, show_progressbar=None, inplace=True,
                    lazy_output=None, *, devices=None):
@@ -355,13 +472,8 @@ class EBSD:
         `remove_static_background`."""
         if lazy_output and inplace:
             raise ValueError("'lazy_output=True' requires 'inplace=False'")
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        out = _pattern.fft_filter_stack(np.asarray(self.data), transfer_function, function_domain, shift,
-                                        context=None if contexts else self.context, contexts=contexts)
-        if inplace:
-            self.data = out
-            return None
-        return self._like(out)
+        return self._transform(inplace, devices, lambda p, engines: _pattern.fft_filter_stack(
+            p, transfer_function, function_domain, shift, **engines))
 
     def rescale_intensity(self, relative=False, in_range=None, out_range=None, dtype_out=None, percentiles=None,
                           show_progressbar=None, inplace=True, lazy_output=None, *, devices=None):
@@ -376,15 +488,9 @@ class EBSD:
             raise ValueError("'percentiles' must be None if 'in_range' is not None")
         elif relative is True and in_range is not None:
             raise ValueError("'in_range' must be None if 'relative' is True")
-        _pattern.intensity_dtype_out(dtype_out, self.data.dtype)  # before any GPU work
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        out = _pattern.rescale_intensity_stack(np.asarray(self.data), in_range, out_range, dtype_out, percentiles,
-                                               relative=bool(relative), context=None if contexts else self.context,
-                                               contexts=contexts)
-        if inplace:
-            self.data = out
-            return None
-        return self._like(out)
+        _pattern.intensity_dtype_out(dtype_out, self._data_dtype)  # before any GPU work
+        return self._transform(inplace, devices, lambda p, engines: _pattern.rescale_intensity_stack(
+            p, in_range, out_range, dtype_out, percentiles, relative=bool(relative), **engines))
 
     def normalize_intensity(self, num_std=1, divide_by_square_root=False, dtype_out=None, show_progressbar=None,
                             inplace=True, lazy_output=None, *, devices=None):
@@ -393,14 +499,9 @@ class EBSD:
         `show_progressbar` / `lazy_output` as in `rescale_intensity`."""
         if lazy_output and inplace:
             raise ValueError("'lazy_output=True' requires 'inplace=False'")
-        _pattern.intensity_dtype_out(dtype_out, self.data.dtype)  # before any GPU work
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        out = _pattern.normalize_intensity_stack(np.asarray(self.data), num_std, divide_by_square_root, dtype_out,
-                                                 context=None if contexts else self.context, contexts=contexts)
-        if inplace:
-            self.data = out
-            return None
-        return self._like(out)
+        _pattern.intensity_dtype_out(dtype_out, self._data_dtype)  # before any GPU work
+        return self._transform(inplace, devices, lambda p, engines: _pattern.normalize_intensity_stack(
+            p, num_std, divide_by_square_root, dtype_out, **engines))
 
     def adaptive_histogram_equalization(self, kernel_size=None, clip_limit=0.0, nbins=128, show_progressbar=None,
                                         inplace=True, lazy_output=None, *, devices=None):
@@ -411,8 +512,13 @@ class EBSD:
         `remove_static_background`."""
         if lazy_output and inplace:
             raise ValueError("'lazy_output=True' requires 'inplace=False'")
-        data = np.asarray(self.data)
-        if np.isnan(data).any():
+        # (float patterns of a resident signal: the checks below read the values - one lazy download, kept as the host
+        # copy; integer patterns are not looked at)
+        if self._resident is not None and self._data_dtype.kind != "f":
+            data = self._resident.kept(False)
+        else:
+            data = np.asarray(self.data)
+        if data.dtype.kind == "f" and np.isnan(data).any():
             warnings.warn("Equalization of signals with NaN data has been shown to give bad results")
         elif np.issubdtype(data.dtype, np.floating):
             warnings.warn(
@@ -420,15 +526,12 @@ class EBSD:
                 "intensities to integer intensities is recommended."
             )
         kernel_size = _pattern.clahe_kernel_size(kernel_size, self._signal_shape_rc)
-        _pattern.clahe_arguments(data, kernel_size, clip_limit, nbins)  # before any GPU work
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        out = _pattern.adaptive_histogram_equalization_stack(data, kernel_size, clip_limit, nbins,
-                                                             context=None if contexts else self.context,
-                                                             contexts=contexts)
-        if inplace:
-            self.data = out
-            return None
-        return self._like(out)
+        args = _pattern.clahe_arguments(data, kernel_size, clip_limit, nbins)  # before any GPU work
+        if self._resident is not None:  # (checked above: the stack function would download the patterns to check again)
+            return self._transform(inplace, devices, lambda p, engines: _pattern._process(
+                p, lambda c: c.adaptive_histogram_equalization(*args), engines["context"], 0, None))
+        return self._transform(inplace, devices, lambda p, engines: _pattern.adaptive_histogram_equalization_stack(
+            p, kernel_size, clip_limit, nbins, **engines))
 
     def get_dynamic_background(self, filter_domain="frequency", std=None, truncate=4.0, dtype_out=None,
                                show_progressbar=None, lazy_output=None, *, devices=None, **kwargs):
@@ -442,10 +545,9 @@ class EBSD:
         if kwargs:
             raise TypeError(f"get_dynamic_background() got keyword arguments {sorted(kwargs)} for the reference's SciPy "
                             "filter function, which this GPU engine does not call")
-        _pattern.intensity_dtype_out(dtype_out, self.data.dtype)  # before any GPU work
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        out = _pattern.get_dynamic_background_stack(np.asarray(self.data), filter_domain, std, truncate, dtype_out,
-                                                    context=None if contexts else self.context, contexts=contexts)
+        _pattern.intensity_dtype_out(dtype_out, self._data_dtype)  # before any GPU work
+        out = self._read(devices, lambda p, engines: _pattern.get_dynamic_background_stack(
+            p, filter_domain, std, truncate, dtype_out, **engines))
         return self._like(out)
 
     def downsample(self, factor, dtype_out=None, show_progressbar=None, inplace=True, lazy_output=None, *,
@@ -459,21 +561,27 @@ class EBSD:
         if lazy_output and inplace:
             raise ValueError("'lazy_output=True' requires 'inplace=False'")
         factor = _pattern.check_binning_factor(factor, self._signal_shape_rc)
-        dt = _pattern.intensity_dtype_out(dtype_out, self.data.dtype)  # before any GPU work
+        dt = _pattern.intensity_dtype_out(dtype_out, self._data_dtype)  # before any GPU work
         static_bg = self.static_background
         if static_bg is not None:
             if hasattr(static_bg, "compute"):
                 static_bg = static_bg.compute()
-            static_bg = _pattern.downsample_stack(np.asarray(static_bg), factor, dt, context=self.context)
+            # (a resident signal's context holds its patterns: the background is binned on a scratch context)
+            static_bg = _pattern.downsample_stack(np.asarray(static_bg), factor, dt, device=self._device or 0,
+                                                  context=None if self._resident is not None else self.context)
         detector = self.detector.deepcopy()  # (the default detector when none was set: the reference always has one)
         detector.shape = tuple(n // factor for n in self._signal_shape_rc)
         detector.binning = detector.binning * factor
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        data = _pattern.downsample_stack(np.asarray(self.data), factor, dt, context=None if contexts else self.context,
-                                         contexts=contexts)
-        out = self if inplace else EBSD(data, None, self.xmap, self.step_sizes, self.scan_unit, self._device,
-                                        self._devices)
-        out.data = data
+        if self._resident is not None:
+            out = self._transform(inplace, devices, lambda p, engines: _pattern.downsample_stack(p, factor, dt, **engines))
+            out = self if inplace else out
+        else:
+            contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
+            data = _pattern.downsample_stack(np.asarray(self.data), factor, dt,
+                                             context=None if contexts else self.context, contexts=contexts)
+            out = self if inplace else EBSD(data, None, self.xmap, self.step_sizes, self.scan_unit, self._device,
+                                            self._devices)
+            out.data = data
         out._static_background = static_bg
         out._detector = detector
         out._learning_results = None  # (they belong to the patterns' old shape)
@@ -488,11 +596,14 @@ class EBSD:
         GPU (kpdi_change_dtype: to integers by truncation with NumPy's wrap-around, to float32 by rounding).
         `static_background` is left alone.  The workflow's `change_dtype("float32")` before a decomposition and
         `change_dtype(dtype_orig)` after it."""
-        dt = _pattern.intensity_dtype_out(dtype, self.data.dtype)
-        if self.data.dtype.type not in _pattern.INTENSITY_DTYPES:
-            raise ValueError(f"pattern dtype {self.data.dtype} is not supported by the GPU pre-processing kernels")
-        if dt == self.data.dtype:
+        dt = _pattern.intensity_dtype_out(dtype, self._data_dtype)
+        if self._data_dtype.type not in _pattern.INTENSITY_DTYPES:
+            raise ValueError(f"pattern dtype {self._data_dtype} is not supported by the GPU pre-processing kernels")
+        if dt == self._data_dtype:
             return None
+        if self._resident is not None:
+            return self._transform(True, None, lambda p, engines: _pattern._process(
+                p, lambda c: c.change_dtype(dt), engines["context"], 0, None))
         self.data = _pattern._process(np.asarray(self.data), lambda c: c.change_dtype(dt), self.context, 0, None)
         return None
 
@@ -520,8 +631,9 @@ class EBSD:
             if name == "svd_solver" and value in ("auto", "full"):
                 continue
             raise NotImplementedError(f"{name}={value!r} is not implemented by the GPU decomposition")
-        checked = _decomposition.check_decomposition(self.data.shape, self.data.dtype, output_dimension, centre)
-        self._learning_results = _decomposition._decompose(np.asarray(self.data), checked, centre, self.context)
+        checked = _decomposition.check_decomposition(self._data_shape, self._data_dtype, output_dimension, centre)
+        patterns = np.asarray(self.data) if self._resident is None else self._resident.kept(False)
+        self._learning_results = _decomposition._decompose(patterns, checked, centre, self.context)
         return None
 
     def get_decomposition_model(self, components=None, dtype_out="float32"):
@@ -533,7 +645,11 @@ class EBSD:
         learning results; this signal's stay as they are."""
         if self._learning_results is None:
             raise ValueError("No learning results found: run EBSD.decomposition() first")
-        checked = _decomposition.check_model(self.data.shape, self._learning_results, components, dtype_out)
+        checked = _decomposition.check_model(self._data_shape, self._learning_results, components, dtype_out)
+        if self._resident is not None:  # the model replaces the patterns of a device-to-device copy
+            results = self._learning_results
+            return self._transform(False, None, lambda p, engines: _decomposition._model(
+                p, checked, results, dtype_out, engines["context"]))
         out = _decomposition._model(np.asarray(self.data), checked, self._learning_results, dtype_out, self.context)
         return self._like(out)
 
@@ -541,17 +657,12 @@ class EBSD:
         """signals/ebsd.py:1312-1375: Q of every pattern (`kikuchipy_amd.pattern.get_image_quality` with the default
         frequency vectors), float32 of the navigation shape (0-d without navigation axes).  `show_progressbar` is
         accepted and has nothing to show."""
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        data = np.asarray(self.data)
-        q = _pattern.get_image_quality(data.reshape((-1,) + data.shape[-2:]), normalize,
-                                       context=None if contexts else self.context, contexts=contexts)
+        q = self._read(devices, lambda p, engines: _pattern.get_image_quality(p, normalize, **engines), flat=True)
         return q.reshape(self._navigation_shape_rc)
 
     def _region_sums(self, rects, devices=None):
         """`kikuchipy_amd.pattern.region_sums` of this signal's patterns: navigation shape + (n_rects,)."""
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        return _pattern.region_sums(np.asarray(self.data), rects, context=None if contexts else self.context,
-                                    contexts=contexts)
+        return self._read(devices, lambda p, engines: _pattern.region_sums(p, rects, **engines))
 
     def get_virtual_bse_intensity(self, roi, out_signal_axes=None, *, devices=None):
         """signals/ebsd.py:1555-1598: the virtual backscatter electron image formed by the intensity within `roi` on the
@@ -592,13 +703,8 @@ class EBSD:
         w = _neighbours.window_on_map(win, nav)  # before any GPU work, as the window sums the stack function checks
         if not _neighbours.neighbour_window_sums(w, nav[0], nav[1] if len(nav) == 2 else 1).all():
             raise ValueError("The window sum of a map point is 0: its average is undefined")
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        out = _neighbours.average_neighbour_patterns_stack(np.asarray(self.data), win,
-                                                           context=None if contexts else self.context, contexts=contexts)
-        if inplace:
-            self.data = out
-            return None
-        return self._like(out)
+        return self._transform(inplace, devices, lambda p, engines: _neighbours.average_neighbour_patterns_stack(
+            p, win, **engines))
 
     def get_neighbour_dot_product_matrices(self, window=None, zero_mean=True, normalize=True, dtype_out="float32",
                                            show_progressbar=None, *, devices=None):
@@ -609,9 +715,8 @@ class EBSD:
         nav = self._navigation_shape_rc
         window = _neighbours.dot_product_window(window, nav)  # before any GPU work
         _neighbours._dot_dtype(dtype_out)
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        return _neighbours.neighbour_dot_product_matrices(np.asarray(self.data), window, zero_mean, normalize, dtype_out,
-                                                          context=None if contexts else self.context, contexts=contexts)
+        return self._read(devices, lambda p, engines: _neighbours.neighbour_dot_product_matrices(
+            p, window, zero_mean, normalize, dtype_out, **engines))
 
     def get_average_neighbour_dot_product_map(self, window=None, zero_mean=True, normalize=True, dtype_out="float32",
                                               dp_matrices=None, show_progressbar=None, *, devices=None):
@@ -623,10 +728,156 @@ class EBSD:
         if dp_matrices is not None:
             return _neighbours.average_dot_product_map_from_matrices(dp_matrices, window, len(nav))
         _neighbours._dot_dtype(dtype_out)
-        contexts = self._member_contexts(devices, PREPROCESS_GROUP_MIN_POINTS)
-        return _neighbours.average_neighbour_dot_product_map(np.asarray(self.data), window, zero_mean, normalize,
-                                                             dtype_out, context=None if contexts else self.context,
-                                                             contexts=contexts)
+        return self._read(devices, lambda p, engines: _neighbours.average_neighbour_dot_product_map(
+            p, window, zero_mean, normalize, dtype_out, **engines))
+
+    # ------------------------------------------------------------------ selecting data
+    @property
+    def inav(self):
+        """`s.inav[x, y]`: a new signal of the chosen map points, in HyperSpy's (x, y) order - `s.inav[:, 0]` is the
+        first map row.  Integers (which drop their axis), slices with positive steps, negative indices as NumPy reads
+        them; float indices (HyperSpy's indexing by axis value) are not implemented and raise.  `xmap`, per-point PCs
+        and `step_sizes` follow (signals/ebsd.py:2830-2876, :3294-3377)."""
+        return _Slicer(self, True)
+
+    @property
+    def isig(self):
+        """`s.isig[x, y]`: a new signal of the chosen detector pixels, in HyperSpy's (x, y) order -
+        `s.isig[5:55, 10:50]` is columns 5:55 and rows 10:50.  Slices only (an integer would remove a signal axis).
+        `static_background` is sliced and the detector cropped (`EBSDDetector.crop`)."""
+        return _Slicer(self, False)
+
+    def crop(self, axis, start=None, end=None, convert_units=False):
+        """Crop the signal in place along `axis` to [start, end): an int into the axes in HyperSpy's order - navigation
+        (x, y), then signal (dx, dy) - or one of those names (signals/ebsd.py:2726-2770).  `crop(2, 5, 55)` then
+        `crop("dy", 10, 50)` equals `isig[5:55, 10:50]`."""
+        if convert_units:
+            raise NotImplementedError("convert_units=True is not implemented: this signal's axes carry no units to convert")
+        nav_dim = len(self._navigation_shape_rc)
+        kind, i = _selection.crop_axis(axis, nav_dim)
+        key = [slice(None)] * (nav_dim if kind == "navigation" else 2)
+        key[i] = slice(start, end)
+        self._select(tuple(key), kind == "navigation", inplace=True)
+
+    def crop_signal(self, top=None, bottom=None, left=None, right=None, convert_units=False):
+        """Crop the patterns in place to rows [top, bottom) and columns [left, right) (HyperSpy's
+        `Signal2D.crop_signal`, which calls `crop` per axis)."""
+        if convert_units:
+            raise NotImplementedError("convert_units=True is not implemented: this signal's axes carry no units to convert")
+        self._select((slice(left, right), slice(top, bottom)), False, inplace=True)
+
+    def extract_grid(self, grid_shape, return_indices=False):
+        """signals/ebsd.py:267-378: a new signal with the patterns at the points of a grid of `grid_shape` - an int, or
+        (n columns, n rows) - evenly spaced in the map (`kikuchipy_amd._selection.grid_indices`); with
+        `return_indices` also their indices into `data`, an array of shape (2,) + the grid's shape (rows first).  The
+        detector's per-point PCs are picked at the grid points, `step_sizes` are scaled by the spacing, `xmap` is
+        indexed if it supports it."""
+        if isinstance(grid_shape, (int, np.integer)):
+            grid_shape = (int(grid_shape),)
+        grid_shape = tuple(grid_shape)
+        nav_xy = self._navigation_shape_rc[::-1]
+        if len(grid_shape) != len(nav_xy) or any(g > n for g, n in zip(grid_shape, nav_xy)):
+            raise ValueError(f"grid_shape {grid_shape} must be compatible with navigation shape {nav_xy}")
+        nav = self._navigation_shape_rc
+        idx, spacing = _selection.grid_indices(grid_shape[::-1], nav, return_spacing=True)
+        flat = np.ascontiguousarray((idx[0] * nav[1] + idx[1] if len(nav) == 2 else idx[0]).ravel(), dtype=np.int64)
+        new_nav = tuple(idx.shape[1:])
+        new = self._selected(flat, new_nav, None, None, inplace=False)
+        try:
+            mask = np.zeros(nav, dtype=bool)
+            mask[tuple(idx)] = True
+            new._xmap = None if self._xmap is None else self._xmap[mask.ravel()].deepcopy()
+        except (IndexError, TypeError, ValueError, AttributeError):
+            new._xmap = None
+        det = self.detector.deepcopy()
+        if det.navigation_shape == nav:
+            det.pc = det.pc[tuple(idx)]
+        elif det.navigation_shape != (1,):
+            det.pc = [0.5, 0.5, 0.5]
+        new._detector = det
+        if self.step_sizes is not None and len(self.step_sizes) == len(nav):
+            new.step_sizes = tuple(s * int(sp) for s, sp in zip(self.step_sizes, spacing))
+        return (new, idx) if return_indices else new
+
+    def _select(self, key, is_navigation, inplace=False):
+        """`inav[key]` / `isig[key]` (a new signal) or, `inplace`, the same selection on this signal."""
+        nav, sig = self._navigation_shape_rc, self._signal_shape_rc
+        if is_navigation:
+            flat, new_nav, axes = _selection.navigation_selection(nav, key)
+            out = self._selected(flat, new_nav, None, None, inplace)
+            # the reference's _update_custom_attributes (signals/ebsd.py:3352-3375), in array order
+            slices = tuple(f if dropped else slice(f, f + s * (c - 1) + 1, s) for f, s, c, dropped in axes)
+            try:
+                out._xmap = None if self._xmap is None else self._xmap[slices]
+            except (IndexError, TypeError, ValueError, AttributeError):
+                out._xmap = None
+            det = out._detector
+            if det is not None and det.navigation_shape != (1,):
+                pc = det.pc[slices] if det.navigation_shape == nav else np.empty(0)
+                det.pc = pc if pc.size else [0.5, 0.5, 0.5]
+            if self.step_sizes is not None and len(self.step_sizes) == len(nav):
+                out.step_sizes = tuple(size * s for size, (_, s, _, dropped) in zip(self.step_sizes, axes) if not dropped)
+            return None if inplace else out
+        rows, cols = _selection.signal_selection(sig, key)
+        old_detector = self.detector.deepcopy()
+        out = self._selected(None, nav, rows, cols, inplace)
+        rs, cs = (slice(f, f + s * (c - 1) + 1, s) for f, s, c in (rows, cols))
+        bg = self._static_background
+        if bg is not None:
+            try:
+                out._static_background = np.ascontiguousarray(bg[rs, cs])
+            except (TypeError, IndexError):
+                pass  # (as the reference: a background that cannot be sliced stays)
+        try:
+            if rows[1] != 1 or cols[1] != 1:
+                raise ValueError("a detector is cropped to a rectangle of adjacent pixels")
+            out._detector = old_detector.crop((rows[0], rows[0] + rows[2], cols[0], cols[0] + cols[2]))
+        except ValueError:
+            from kikuchipy_amd.detectors import EBSDDetector
+
+            out._detector = EBSDDetector(shape=(rows[2], cols[2]), pc=[0.5, 0.5, 0.5], sample_tilt=old_detector.sample_tilt,
+                                         tilt=old_detector.tilt, azimuthal=old_detector.azimuthal,
+                                         px_size=old_detector.px_size, binning=old_detector.binning)
+        return None if inplace else out
+
+    def _selected(self, flat, new_nav, rows, cols, inplace):
+        """The data of a selection - patterns `flat` (indices into the flattened map, None: all) in the navigation shape
+        `new_nav`, detector rows / columns (first, step, count) (None: all) - as a new signal with deep copies of this
+        one's attributes, or in this signal.  Host-backed: NumPy indexing into a contiguous copy.  Resident:
+        kpdi_select_patterns, in place or into the new signal's context."""
+        sy, sx = self._signal_shape_rc
+        rows = (0, 1, sy) if rows is None else rows
+        cols = (0, 1, sx) if cols is None else cols
+        if self._resident is not None:
+            src = self._resident
+            _pattern._upload(src.context, src)  # (a signal mask left by an indexing run goes: the shape may change)
+            if inplace:
+                src.context.select_patterns(flat, rows, cols)
+                self._resident = _pattern.ResidentPatterns(src.context, new_nav)
+                self._patterns_changed()
+                out = self
+            else:
+                out = self._resident_twin(new_nav, lambda c: src.context.select_patterns(flat, rows, cols, into=c))
+        else:
+            data = np.asarray(self.data)
+            stack = data.reshape((-1, sy, sx))
+            if flat is not None:
+                stack = stack[flat]
+            rs, cs = (slice(f, f + s * (c - 1) + 1, s) for f, s, c in (rows, cols))
+            picked = np.ascontiguousarray(stack[:, rs, cs]).reshape(tuple(new_nav) + (rows[2], cols[2]))
+            if np.may_share_memory(picked, data):
+                picked = picked.copy()
+            if inplace:
+                self.data = picked
+                out = self
+            else:
+                out = EBSD(picked, None if self._static_background is None else np.array(self._static_background),
+                           copy.deepcopy(self._xmap), self.step_sizes, self.scan_unit, self._device, self._devices)
+                out._detector = None if self._detector is None else self._detector.deepcopy()
+                if hasattr(self, "original_metadata"):
+                    out.original_metadata = self.original_metadata
+        out._learning_results = None  # (they belong to the data's old shape)
+        return out
 
     # ------------------------------------------------------------------ refinement
     def _refine(self, mode, xmap, detector, master_pattern, energy, navigation_mask, signal_mask,
@@ -685,10 +936,21 @@ class EBSD:
                             devices=None, comm=None, verbose=True, compute=None):
         """See `kikuchipy_amd.dictionary_indexing`; `dictionary` is an `EBSD`
         with a 1-D navigation axis and an `xmap` of equal size.  As there, a call that names no
-        device shards the dictionary over every visible GPU from this one process."""
+        device shards the dictionary over every visible GPU from this one process.  A resident signal
+        (`to_device`) is matched where it is, without an upload, on its own device: naming other
+        `devices`, or a `comm`, raises a ValueError, and so does a `ResidentDictionary` (it lives in an
+        engine of its own: `to_host()` first)."""
         from kikuchipy_amd.indexing._resident_dictionary import ResidentDictionary
 
+        if self._resident is not None:
+            self._own_device_only(devices, comm)
         if isinstance(dictionary, ResidentDictionary):
+            if self._resident is not None:
+                # the dictionary lives in its own engine, the patterns in this signal's: matching them would take a
+                # silent download and an upload of the whole set
+                raise ValueError("a resident signal cannot be indexed against a ResidentDictionary, which keeps its "
+                                 "patterns in an engine of its own: call to_host() first (one download), or index "
+                                 "against the dictionary signal itself")
             # prepared once and kept in HBM: only the match runs (metric and signal mask are its own)
             if tuple(dictionary.shape[1:]) != self._signal_shape_rc:
                 raise ValueError(
@@ -720,12 +982,15 @@ class EBSD:
         if isinstance(metric, str) and metric in METRICS:
             # on this signal's engine (one context, or a group over several GPUs): its device buffers - and a group's
             # communicator - are reused from call to call
-            device, engine = self._engine(devices, comm, dict_size)
+            if self._resident is not None:  # on the context that holds the patterns, and nowhere else
+                device, engine = self._device or 0, self.context
+            else:
+                device, engine = self._engine(devices, comm, dict_size)
             metric = METRICS[metric](device=device, compute=compute, context=engine)
             metric.rechunk = rechunk
         res = _dictionary_indexing(
-            self.data, dict_data, metric, keep_n, n_per_iteration, navigation_mask, signal_mask,
-            rechunk, dtype, step_sizes=self.step_sizes, dictionary_rotations=dict_xmap.rotations,
+            self.data if self._resident is None else self._resident.kept(False), dict_data, metric, keep_n,
+            n_per_iteration, navigation_mask, signal_mask, rechunk, dtype, step_sizes=self.step_sizes, dictionary_rotations=dict_xmap.rotations,
             phase_name=getattr(dict_xmap, "phase_name", None), scan_unit=self.scan_unit, device=self._device, comm=comm,
             compute=compute,
             verbose=verbose,
@@ -734,6 +999,17 @@ class EBSD:
         # `to_crystal_map()` when the dictionary's crystal map is orix's
         res.phase_list = getattr(dict_xmap, "phases_in_data", None)
         return res
+
+
+class _Slicer:
+    """`EBSD.inav` / `EBSD.isig`: indexing returns a new signal."""
+
+    def __init__(self, signal, is_navigation):
+        self._signal = signal
+        self._is_navigation = is_navigation
+
+    def __getitem__(self, key):
+        return self._signal._select(key, self._is_navigation)
 
 
 def _rotations_of(xmap):
