@@ -307,8 +307,7 @@ struct kpdi_ctx {
   kpdi::DevBuf tail_s, tail_i;       // partial lists of the quarter-tile tail launch (match.hip: ROWT = 1)
   kpdi::DevBuf epi_stats;            // 4 x u64: what the epilogues of match16.hip did (profiling level 3; kpdi_counters.epi_*)
   kpdi::DevBuf list16;               // float16 form: home of the per-lane lists during a launch (match16.hip)
-  int tail_nsplit = 0;         // lists per pattern / 2 of the last run_match's tail launch, 0 = none
-  int tail_lists = 0;          // lists per pattern in tail_s / tail_i after the last run_match (0 = none): 2 * tail_nsplit
+  int tail_lists = 0;          // lists per pattern in tail_s / tail_i after the last run_match (0 = none): 2 per split
                                // (match.hip's tail launch) or 1 (tailgemm.hip)
   kpdi::DevBuf tail_scores;          // tailgemm.hip: scores of the last partial round, [rows][m_pad]
   kpdi::DevBuf run_s[2], run_i[2];   // running best-k ping-pong
@@ -317,15 +316,10 @@ struct kpdi_ctx {
   bool run_empty = true;          // no chunk merged yet: the running lists hold nothing (and are not initialised)
   kpdi::FillSegments fills;       // small initialisations queued for ONE launch (queue_fill / flush_fills)
   const float *tail_queued = nullptr;  // prepared chunk whose partial last tile is already queued for zeroing
-  // the match launch's bookkeeping (bound / counters) queued ahead of the preparation kernels by push_chunk_dev
-  struct MatchSetup {
-    bool valid = false;
-    int n_chunk = 0, n_tiles = 0, nsplit = 0, rows_per_launch = 0, list_len = 0;
-  } presetup;
-  struct MatchPlan {
-    int tail_tiles = 0, n_main = 0, fixed_draws = 3, bound_rank = 1, bound_grouped = 0, tail_units = 0, tail_nsplit = 0;
-    int gemm_rows = 0;  // float32 form of match16.hip: dictionary rows behind the whole rounds that tailgemm.hip takes (0 = none)
-  } preplan;
+  // the plan whose fills (shared bound, tile counters) sweep_raw_chunk queued ahead of the preparation kernels: a
+  // run_match of this very plan finds them done
+  kpdi::plan::SweepPlan queued;
+  bool queued_valid = false;
   bool final_valid = false;       // `final_idx` points at the lists kpdi_finalize handed out last
   const int *final_idx = nullptr;  // (a view of lists some buffer below owns)
   kpdi::DevBuf osm_idx, osm_out;
@@ -347,8 +341,9 @@ struct kpdi_ctx {
     bool active = false, defer = false;
     const float *y = nullptr;
     const void *raw = nullptr;
-    int raw_dtype = 0, n_tiles = 0, nsplit = 0, rows_per_launch = 0, cap = 0, done = 0, extra = 0;
-    int64_t n_chunk = 0, global_start = 0;
+    int raw_dtype = 0, cap = 0, done = 0, extra = 0;
+    int64_t global_start = 0;
+    kpdi::plan::SweepPlan plan;  // of the chunk (its n_chunk: plan.req.n_chunk); every pass derives its own
     kpdi::Event ready;
     kpdi::PinBuf flag;  // int: patterns the last merge could not certify
   } pend64;
@@ -507,7 +502,7 @@ inline int operand_form(const kpdi_ctx *c) { return c->wide32 ? 3 : c->compute; 
 // patterns per dictionary tile of the match kernel in use (the float16 form has its own kernel)
 inline int dict_tile(const kpdi_ctx *c) { return uses16(c) ? f16_geometry(c->f16_waves).dict_tile : TILE_DICT; }
 // lists per pattern and dictionary split the match kernel writes
-inline int lists_per_split(const kpdi_ctx *c) { return uses16(c) ? 4 : 2; }
+inline int lists_per_split(const kpdi_ctx *c) { return plan::lists_per_split(operand_form(c)); }
 // entries ranked per pass when keep_n needs several (bounded) passes
 inline int pass_entries(const kpdi_ctx *c) { return c->wide32 ? 20 : KMAX_LIMIT; }
 // the planner's view of this context (plan.h)
@@ -523,10 +518,10 @@ inline plan::Env plan_env(const kpdi_ctx *c) {
 int flush_preprocess(kpdi_ctx *c, bool with_prep, bool *prep_done);
 int prepare_experimental(kpdi_ctx *c);
 int ensure_running(kpdi_ctx *c);
-int run_match(kpdi_ctx *c, const float *dict_y, int n_chunk, int n_tiles, int nsplit, int rows_per_launch, int list_len,
-              int64_t global_start, const float *bound_s, const int *bound_i, bool allow_tail = false);
-int local_pass(kpdi_ctx *c, const float *y, int n_chunk, int n_tiles, int nsplit, int rows_per_launch, int64_t global_start,
-               int done, int kp, int stride);
+// launches `pl` as it stands (plan.h: sweep_plan); a bounded plan comes with its bound
+int run_match(kpdi_ctx *c, const float *dict_y, const plan::SweepPlan &pl, int64_t global_start, const float *bound_s, const int *bound_i);
+// `chunk`: the plan of the chunk's sweep (one without tails); the pass derives its own from it
+int local_pass(kpdi_ctx *c, const float *y, const plan::SweepPlan &chunk, int64_t global_start, int done, int kp, int stride);
 int prepare_chunk(kpdi_ctx *c, const void *d_patterns, int dtype, int64_t n_chunk, float *out);
 void decide_form(kpdi_ctx *c, int64_t n_chunk);
 int check_chunk_args(kpdi_ctx *c, int dtype, int64_t n_chunk, int64_t global_start);
@@ -551,8 +546,7 @@ void release_held(kpdi_ctx *c);
 
 // ---- exact64.hip
 int resolve_exact64(kpdi_ctx *c);
-int sweep_exact64(kpdi_ctx *c, const float *y, int64_t n_chunk, int64_t global_start, const void *raw, int raw_dtype, int n_tiles,
-                  int nsplit, int rows_per_launch);
+int sweep_exact64(kpdi_ctx *c, const float *y, const plan::SweepPlan &chunk, int64_t global_start, const void *raw, int raw_dtype);
 int finalize64(kpdi_ctx *c, double *scores64, float *scores32, int64_t *indices_out);
 
 // ---- finalize.hip

@@ -19,10 +19,11 @@ static int exact64_passes(kpdi_ctx *c, int64_t target) {
   kpdi_ctx::Pending64 &q = c->pend64;
   const int k = c->keep_n;
   const int pass = pass_entries(c);
+  const int64_t n_chunk = q.plan.req.n_chunk;
   unsigned *cert = c->cert64.as<unsigned>();
   while (q.done < target) {
     const int kp = (int)std::min<int64_t>(q.done == 0 ? kpdi::KMAX_LIMIT : pass, target - q.done);
-    int rc = local_pass(c, q.y, (int)q.n_chunk, q.n_tiles, q.nsplit, q.rows_per_launch, q.global_start, q.done, kp, q.cap);
+    int rc = local_pass(c, q.y, q.plan, q.global_start, q.done, kp, q.cap);
     if (rc) return rc;
     ScopedTimer t(c, &c->ev_rescore);
     kpdi::RescoreLaunch r{};
@@ -31,7 +32,7 @@ static int exact64_passes(kpdi_ctx *c, int64_t target) {
     r.row_map = c->have_nav_mask ? c->row_map.as<int>() : nullptr;
     r.dict_raw = q.raw;
     r.dict_dtype = q.raw_dtype;
-    r.n_chunk = q.n_chunk;
+    r.n_chunk = n_chunk;
     r.global_start = q.global_start;
     r.pix_map = c->have_sig_mask ? c->pix_map.as<int>() : nullptr;
     r.k = c->k_kept;
@@ -64,7 +65,7 @@ static int exact64_passes(kpdi_ctx *c, int64_t target) {
     g.cand_s32 = c->loc_s.as<float>();
     g.s32_stride = q.cap;
     g.s32_col = q.done + kp - 1;
-    g.enumerated_all = q.done + kp >= q.n_chunk;
+    g.enumerated_all = q.done + kp >= n_chunk;
     g.max_diff = cert;
     // what an unscreened candidate's float64 score may exceed its float32 score by: at least the worst-case
     // accumulation bound of a K-term float32 dot product of unit vectors, (K + 2) 2^-24 (2.1e-4 at K = 3600) - a
@@ -91,17 +92,18 @@ static int exact64_passes(kpdi_ctx *c, int64_t target) {
 int resolve_exact64(kpdi_ctx *c) {
   kpdi_ctx::Pending64 &q = c->pend64;
   if (!q.active) return KPDI_OK;
+  const int64_t n_chunk = q.plan.req.n_chunk;
   q.active = false;  // (an error below leaves no half-resolved chunk behind)
   bool more = false;
   int uncertified = 0;
   for (;;) {
     HIPCHK(hipEventSynchronize(q.ready));
     uncertified = *(volatile int *)q.flag.p;
-    if (uncertified == 0 || q.done >= q.n_chunk || q.extra == EXTRA64) break;
+    if (uncertified == 0 || q.done >= n_chunk || q.extra == EXTRA64) break;
     ++q.extra;
     c->cnt.rescore_extra_passes += 1;
     more = true;
-    int rc = exact64_passes(c, std::min<int64_t>((int64_t)q.done + pass_entries(c), q.n_chunk));
+    int rc = exact64_passes(c, std::min<int64_t>((int64_t)q.done + pass_entries(c), n_chunk));
     if (rc) return rc;
   }
   c->cnt.uncertified_patterns += uncertified;
@@ -116,9 +118,9 @@ int resolve_exact64(kpdi_ctx *c) {
 // screening passes of 32 candidates.  The verdict of the first passes is read back asynchronously: a caller streaming
 // host chunks (kpdi_push_dictionary_chunk) looks at it only after the NEXT chunk's upload has been queued, so that
 // upload and sweep overlap as they do in the float32 modes; everyone else resolves it before returning.
-int sweep_exact64(kpdi_ctx *c, const float *y, int64_t n_chunk, int64_t global_start, const void *raw, int raw_dtype,
-                  int n_tiles, int nsplit, int rows_per_launch) {
+int sweep_exact64(kpdi_ctx *c, const float *y, const plan::SweepPlan &chunk, int64_t global_start, const void *raw, int raw_dtype) {
   const int k = c->keep_n;
+  const int64_t n_chunk = chunk.req.n_chunk;
   if ((int64_t)k + MARGIN64 > 4096) return fail(KPDI_EINVAL, "float64 arithmetic supports keep_n <= %d", 4096 - MARGIN64);
   const int pass = pass_entries(c);
   const int cap = kpdi::round_up(k + MARGIN64, pass) + pass * EXTRA64;
@@ -137,13 +139,10 @@ int sweep_exact64(kpdi_ctx *c, const float *y, int64_t n_chunk, int64_t global_s
   q.y = y;
   q.raw = raw;
   q.raw_dtype = raw_dtype;
-  q.n_tiles = n_tiles;
-  q.nsplit = nsplit;
-  q.rows_per_launch = rows_per_launch;
+  q.plan = chunk;
   q.cap = cap;
   q.done = 0;
   q.extra = 0;
-  q.n_chunk = n_chunk;
   q.global_start = global_start;
   int rc = exact64_passes(c, std::min<int64_t>((int64_t)k + MARGIN64, n_chunk));
   if (rc) return rc;

@@ -1,8 +1,11 @@
 // plan.h - the launch planner of a sweep: pure functions of the problem (experimental patterns M, dictionary patterns of
 // the chunk n, kept pixels K, keep_n), the device (compute units) and the developer switches - no HIP call, no context.
-// sweep.hip asks it how to lay a chunk on the chip; kpdi_plan_describe (include/kpdi.h) exports the answer so that
-// tests/test_planner.py can check the invariants on a machine without a GPU: every row block covered exactly once,
-// padded grids at most 9/8 of the rows, no launch without tiles, for shares of 1 ... 300 000 patterns.
+// There is ONE plan per sweep, a plan::SweepPlan, and one function that fills it, plan::sweep_plan: sweep.hip builds the
+// request of a chunk and launches the plan it gets, kpdi_plan_describe (include/kpdi.h, plan.hip) builds the request the
+// engine would build and reports the same object - so that tests/test_planner.py checks the engine's own decisions on a
+// machine without a GPU: every row block covered exactly once, padded grids at most 9/8 of the rows, no launch without
+// tiles, for shares of 1 ... 300 000 patterns.  The primitives in front of it (choose_nsplit, xcd_grid, the tails, the
+// tile order) are the arithmetic; sweep_plan is the only place that says when each applies.
 //
 // Units of the cost model: the time of one 128-pattern dictionary tile of match.hip against one 256-pattern row block
 // (form_model.h holds the fitted constants).
@@ -214,6 +217,113 @@ inline int classic_fixed_draws(const Env &e, int n_main, int nsplit, int tail_ti
   const double frac = e.sw.fixed_frac;
   const int per_wg = n_main / nsplit;
   return (tail_tiles > 0 || n_main % nsplit == 0) && frac > 0 ? per_wg + 1 : std::max(3, (int)(frac * per_wg));
+}
+
+// ---- the plan of one sweep: everything above, decided once ---------------------------------------------------------------
+inline int lists_per_split(int form) { return form >= 2 ? 4 : 2; }  // lists per pattern and split the match kernel writes
+
+// What a sweep is asked to do.  `form`: operand form of the prepared matrices (kernels.h: 0 f32 tiled and 1 split f16 are
+// match.hip's, 2 float16 and 3 f32 plane-major match16.hip's); `tile`: dictionary patterns per tile of that kernel;
+// `list_len`: entries of a partial list (match_list_len); `bounded`: a pass that only admits candidates ranked after a
+// bound (keep_n > 32, float64 screening); `allow_tail`: the last partial round may go to a launch of its own.
+struct SweepRequest {
+  int form = 0, tile = TILE_DICT, row_blocks = 1;
+  int64_t n_chunk = 0;
+  int list_len = 0;
+  bool bounded = false, allow_tail = false;
+  bool operator==(const SweepRequest &o) const {
+    return form == o.form && tile == o.tile && row_blocks == o.row_blocks && n_chunk == o.n_chunk && list_len == o.list_len &&
+           bounded == o.bounded && allow_tail == o.allow_tail;
+  }
+};
+
+// one match launch: its row blocks and how the XCDs tile its rows_grid x nsplit workgroups (xcd_grid)
+struct Launch {
+  int row_first = 0, rows = 0, xcd_rows = 0, xcd_splits = 0, rows_grid = 0;
+};
+
+// How the chunk is laid on the chip: filled by sweep_plan() (and re-listed by pass()), by nobody else.
+struct SweepPlan {
+  SweepRequest req;
+  int n_tiles = 0, nsplit = 1, rows_per_launch = 1, launches = 1;
+  int n_main = 0;                                                        // tiles of the main launch(es)
+  int tail_tiles = 0, tail_units = 0, tail_nsplit = 0, fixed_draws = 3;  // match.hip: classic_tail_tiles, classic_fixed_draws
+  int tail_first = 0, tail_shift = 0, gemm_rows = 0;                     // match16.hip f32: wide_tail, or wide_gemm_tail's rows
+  int perm_rounds = 0, perm_stride = 1;                                  // match16.hip: tile_order_stride
+  int bound_rank = 1, bound_grouped = 0, bound_used = 0;                 // kernels.h: bound_plan
+  Launch full, last;  // the launches but the last are alike; of a single launch both are that one
+  int grid_rows = 0;  // the largest padded grid of the sweep's launches, in row blocks
+  Launch launch(int j) const {
+    Launch l = j + 1 < launches ? full : last;
+    l.row_first = j * rows_per_launch;
+    return l;
+  }
+  // the published ranks of the shared bound are only comparable under one bound plan
+  int bound_key() const { return (bound_rank << 8) | (bound_grouped << 7) | bound_used; }
+  // one screening pass over the same chunk (sweep.hip: local_pass): this plan - one without tails - with the pass's lists
+  SweepPlan pass(int list_len, bool bounded) const {
+    SweepPlan p = *this;
+    p.req.list_len = list_len;
+    p.req.bounded = bounded;
+    bound_plan(lists_per_split(req.form) * nsplit, list_len, &p.bound_rank, &p.bound_grouped, &p.bound_used);
+    return p;
+  }
+  // (for one Env - a context's, between two kpdi_set_problem - a plan is a function of its request)
+  bool operator==(const SweepPlan &o) const { return req == o.req; }
+};
+
+// THE plan of a sweep.  The primitives above keep their arithmetic; here are the conditions under which each applies:
+// match.hip's tail launch only in its f32 form, tailgemm.hip only for an unbounded sweep of match16.hip's f32 form (both
+// only where a tail is allowed), partial units inside that kernel whenever tailgemm.hip does not take the tail, a permuted
+// tile order - whole rounds only, partial units stay last - in both of match16.hip's forms.
+inline SweepPlan sweep_plan(const Env &e, const SweepRequest &r) {
+  SweepPlan p;
+  p.req = r;
+  const bool k16 = r.form >= 2;  // match16.hip's kernels: static hand-out, padded grids
+  p.n_tiles = (int)((r.n_chunk + r.tile - 1) / r.tile);
+  p.rows_per_launch = r.row_blocks;
+  p.nsplit = choose_nsplit(e, k16, r.row_blocks, p.n_tiles, &p.rows_per_launch);
+  p.launches = (r.row_blocks + p.rows_per_launch - 1) / p.rows_per_launch;
+  if (r.form == 0 && r.allow_tail) p.tail_tiles = classic_tail_tiles(e, p.n_tiles, p.nsplit, p.launches == 1, r.bounded);
+  p.n_main = p.n_tiles - p.tail_tiles;
+  if (p.tail_tiles > 0) {
+    p.tail_units = (int)((std::min(r.n_chunk, (int64_t)p.n_tiles * TILE_DICT) - (int64_t)p.n_main * TILE_DICT + 31) / 32);
+    p.tail_nsplit = std::min(p.nsplit, p.tail_units);
+  }
+  if (r.form == 3) {
+    int rows = 0;
+    const double inside = wide_tail(e, p.n_tiles, p.nsplit, &p.tail_shift);
+    p.tail_first = p.n_tiles - p.n_tiles % p.nsplit;
+    if (r.allow_tail && !r.bounded && wide_gemm_tail(e, r.row_blocks, p.n_tiles, p.nsplit, r.n_chunk, &rows) < inside && rows > 0) {
+      p.gemm_rows = rows;
+      p.n_main = p.tail_first;
+      p.tail_shift = 0;
+    }
+  }
+  if (k16) p.perm_stride = tile_order_stride(e, p.tail_shift > 0 ? p.tail_first : p.n_main, p.nsplit, &p.perm_rounds);
+  p.fixed_draws = classic_fixed_draws(e, p.n_main, p.nsplit, p.tail_tiles);
+  bound_plan(lists_per_split(r.form) * p.nsplit, r.list_len, &p.bound_rank, &p.bound_grouped, &p.bound_used);
+  p.full.rows = std::min(p.rows_per_launch, r.row_blocks);
+  p.last.rows = r.row_blocks - (p.launches - 1) * p.rows_per_launch;
+  for (Launch *l : {&p.full, &p.last}) {
+    xcd_grid(e, l->rows, p.nsplit, r.tile, k16, &l->xcd_rows, &l->xcd_splits, &l->rows_grid);
+    p.grid_rows = std::max(p.grid_rows, l->rows_grid);
+  }
+  return p;
+}
+
+// The request of a chunk's sweep: up to KMAX_LIMIT entries per pattern are ranked by ONE set of launches, tails allowed;
+// longer lists and the screening of float64 arithmetic take passes (SweepPlan::pass gives each its list length and
+// bound) that share this shape and launch no tail.
+inline SweepRequest chunk_request(int form, int tile, int row_blocks, int64_t n_chunk, int keep_n, bool screening) {
+  SweepRequest r;
+  r.form = form;
+  r.tile = tile;
+  r.row_blocks = row_blocks;
+  r.n_chunk = n_chunk;
+  r.allow_tail = !screening && keep_n <= KMAX_LIMIT;
+  r.list_len = r.allow_tail ? match_list_len(keep_n) : 0;
+  return r;
 }
 
 // Which f32 match kernel serves a sweep whose chunks hold n_chunk patterns.  match16.hip's one-wave-per-SIMD form

@@ -1,4 +1,6 @@
-// plan.hip - kpdi_plan_describe (include/kpdi.h): what the planner of plan.h decides for a sweep, as plain data.  Host
+// plan.hip - kpdi_plan_describe (include/kpdi.h): the plan::SweepPlan that sweep.hip would launch for a sweep, as plain
+// data.  It builds the engine's request (plan.h: chunk_request; for keep_n > 32 the first pass of it) and copies what
+// plan::sweep_plan answers - no planning of its own; the fields of the kernel form that is not in use read 0.  Host
 // arithmetic only: callable without a GPU (tests/test_planner.py).
 #include "../../include/kpdi.h"
 #include "group_hooks.h"
@@ -14,52 +16,40 @@ extern "C" int kpdi_plan_describe(int64_t m, int64_t n_chunk, int k_kept, int ke
   e.n_cu = n_cu;
   e.blocks_per_cu = match_blocks_per_cu();
   e.sw.read();
-  *out = kpdi_plan{};
-  const int m_pad = round_up(m, TILE_EXP), row_blocks = m_pad / TILE_EXP;
+  const int row_blocks = round_up(m, TILE_EXP) / TILE_EXP;
   const bool wide = form < 0 ? plan::prefer_wide(e, row_blocks, k_kept, n_chunk) : form == 3;
-  const int tile = wide ? F16_TILE : TILE_DICT;
-  const int n_tiles = round_up(n_chunk, tile) / tile;
-  int rpl = row_blocks;
-  const int nsplit = plan::choose_nsplit(e, wide, row_blocks, n_tiles, &rpl);
-  out->form = wide ? 3 : 0;
-  out->tile = tile;
+  plan::SweepPlan p = plan::sweep_plan(e, plan::chunk_request(wide ? 3 : 0, wide ? F16_TILE : TILE_DICT, row_blocks, n_chunk, keep_n, false));
+  if (!p.req.allow_tail) p = p.pass(match_list_len((int)std::min<int64_t>(KMAX_LIMIT, n_chunk)), false);  // (sweep.hip: the first local_pass)
+  *out = kpdi_plan{};
+  out->form = p.req.form;
+  out->tile = p.req.tile;
   out->row_blocks = row_blocks;
-  out->n_tiles = n_tiles;
-  out->nsplit = nsplit;
-  out->rows_per_launch = rpl;
-  out->launches = (row_blocks + rpl - 1) / rpl;
+  out->n_tiles = p.n_tiles;
+  out->nsplit = p.nsplit;
+  out->rows_per_launch = p.rows_per_launch;
+  out->launches = p.launches;
   out->round_rows = plan::round_rows(e, row_blocks);
-  const bool bounded = keep_n > KMAX_LIMIT;  // (passes after the first are bounded; the first pass plans like a plain sweep)
+  out->n_main = p.n_main;
   if (!wide) {
-    out->tail_tiles = plan::classic_tail_tiles(e, n_tiles, nsplit, row_blocks <= rpl, false);
-    out->n_main = n_tiles - out->tail_tiles;
-    out->fixed_draws = plan::classic_fixed_draws(e, out->n_main, nsplit, out->tail_tiles);
-    if (out->tail_tiles > 0) {
-      out->tail_units = (int)((std::min<int64_t>(n_chunk, (int64_t)n_tiles * TILE_DICT) - (int64_t)out->n_main * TILE_DICT + 31) / 32);
-      out->tail_nsplit = std::min(nsplit, out->tail_units);
-    }
+    out->tail_tiles = p.tail_tiles;
+    out->tail_units = p.tail_units;
+    out->tail_nsplit = p.tail_nsplit;
+    out->fixed_draws = p.fixed_draws;
   } else {
-    out->n_main = n_tiles;
-    const double inside = plan::wide_tail(e, n_tiles, nsplit, &out->tail_shift);
-    out->tail_first = n_tiles - n_tiles % nsplit;
-    int rows = 0;
-    if (!bounded && plan::wide_gemm_tail(e, row_blocks, n_tiles, nsplit, n_chunk, &rows) < inside && rows > 0) {
-      out->tail_gemm_rows = rows;  // (sweep.hip: match_setup)
-      out->n_main = out->tail_first;
-      out->tail_shift = 0;
-    }
-    out->perm_stride = plan::tile_order_stride(e, (out->tail_shift > 0 || rows > 0) ? out->tail_first : n_tiles, nsplit, &out->perm_rounds);
+    out->tail_first = p.tail_first;
+    out->tail_shift = p.tail_shift;
+    out->tail_gemm_rows = p.gemm_rows;
+    out->perm_rounds = p.perm_rounds;
+    out->perm_stride = p.perm_stride;
   }
-  for (int r0 = 0, j = 0; r0 < row_blocks; r0 += rpl, ++j) {
-    if (j >= KPDI_PLAN_MAX_LAUNCHES) {
-      out->n_launch_desc = KPDI_PLAN_MAX_LAUNCHES;
-      return KPDI_OK;  // (`launches` says how many there are; the first KPDI_PLAN_MAX_LAUNCHES are described)
-    }
-    out->launch[j].row_first = r0;
-    out->launch[j].rows = std::min(rpl, row_blocks - r0);
-    plan::xcd_grid(e, out->launch[j].rows, nsplit, tile, wide, &out->launch[j].xcd_rows, &out->launch[j].xcd_splits,
-                   &out->launch[j].rows_grid);
-    out->n_launch_desc = j + 1;
+  out->n_launch_desc = std::min(p.launches, KPDI_PLAN_MAX_LAUNCHES);  // (`launches` says how many there are)
+  for (int j = 0; j < out->n_launch_desc; ++j) {
+    const plan::Launch l = p.launch(j);
+    out->launch[j].row_first = l.row_first;
+    out->launch[j].rows = l.rows;
+    out->launch[j].xcd_rows = l.xcd_rows;
+    out->launch[j].xcd_splits = l.xcd_splits;
+    out->launch[j].rows_grid = l.rows_grid;
   }
   return KPDI_OK;
 }

@@ -1,6 +1,9 @@
-// sweep.hip - one dictionary chunk against the resident experimental set: preparation, the match launch(es) the
-// planner (plan.h) lays out, the merge into the running best-k; the upload pipeline of host chunks; resident (held)
-// chunks; and the C ABI entry points that push / hold chunks (include/kpdi.h).
+// sweep.hip - one dictionary chunk against the resident experimental set: preparation, the match launch(es) of the
+// chunk's plan, the merge into the running best-k; the upload pipeline of host chunks; resident (held) chunks; and the C
+// ABI entry points that push / hold chunks (include/kpdi.h).
+// There is one plan per sweep, the plan::SweepPlan that plan::sweep_plan (plan.h) fills: chunk_plan below asks for it once
+// per chunk, run_match launches it and reads the counters from it, local_pass and exact64.hip hand it on.  Nothing in
+// this file calls a primitive of the planner that decides a launch's shape.
 // (one of the host translation units api.hip was split into in round 5: context.h holds what they share)
 #include "context.h"
 
@@ -130,79 +133,50 @@ int ensure_running(kpdi_ctx *c) {
   return KPDI_OK;
 }
 
-// one match launch over the prepared chunk -> partial lists
+// ---- the match launches of one plan (plan.h: SweepPlan) over the prepared chunk -> partial lists ----------------------
+// Nothing below decides how the chunk is laid on the chip: chunk_plan asks plan::sweep_plan once per chunk, match_setup
+// queues the fills that plan needs, run_match launches it as it stands (tails included: match.hip's quarter tiles join
+// the merge as a third source, tailgemm.hip's select list likewise), local_pass derives a pass's plan from the chunk's.
 //
-// Tail: the dictionary tiles of a row block are shared by `nsplit` workgroups; when their number is a
-// small non-multiple of nsplit (a rank's share of a sharded dictionary: 98 tiles over 16 workgroups)
-// whole tiles would leave most workgroups idle during the last round (makespan 7 tile-times for 6.1 of
-// work).  The last n_tiles % nsplit tiles are then handed out as QUARTER tiles by a second launch of the
-// kernel's 32-row form, whose lists join the merge as a third source.
-// What a match launch needs initialised before it starts - the shared bound (when its plan changes), the tile counters of
-// the main and the tail launch - is QUEUED here (queue_fill), so that it shares one launch with whatever else the sweep
-// initialises; the plan itself is returned for run_match.
-typedef kpdi_ctx::MatchPlan MatchPlan;
-static int match_setup(kpdi_ctx *c, int n_chunk, int n_tiles, int nsplit, int rows_per_launch, int list_len, bool bounded,
-                bool allow_tail, MatchPlan *pl) {
-  const int row_blocks = c->m_pad / kpdi::TILE_EXP;
-  *pl = MatchPlan{};
-  if (allow_tail && c->compute == KPDI_COMPUTE_F32 && !c->wide32)
-    pl->tail_tiles = plan::classic_tail_tiles(plan_env(c), n_tiles, nsplit, row_blocks <= rows_per_launch, bounded);
-  pl->n_main = n_tiles - pl->tail_tiles;
-  if (allow_tail && c->compute == KPDI_COMPUTE_F32 && c->wide32 && !bounded) {
-    // float32 form of match16.hip: the last partial round inside the kernel (halves / quarters of a tile) or as a kernel
-    // of its own (tailgemm.hip), whichever the model prices lower
-    int shift = 0, rows = 0;
-    const double inside = plan::wide_tail(plan_env(c), n_tiles, nsplit, &shift);
-    const double own = plan::wide_gemm_tail(plan_env(c), row_blocks, n_tiles, nsplit, n_chunk, &rows);
-    if (rows > 0 && own < inside) {
-      pl->gemm_rows = rows;
-      pl->n_main = n_tiles - n_tiles % nsplit;
-    }
-  }
-  {
-    // the published ranks are only comparable under one plan: (re)initialise when it changes
-    int used;
-    kpdi::bound_plan(lists_per_split(c) * nsplit, list_len, &pl->bound_rank, &pl->bound_grouped, &used);
-    const int key = (pl->bound_rank << 8) | (pl->bound_grouped << 7) | used;
-    if (key != c->bound_key || bounded) {
-      HIPCHK(c->gthr.reserve((size_t)c->m_pad * kpdi::BOUND_SLOTS * sizeof(unsigned)));
-      int rc = queue_fill(c, c->gthr.p, (size_t)c->m_pad * kpdi::BOUND_SLOTS, 0u, used);
-      if (rc) return rc;
-      c->bound_key = bounded ? -1 : key;  // bounded passes always start from scratch
-    }
-  }
-  pl->fixed_draws = plan::classic_fixed_draws(plan_env(c), pl->n_main, nsplit, pl->tail_tiles);
-  const size_t ctr_words = (size_t)row_blocks;
-  HIPCHK(c->tile_ctr.reserve(2 * ctr_words * sizeof(unsigned)));  // second half: the tail launch
-  int rc = queue_fill(c, c->tile_ctr.p, ctr_words, (unsigned)pl->fixed_draws * (unsigned)nsplit);
-  if (rc) return rc;
-  if (pl->tail_tiles > 0) {
-    pl->tail_units = (std::min(n_chunk, n_tiles * kpdi::TILE_DICT) - pl->n_main * kpdi::TILE_DICT + 31) / 32;
-    pl->tail_nsplit = std::min(nsplit, pl->tail_units);
-    rc = queue_fill(c, c->tile_ctr.as<unsigned>() + ctr_words, ctr_words, 3u * (unsigned)pl->tail_nsplit);
+// What the launches of a plan need initialised before they start - the shared bound (when its plan changes, and for every
+// bounded pass), the tile counters of the main and the tail launch - is QUEUED here (queue_fill), so that it shares one
+// launch with whatever else the sweep initialises.
+static int match_setup(kpdi_ctx *c, const plan::SweepPlan &pl) {
+  if (pl.bound_key() != c->bound_key || pl.req.bounded) {
+    HIPCHK(c->gthr.reserve((size_t)c->m_pad * kpdi::BOUND_SLOTS * sizeof(unsigned)));
+    int rc = queue_fill(c, c->gthr.p, (size_t)c->m_pad * kpdi::BOUND_SLOTS, 0u, pl.bound_used);
     if (rc) return rc;
+    c->bound_key = pl.req.bounded ? -1 : pl.bound_key();  // bounded passes always start from scratch
   }
-  return KPDI_OK;
+  const size_t ctr_words = (size_t)pl.req.row_blocks;
+  HIPCHK(c->tile_ctr.reserve(2 * ctr_words * sizeof(unsigned)));  // second half: the tail launch
+  int rc = queue_fill(c, c->tile_ctr.p, ctr_words, (unsigned)pl.fixed_draws * (unsigned)pl.nsplit);
+  if (rc) return rc;
+  if (pl.tail_tiles > 0) rc = queue_fill(c, c->tile_ctr.as<unsigned>() + ctr_words, ctr_words, 3u * (unsigned)pl.tail_nsplit);
+  return rc;
 }
 
-int run_match(kpdi_ctx *c, const float *dict_y, int n_chunk, int n_tiles, int nsplit, int rows_per_launch,
-              int list_len, int64_t global_start, const float *bound_s, const int *bound_i, bool allow_tail) {
-  c->tail_nsplit = 0;
+// the plan of a chunk's sweep (plan.h: chunk_request): the one sweep_raw_chunk has just made and queued the fills of,
+// when there is one - a chunk is planned once
+static plan::SweepPlan chunk_plan(kpdi_ctx *c, int64_t n_chunk) {
+  const plan::SweepRequest rq =
+      plan::chunk_request(operand_form(c), dict_tile(c), c->m_pad / kpdi::TILE_EXP, n_chunk, c->keep_n, c->exact64);
+  return c->queued_valid && c->queued.req == rq ? c->queued : plan::sweep_plan(plan_env(c), rq);
+}
+
+int run_match(kpdi_ctx *c, const float *dict_y, const plan::SweepPlan &pl, int64_t global_start, const float *bound_s,
+              const int *bound_i) {
   c->tail_lists = 0;
-  MatchPlan pl;
-  const kpdi_ctx::MatchSetup &ps = c->presetup;
-  if (ps.valid && ps.n_chunk == n_chunk && ps.n_tiles == n_tiles && ps.nsplit == nsplit && ps.rows_per_launch == rows_per_launch &&
-      ps.list_len == list_len && bound_s == nullptr && allow_tail) {
-    pl = c->preplan;  // queued (and flushed with the preparation's own initialisations) by push_chunk_dev
-  } else {
-    int rc = match_setup(c, n_chunk, n_tiles, nsplit, rows_per_launch, list_len, bound_s != nullptr, allow_tail, &pl);
+  if (!(c->queued_valid && c->queued == pl)) {  // (else: queued, and flushed with the preparation's own fills, by sweep_raw_chunk)
+    int rc = match_setup(c, pl);
     if (rc) return rc;
   }
-  c->presetup.valid = false;
+  c->queued_valid = false;
   {
     int rc = flush_fills(c);
     if (rc) return rc;
   }
+  const int n_chunk = (int)pl.req.n_chunk, nsplit = pl.nsplit, list_len = pl.req.list_len, row_blocks = pl.req.row_blocks;
   const int tail_tiles = pl.tail_tiles, n_main = pl.n_main;
   const bool f16 = uses16(c);
   const int lists_per_split = kpdi::lists_per_split(c);
@@ -226,37 +200,30 @@ int run_match(kpdi_ctx *c, const float *dict_y, int n_chunk, int n_tiles, int ns
   ml.part_cnt = f16 ? c->part_cnt.as<int>() : nullptr;
   ml.bound_score = bound_s;
   ml.bound_idx = bound_i;
-  ml.operand_form = operand_form(c);
-  if (c->wide32 && pl.gemm_rows == 0) {  // (float32 form only: the same guards in the float16 schedule cost its 32-cycle MFMAs 10 %)
-    (void)plan::wide_tail(plan_env(c), n_main, nsplit, &ml.tail_shift);
-    ml.tail_first = n_main - n_main % nsplit;
-  }
-  if (f16) {
-    // whole-tile rounds are walked in a permuted order (plan.h: tile_order_stride); partial units stay last
-    const int whole = (c->wide32 && ml.tail_shift > 0) ? ml.tail_first : n_main;
-    ml.perm_stride = plan::tile_order_stride(plan_env(c), whole, nsplit, &ml.perm_rounds);
-    if (c->profiling == 3) {  // the developer level: the epilogues count what they do (~50 us of atomics per launch)
-      if (!c->epi_stats.p) {
-        HIPCHK(c->epi_stats.reserve(4 * sizeof(unsigned long long)));
-        HIPCHK(hipMemsetAsync(c->epi_stats.p, 0, 4 * sizeof(unsigned long long), c->stream));
-      }
-      ml.epi_stats = c->epi_stats.as<unsigned long long>();
+  ml.operand_form = pl.req.form;
+  // (partial units in the float32 form only: the same guards in the float16 schedule cost its 32-cycle MFMAs 10 %)
+  ml.tail_shift = pl.tail_shift;
+  ml.tail_first = pl.tail_first;
+  ml.perm_stride = pl.perm_stride;
+  ml.perm_rounds = pl.perm_rounds;
+  if (f16 && c->profiling == 3) {  // the developer level: the epilogues count what they do (~50 us of atomics per launch)
+    if (!c->epi_stats.p) {
+      HIPCHK(c->epi_stats.reserve(4 * sizeof(unsigned long long)));
+      HIPCHK(hipMemsetAsync(c->epi_stats.p, 0, 4 * sizeof(unsigned long long), c->stream));
     }
+    ml.epi_stats = c->epi_stats.as<unsigned long long>();
   }
   ml.bound_rank = pl.bound_rank;
   ml.bound_grouped = pl.bound_grouped;
   ml.gthr = c->gthr.as<unsigned>();
   ml.tile_groups = 1;
   ml.fixed_draws = pl.fixed_draws;
-  const size_t ctr_bytes = (size_t)(c->m_pad / kpdi::TILE_EXP) * sizeof(unsigned);
   ml.tile_ctr = c->tile_ctr.as<unsigned>();
-  const int row_blocks = c->m_pad / kpdi::TILE_EXP;
-  int launched_rows = 0;
   {
     ScopedTimer t(c, &c->ev_match);  // one timed region = the whole sweep of this chunk
     // several launches (large experimental sets) alternate between two streams: the workgroups
     // of launch j+1 start on the CUs that launch j's tail leaves idle
-    const bool two = row_blocks > rows_per_launch && !c->sw.one_stream;
+    const bool two = pl.launches > 1 && !c->sw.one_stream;
     const bool tail2 = tail_tiles > 0 && c->sw.tail_stream2;  // the tail launch runs on the second stream
     if (two || tail2) {
       if (!c->stream2) {
@@ -267,22 +234,16 @@ int run_match(kpdi_ctx *c, const float *dict_y, int n_chunk, int n_tiles, int ns
       HIPCHK(hipEventRecord(c->ev_fork, c->stream));
       HIPCHK(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
     }
-    int j = 0;
-    // (a launch's grid may be padded, plan_xcd_grid: the largest of the sweep's launches - the full ones and the last one)
-    int grid_rows = 0;
-    const int full_rows = std::min(rows_per_launch, row_blocks);
-    for (int rows : {full_rows, row_blocks % rows_per_launch ? row_blocks % rows_per_launch : full_rows}) {
-      int xr, xs, rg;
-      plan::xcd_grid(plan_env(c), rows, nsplit, dict_tile(c), f16, &xr, &xs, &rg);
-      grid_rows = std::max(grid_rows, rg);
-    }
-    const size_t scratch16 = f16 ? kpdi::match16_scratch_bytes(grid_rows * nsplit, c->f16_waves, list_len) : 0;
-    launched_rows = grid_rows;
+    // (a launch's grid may be padded, plan.h: xcd_grid - the scratch is sized for the largest of the sweep's launches)
+    const size_t scratch16 = f16 ? kpdi::match16_scratch_bytes(pl.grid_rows * nsplit, c->f16_waves, list_len) : 0;
     if (f16) HIPCHK(c->list16.reserve((two ? 2 : 1) * scratch16));
-    for (int r0 = 0; r0 < row_blocks; r0 += rows_per_launch, ++j) {
-      ml.row_first = r0;
-      ml.rows = std::min(rows_per_launch, row_blocks - r0);
-      plan::xcd_grid(plan_env(c), ml.rows, nsplit, dict_tile(c), f16, &ml.xcd_rows, &ml.xcd_splits, &ml.rows_grid);
+    for (int j = 0; j < pl.launches; ++j) {
+      const plan::Launch l = pl.launch(j);
+      ml.row_first = l.row_first;
+      ml.rows = l.rows;
+      ml.xcd_rows = l.xcd_rows;
+      ml.xcd_splits = l.xcd_splits;
+      ml.rows_grid = l.rows_grid;
       hipStream_t st = (two && (j & 1)) ? c->stream2 : c->stream;
       if (f16) {
         // launches on the two streams overlap: each stream has its own list scratch
@@ -314,7 +275,7 @@ int run_match(kpdi_ctx *c, const float *dict_y, int n_chunk, int n_tiles, int ns
       tl.xcd_rows = tl.xcd_splits = tl.rows_grid = 0;
       tl.part_scores = c->tail_s.as<float>();
       tl.part_idx = c->tail_i.as<int>();
-      tl.tile_ctr = c->tile_ctr.as<unsigned>() + ctr_bytes / sizeof(unsigned);  // (initialised with the main launch's)
+      tl.tile_ctr = c->tile_ctr.as<unsigned>() + row_blocks;  // (initialised with the main launch's)
       tl.row_first = 0;
       tl.rows = row_blocks;
       // The tail launch does not depend on the main launch (lists of its own, counters of its own, the shared bound is a
@@ -330,7 +291,6 @@ int run_match(kpdi_ctx *c, const float *dict_y, int n_chunk, int n_tiles, int ns
         HIPCHK(hipEventRecord(c->ev_join, c->stream2));
         HIPCHK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
       }
-      c->tail_nsplit = ns_t;
       c->tail_lists = 2 * ns_t;
     }
     if (pl.gemm_rows > 0) {
@@ -365,9 +325,9 @@ int run_match(kpdi_ctx *c, const float *dict_y, int n_chunk, int n_tiles, int ns
     }
   }
   c->cnt.match_launches += 1;
-  c->cnt.match_form = operand_form(c);
+  c->cnt.match_form = pl.req.form;
   c->cnt.match_flops += 2.0 * (double)c->m * (double)n_chunk * (double)c->k_kept;
-  c->cnt.match_grid = launched_rows * nsplit;  // workgroups of the sweep's largest launch (its padding included)
+  c->cnt.match_grid = pl.grid_rows * nsplit;  // workgroups of the sweep's largest launch (its padding included)
   c->cnt.match_nsplit = nsplit;
   return KPDI_OK;
 }
@@ -446,19 +406,14 @@ static int sweep_raw_chunk(kpdi_ctx *c, const void *d_patterns, int dtype, int64
   if (!c->exact64 && c->keep_n <= kpdi::KMAX_LIMIT) {
     rc = ensure_running(c);
     if (rc) return rc;
-    kpdi_ctx::MatchSetup &ps = c->presetup;
-    ps.n_chunk = (int)n_chunk;
-    ps.n_tiles = n_pad / tile;
-    const int row_blocks = c->m_pad / kpdi::TILE_EXP;
-    ps.rows_per_launch = row_blocks;
-    ps.nsplit = plan::choose_nsplit(plan_env(c), uses16(c), row_blocks, ps.n_tiles, &ps.rows_per_launch);
-    ps.list_len = kpdi::match_list_len(c->keep_n);
-    rc = match_setup(c, ps.n_chunk, ps.n_tiles, ps.nsplit, ps.rows_per_launch, ps.list_len, false, true, &c->preplan);
+    c->queued_valid = false;
+    c->queued = chunk_plan(c, n_chunk);
+    rc = match_setup(c, c->queued);
     if (rc) return rc;
-    ps.valid = true;
+    c->queued_valid = true;
     if (n_pad > n_chunk) {
       float *out = c->dict_y.as<float>();
-      rc = queue_fill(c, out + (size_t)(ps.n_tiles - 1) * tile * c->kpad, (size_t)tile * c->kpad, 0u);
+      rc = queue_fill(c, out + (size_t)(n_pad / tile - 1) * tile * c->kpad, (size_t)tile * c->kpad, 0u);
       if (rc) return rc;
       c->tail_queued = out;
     }
@@ -618,12 +573,11 @@ int pending_commit(kpdi_ctx *c, int64_t n_chunk, int64_t global_start, bool hold
 // One screening pass over a prepared chunk: the ranks [done, done + kp) of every pattern WITHIN this chunk ->
 // columns done .. of loc_s / loc_i (row stride `stride`); pass p only admits candidates ranked strictly
 // after the last entry of pass p-1 (bound_s / bound_i = the last column so far)
-int local_pass(kpdi_ctx *c, const float *y, int n_chunk, int n_tiles, int nsplit, int rows_per_launch,
-               int64_t global_start, int done, int kp, int stride) {
-  const int len = kpdi::match_list_len(kp);
+int local_pass(kpdi_ctx *c, const float *y, const plan::SweepPlan &chunk, int64_t global_start, int done, int kp, int stride) {
+  const int len = kpdi::match_list_len(kp), nsplit = chunk.nsplit;
   c->bound_key = -1;  // each pass ranks a different slice: its shared bound starts from scratch
-  int rc = run_match(c, y, n_chunk, n_tiles, nsplit, rows_per_launch, len, global_start,
-                     done ? c->bound_s.as<float>() : nullptr, done ? c->bound_i.as<int>() : nullptr);
+  int rc = run_match(c, y, chunk.pass(len, done > 0), global_start, done ? c->bound_s.as<float>() : nullptr,
+                     done ? c->bound_i.as<int>() : nullptr);
   if (rc) return rc;
   kpdi::MergeLaunch pm{};
   pm.m = c->m;
@@ -657,11 +611,8 @@ int sweep_prepared(kpdi_ctx *c, const float *y, int64_t n_chunk, int64_t global_
   if (rc) return rc;
   rc = ensure_running(c);
   if (rc) return rc;
-  const int n_tiles = kpdi::round_up(n_chunk, dict_tile(c)) / dict_tile(c);
-
-  const int row_blocks = c->m_pad / kpdi::TILE_EXP;
-  int rows_per_launch = row_blocks;
-  const int nsplit = plan::choose_nsplit(plan_env(c), uses16(c), row_blocks, n_tiles, &rows_per_launch);
+  const plan::SweepPlan pl = chunk_plan(c, n_chunk);
+  const int nsplit = pl.nsplit;
   const int k = c->keep_n;
   if (c->exact64) {
     if (seg) return fail(KPDI_EINVAL, "float64 arithmetic rescoring reads a chunk's own raw patterns: a dictionary held as coalesced chunks "
@@ -670,7 +621,7 @@ int sweep_prepared(kpdi_ctx *c, const float *y, int64_t n_chunk, int64_t global_
       return fail(KPDI_EINVAL, "float64 arithmetic rescoring reads the RAW dictionary patterns: resident (held) chunks keep "
                                "only the prepared form - push the chunks instead");
     c->final_valid = false;
-    return sweep_exact64(c, y, n_chunk, global_start, raw, raw_dtype, n_tiles, nsplit, rows_per_launch);
+    return sweep_exact64(c, y, pl, global_start, raw, raw_dtype);
   }
   const int cur = c->run_cur, nxt = cur ^ 1;
   c->final_valid = false;
@@ -704,8 +655,8 @@ int sweep_prepared(kpdi_ctx *c, const float *y, int64_t n_chunk, int64_t global_
     mg.seg_sources = ~0u << ns;
   }
   if (k <= kpdi::KMAX_LIMIT) {
-    const int len = kpdi::match_list_len(k);
-    rc = run_match(c, y, (int)n_chunk, n_tiles, nsplit, rows_per_launch, len, idx_base, nullptr, nullptr, true);
+    const int len = pl.req.list_len;
+    rc = run_match(c, y, pl, idx_base, nullptr, nullptr);
     if (rc) return rc;
     mg.src_scores[ns] = c->part_s.as<float>();
     mg.src_idx[ns] = c->part_i.as<int>();
@@ -739,7 +690,7 @@ int sweep_prepared(kpdi_ctx *c, const float *y, int64_t n_chunk, int64_t global_
     if (kk < k) HIPCHK(kpdi::launch_fill_topk(c->loc_s.as<float>(), c->loc_i.as<int>(), (int64_t)n, c->stream));
     for (int done = 0; done < kk;) {  // (the first pass is unbounded: up to 32 entries in every form)
       const int kp = std::min(done == 0 ? kpdi::KMAX_LIMIT : pass_entries(c), kk - done);
-      rc = local_pass(c, y, (int)n_chunk, n_tiles, nsplit, rows_per_launch, idx_base, done, kp, k);
+      rc = local_pass(c, y, pl, idx_base, done, kp, k);
       if (rc) return rc;
       done += kp;
     }

@@ -8,6 +8,7 @@ patterns: every row block is covered exactly once, padded grids hold at most 9/8
 tiles, the tail units cover exactly the tiles the main rounds leave."""
 
 import math
+import os
 
 import numpy as np
 import pytest
@@ -93,6 +94,51 @@ def test_invariants_over_shares_and_map_sizes(form):
     for m in MS:
         for n in SHARES:
             check(_lib.plan_describe(m, n, 3600, 20, N_CU, form), m, n, form)
+
+
+# tests/golden/plan_parent.npz (tools/gen_plan_golden.py): what kpdi_plan_describe answered BEFORE the engine and the
+# description shared one plan::sweep_plan - every scalar field and every launch descriptor, over MS x SHARES
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_parent.npz")
+GOLDEN_SETS = ((-1, 20), (0, 20), (3, 20), (3, 50))  # (form, keep_n), all with k_kept = 3600
+SCALARS = tuple(name for name, _ in _lib.Plan._fields_ if name != "launch")
+LAUNCH_FIELDS = tuple(name for name, _ in _lib.PlanLaunch._fields_)
+
+
+def plan_table(form, keep_n):
+    """Every plan of MS x SHARES as two integer tables: the scalar fields (one row per plan, columns SCALARS) and the
+    described launches of all plans one after the other (columns LAUNCH_FIELDS; n_launch_desc of each plan says how many)."""
+    scalars, launches = [], []
+    for m in MS:
+        for n in SHARES:
+            p = _lib.plan_describe(m, n, 3600, keep_n, N_CU, form)
+            scalars.append([getattr(p, f) for f in SCALARS])
+            launches += [[getattr(p.launch[j], f) for f in LAUNCH_FIELDS] for j in range(p.n_launch_desc)]
+    return np.array(scalars, dtype=np.int64), np.array(launches, dtype=np.int32)
+
+
+@pytest.mark.parametrize("form,keep_n", GOLDEN_SETS)
+def test_plans_are_those_of_the_parent(form, keep_n):
+    """prefer_wide and every primitive of plan.h decide what they decided before the refactor: every recorded field, exactly."""
+    with np.load(GOLDEN) as g:
+        assert tuple(g["scalar_names"]) == SCALARS and tuple(g["launch_names"]) == LAUNCH_FIELDS
+        assert g["ms"].tolist() == list(MS) and g["shares"].tolist() == list(SHARES)
+        want_s, want_l = g[f"scalars__{form}__{keep_n}"], g[f"launches__{form}__{keep_n}"]
+    got_s, got_l = plan_table(form, keep_n)
+    assert got_s.shape == want_s.shape == (len(MS) * len(SHARES), len(SCALARS))
+    bad = np.argwhere(got_s != want_s)
+    assert bad.size == 0, [(MS[i // len(SHARES)], SHARES[i % len(SHARES)], SCALARS[f], int(got_s[i, f]), int(want_s[i, f]))
+                           for i, f in bad[:8]]
+    assert np.array_equal(got_l, want_l)
+
+
+def test_classic_form_of_bounded_passes_has_no_tail_launch():
+    """keep_n > 32 is ranked in passes (sweep.hip: local_pass), none of which launches match.hip's quarter-tile tail: the
+    description says what the engine does (it used to report the tail of a plain sweep)."""
+    for m in MS:
+        for n in SHARES:
+            p = _lib.plan_describe(m, n, 3600, 50, N_CU, 0)
+            check(p, m, n, 0)
+            assert p.tail_tiles == 0 and p.n_main == p.n_tiles and p.tail_units == 0 and p.tail_nsplit == 0, (m, n)
 
 
 def test_known_plans_of_the_benchmark_configurations():
