@@ -623,6 +623,25 @@ int kpdi_refine_solve_powell(kpdi_ctx *ctx, int mode, int64_t n_patterns, int n_
 int kpdi_powell_selftest(kpdi_ctx *ctx, int kind, int nvar, const double *x0, const double *lower,
                          const double *upper, double xtol, double ftol, int maxiter, int maxfev,
                          double *result);
+/* The simplex search NLopt offers as LN_NELDERMEAD, as csrc/nlopt_simplex.h restates it from the text of DESIGN.md
+ * section 21 (NLopt itself is not compared with), from every start of every pattern: each (pattern, start) is one
+ * independent optimisation with its own evaluation count.  lower / upper: both NULL or both given; infinite bounds and
+ * lower == upper (the variable is held) are allowed, NaN is refused.  xstep: NULL (the default step of the text) or
+ * one initial step per variable (nvar values, shared by every job).  maxeval <= 0: no limit; ftol_rel <= 0 together
+ * with maxeval <= 0 is refused, as are starting points and steps that are not finite.
+ * Result rows as kpdi_refine_solve: fun = the lowest value seen, nfev, x = the point it was seen at; the `nit` slot holds
+ * the status (NLopt's codes: 1 success, 3 ftol reached, 4 xtol reached, 5 maxeval reached, -1 failure: a step that
+ * does not move its variable, -2 invalid arguments: a start outside its bounds). */
+int kpdi_refine_solve_nlopt(kpdi_ctx *ctx, int mode, int64_t n_patterns, int n_starts,
+                            const double *x0, const double *fixed, const double *lower,
+                            const double *upper, const double *xstep, double ftol_rel, int maxeval,
+                            double *results);
+/* csrc/nlopt_simplex.h alone on an analytic f64 objective, nvar <= 6: kinds 0..4 of kpdi_powell_selftest, 5: the sum
+ * of (i + 1) |d| / (1 + |d|), d = x[i] - 0.3 (i + 1), whose concave arms make contractions fail (the shrink step).
+ * result: fun, nfev, status, x[0..nvar). */
+int kpdi_nlopt_simplex_selftest(kpdi_ctx *ctx, int kind, int nvar, const double *x0,
+                                const double *lower, const double *upper, const double *xstep,
+                                double ftol_rel, int maxeval, double *result);
 
 /* The top-k merge kernels alone, on lists the caller makes (tests/test_gpu_merge.py): everything is host memory.
  * kpdi_merge_selftest: n_src <= 3 sources; src_scores / src_idx / src_cnt are arrays of n_src host pointers

@@ -186,6 +186,8 @@ SIGNATURES = {
     "kpdi_refine_solve_powell": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i, _i, _vp, _i64, _vp,
                                       _i]),
     "kpdi_powell_selftest": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _i, _i, _vp]),
+    "kpdi_refine_solve_nlopt": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),
+    "kpdi_nlopt_simplex_selftest": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),
     "kpdi_merge_selftest": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.c_uint32,
                                  _vp, _vp, _i, _vp, _vp]),
     "kpdi_merge64_selftest": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _i, _i, _i64, _i64, _vp, _i, _i, _i,
@@ -955,6 +957,32 @@ class Context:
         """csrc/powell.h alone on an analytic objective (kpdi_powell_selftest): fun, nfev, nit, status, x."""
         return self._optimiser_selftest(self._f.powell_selftest, 4, kind, x0, lower, upper, xtol, ftol, maxiter, maxfev)
 
+    def refine_solve_nlopt(self, mode, x0, fixed=None, lower=None, upper=None, xstep=None, ftol_rel=1e-4, maxeval=0):
+        """The LN_NELDERMEAD search of csrc/nlopt_simplex.h from every start on the device (kpdi_refine_solve_nlopt).
+        x0: (n_patterns, n_starts, nvar); bounds: none or both (infinite allowed); xstep: None (the default step) or
+        nvar initial steps.  Returns the (n_patterns, n_starts, 3 + nvar) rows fun, nfev, status, x."""
+        nvar, x0, f, lo, hi, res = self._solve_arrays(mode, x0, fixed, lower, upper)
+        step = None
+        if xstep is not None:
+            step = np.ascontiguousarray(xstep, dtype=np.float64).ravel()
+            if step.size != nvar:
+                raise KpdiError(f"xstep must have {nvar} values")
+        check(self._f.refine_solve_nlopt(self._h, int(mode), x0.shape[0], x0.shape[1], _ptr(x0), _ptr(f), _ptr(lo),
+                                         _ptr(hi), _ptr(step), float(ftol_rel), int(maxeval or 0), _ptr(res)))
+        return res[:, :, :3 + nvar]
+
+    def nlopt_simplex_selftest(self, kind, x0, lower=None, upper=None, xstep=None, ftol_rel=0.0, maxeval=0):
+        """csrc/nlopt_simplex.h alone on an analytic objective (kpdi_nlopt_simplex_selftest): fun, nfev, status, x."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).ravel()
+        lo, hi, step = (None if a is None else np.ascontiguousarray(a, dtype=np.float64).ravel()
+                        for a in (lower, upper, xstep))
+        if any(a is not None and a.size != x0.size for a in (lo, hi, step)):
+            raise KpdiError("lower, upper and xstep must have one value per variable")
+        res = np.empty(3 + x0.size, dtype=np.float64)
+        check(self._f.nlopt_simplex_selftest(self._h, int(kind), x0.size, _ptr(x0), _ptr(lo), _ptr(hi), _ptr(step),
+                                             float(ftol_rel), int(maxeval or 0), _ptr(res)))
+        return res
+
     def merge_selftest(self, sources, m, k, out_scores, out_idx, out_offset=0, segments=None, seg_sources=0, force=-1):
         """merge.hip alone (kpdi_merge_selftest).  sources: up to three dicts of scores (float32), idx (int32), cnt
         (int32 (m, lists) or None), lists, len, row_stride, list_stride; out_scores / out_idx: (m, out_stride), prefilled.
@@ -1609,6 +1637,12 @@ class Group(Context):
 
     def powell_selftest(self, *args, **kwargs):
         return self.root.powell_selftest(*args, **kwargs)
+
+    def refine_solve_nlopt(self, *args, **kwargs):
+        return self.root.refine_solve_nlopt(*args, **kwargs)
+
+    def nlopt_simplex_selftest(self, *args, **kwargs):
+        return self.root.nlopt_simplex_selftest(*args, **kwargs)
 
     def orientation_similarity_map(self, *args, **kwargs):
         return self.root.orientation_similarity_map(*args, **kwargs)

@@ -352,6 +352,27 @@ int powell_check_bounds(const double *lower, const double *upper, size_t count) 
   return KPDI_OK;
 }
 
+// the LN_NELDERMEAD search takes infinite bounds and leaves lower > upper to its own front end (INVALID_ARGS)
+int nlopt_check_bounds(const double *lower, const double *upper, size_t count) {
+  for (size_t i = 0; i < count; ++i)
+    if (std::isnan(lower[i]) || std::isnan(upper[i])) return fail(KPDI_EINVAL, "LN_NELDERMEAD - a bound is NaN");
+  return KPDI_OK;
+}
+
+// what nothing on the device would end: a search without ftol_rel and maxeval stops only when its simplex has
+// collapsed, and one from a non-finite point never does
+int nlopt_check_search(const double *x0, size_t count, const double *xstep, int nvar, double ftol_rel, int maxeval) {
+  if (std::isnan(ftol_rel)) return fail(KPDI_EINVAL, "LN_NELDERMEAD - ftol_rel is NaN");
+  if (!(ftol_rel > 0.0) && maxeval <= 0)
+    return fail(KPDI_EINVAL, "LN_NELDERMEAD - give ftol_rel > 0 or maxeval > 0: nothing else ends the search");
+  for (size_t i = 0; i < count; ++i)
+    if (!std::isfinite(x0[i])) return fail(KPDI_EINVAL, "LN_NELDERMEAD - a starting point is not finite");
+  if (xstep)
+    for (int i = 0; i < nvar; ++i)
+      if (!std::isfinite(xstep[i])) return fail(KPDI_EINVAL, "LN_NELDERMEAD - an initial step is not finite");
+  return KPDI_OK;
+}
+
 // what a solver plugs into refine_solve: everything else of a solve is the same for every solver
 struct RefineSolver {
   int (*check_bounds)(const double *lower, const double *upper, size_t count);
@@ -364,7 +385,8 @@ struct RefineSolver {
 // them, the `trace_capacity` rows (x[0..nvar), f) of job `trace_job` when the caller gives a `trace`
 int refine_solve(kpdi_ctx *c, const RefineSolver &solver, int mode, int64_t n_patterns, int n_starts, const double *x0,
                  const double *fixed, const double *lower, const double *upper, double xtol, double ftol, int maxiter,
-                 int maxfev, double *results, int64_t trace_job, double *trace, int trace_capacity) {
+                 int maxfev, double *results, int64_t trace_job, double *trace, int trace_capacity,
+                 const kpdi::NloptStep *xstep = nullptr) {
   if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
   if (!x0 || !results) return fail(KPDI_EINVAL, "NULL argument");
   if ((lower == nullptr) != (upper == nullptr)) return fail(KPDI_EINVAL, "give both bounds or neither");
@@ -407,6 +429,7 @@ int refine_solve(kpdi_ctx *c, const RefineSolver &solver, int mode, int64_t n_pa
   a.xatol = xtol;
   a.fatol = ftol;
   solver.budget(a.nvar, maxiter, maxfev, &a.maxiter, &a.maxfun);
+  if (xstep) a.xstep = *xstep;
   a.results = c->ref_out.as<double>();
   kpdi::EventPair timer(c);
   HIPCHK(timer.begin());
@@ -511,6 +534,59 @@ int kpdi_powell_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0, cons
   HIPCHK(kpdi::launch_powell_selftest(kind, nvar, in.x, in.lo, in.hi, xtol, ftol, maxiter, maxfev,
                                       c->ref_out.as<double>(), c->stream));
   return selftest_download(c, result, 4 + nvar);
+}
+
+int kpdi_refine_solve_nlopt(kpdi_ctx *c, int mode, int64_t n_patterns, int n_starts, const double *x0,
+                            const double *fixed, const double *lower, const double *upper, const double *xstep,
+                            double ftol_rel, int maxeval, double *results) {
+  static const RefineSolver nlopt = {
+      nlopt_check_bounds,
+      [](int, int, int maxeval, int *it, int *fev) {
+        *it = 0;
+        *fev = maxeval;
+      },
+      [](const kpdi::RefineLaunch &a, int64_t, double *, int, hipStream_t s) { return kpdi::launch_refine_solve_nlopt(a, s); }};
+  if (!x0) return fail(KPDI_EINVAL, "NULL argument");
+  int nvar, nfixed;
+  int rc = refine_mode_sizes(mode, &nvar, &nfixed);
+  if (rc) return rc;
+  if (n_patterns < 0 || n_starts <= 0 || n_patterns * n_starts >= (int64_t)INT_MAX)
+    return fail(KPDI_EINVAL, "need at least one start per pattern and fewer than 2^31 (pattern, start) pairs");
+  rc = nlopt_check_search(x0, (size_t)(n_patterns * n_starts) * nvar, xstep, nvar, ftol_rel, maxeval);
+  if (rc) return rc;
+  kpdi::NloptStep step{};
+  if (xstep) {
+    step.given = 1;
+    for (int i = 0; i < nvar; ++i) step.v[i] = xstep[i];
+  }
+  return refine_solve(c, nlopt, mode, n_patterns, n_starts, x0, fixed, lower, upper, 0.0, ftol_rel, 0, maxeval, results, 0,
+                      nullptr, 0, &step);
+}
+
+int kpdi_nlopt_simplex_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0, const double *lower,
+                                const double *upper, const double *xstep, double ftol_rel, int maxeval, double *result) {
+  if (!c || !x0 || !result) return fail(KPDI_EINVAL, "NULL argument");
+  if (kind < 0 || kind > 5) return fail(KPDI_EINVAL, "kind must be within 0..5");
+  if (nvar < 1 || nvar > 6) return fail(KPDI_EINVAL, "nvar must be within 1..6");
+  if ((lower == nullptr) != (upper == nullptr)) return fail(KPDI_EINVAL, "give both bounds or neither");
+  int rc;
+  if (lower && (rc = nlopt_check_bounds(lower, upper, (size_t)nvar))) return rc;
+  if ((rc = nlopt_check_search(x0, (size_t)nvar, xstep, nvar, ftol_rel, maxeval))) return rc;
+  rc = use_device(c);
+  if (rc) return rc;
+  // x0 | lower | upper | xstep
+  SelftestIn in;
+  HIPCHK(c->ref_in.reserve((size_t)(4 * nvar + 1) * sizeof(double)));
+  rc = selftest_upload(c, nvar, x0, lower, upper, 3 + nvar, &in);
+  if (rc) return rc;
+  double *d_step = nullptr;
+  if (xstep) {
+    d_step = c->ref_in.as<double>() + 3 * nvar;
+    HIPCHK(hipMemcpyAsync(d_step, xstep, nvar * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(kpdi::launch_nlopt_simplex_selftest(kind, nvar, in.x, in.lo, in.hi, d_step, ftol_rel, maxeval,
+                                             c->ref_out.as<double>(), c->stream));
+  return selftest_download(c, result, 3 + nvar);
 }
 
 // ---- the merge and fill kernels on caller-made lists (tests/test_gpu_merge.py) ------------------------------------

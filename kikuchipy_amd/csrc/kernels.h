@@ -313,6 +313,10 @@ size_t packed_master_floats(int npx, int npy);
 void pack_master_pattern(const float *upper, const float *lower, int npx, int npy, float *out);
 
 // ---- refinement (refine.hip) -------------------------------------------------
+struct NloptStep {  // the initial step of the LN_NELDERMEAD search, one value per variable; !given = its default step
+  int given;
+  double v[6];
+};
 struct RefineLaunch {
   int mode, nvar, nfixed, n_starts;
   int64_t n_jobs;        // solve: patterns * starts; objective: evaluations
@@ -328,6 +332,7 @@ struct RefineLaunch {
   const double *sqnorm;         // [n]
   double xatol, fatol;
   int maxiter, maxfun;
+  NloptStep xstep;              // launch_refine_solve_nlopt only
   double *results;              // [n_jobs][REFINE_RESULT_STRIDE]: fun, nfev, nit, x[nvar]
 };
 constexpr int REFINE_RESULT_STRIDE = 9;
@@ -342,6 +347,13 @@ hipError_t launch_refine_solve_powell(const RefineLaunch &a, int64_t trace_job, 
 // result: fun, nfev, nit, status, x[0..nvar)
 hipError_t launch_powell_selftest(int kind, int nvar, const double *x0, const double *lower, const double *upper,
                                   double xtol, double ftol, int maxiter, int maxfev, double *result, hipStream_t s);
+// the LN_NELDERMEAD search of nlopt_simplex.h: a.fatol = ftol_rel, a.maxfun = maxeval (<= 0 = none), a.xstep; the `nit`
+// slot of a result row holds the status
+hipError_t launch_refine_solve_nlopt(const RefineLaunch &a, hipStream_t s);
+// result: minf, nevals, status, x[0..nvar)
+hipError_t launch_nlopt_simplex_selftest(int kind, int nvar, const double *x0, const double *lower, const double *upper,
+                                         const double *xstep, double ftol_rel, int maxeval, double *result,
+                                         hipStream_t s);
 hipError_t launch_nelder_mead_selftest(int kind, int nvar, const double *x0, const double *lower, const double *upper,
                                        double xatol, double fatol, int maxiter, int maxfun, double *result,
                                        hipStream_t s);

@@ -12,8 +12,10 @@
 // f64 without fused multiply-add, so that on the same objective values it walks the same
 // simplex path (kpdi_nelder_mead_selftest pins that bit for bit against SciPy).  The second
 // device optimiser is scipy.optimize.minimize(method="Powell"), restated in powell.h and run
-// by `refine_solve_powell_kernel` (kpdi_powell_selftest pins it the same way); every other
-// optimiser stays on the host and calls `refine_objective_kernel`.
+// by `refine_solve_powell_kernel` (kpdi_powell_selftest pins it the same way); the third is the simplex search
+// NLopt offers as LN_NELDERMEAD, restated in nlopt_simplex.h from the text of DESIGN.md section 21 and run by
+// `refine_solve_nlopt_kernel` (kpdi_nlopt_simplex_selftest pins kernel against header; NLopt itself is not compared
+// with).  Every other optimiser stays on the host and calls `refine_objective_kernel`.
 //
 // One workgroup per (experimental pattern, start) runs the WHOLE optimisation: thread 0
 // owns the simplex (LDS) and decides the next point; all 256 threads evaluate the
@@ -31,6 +33,7 @@
 
 #include <climits>
 
+#include "nlopt_simplex.h"
 #include "powell.h"
 
 namespace kpdi {
@@ -544,6 +547,68 @@ __global__ void powell_selftest_kernel(int kind, int nvar, const double *x0, con
   for (int i = 0; i < nvar; ++i) result[4 + i] = pw.x[i];
 }
 
+// ---- the LN_NELDERMEAD search (nlopt_simplex.h) on the device, run like Powell: every thread walks the same simplex on
+// the uniform objective values.  Each (pattern, start) is one `optimize` call with its own evaluation count.
+// result row: minf, nevals, status, x (the best point seen)
+__global__ __launch_bounds__(REF_THREADS, 4) void refine_solve_nlopt_kernel(
+    int mode, int nvar, int nfixed, int n_starts, const double *x0, const double *fixed, const double *lower,
+    const double *upper, RefineGeom g, const float *patterns, const double *sqnorm, NloptStep xstep, double ftol_rel,
+    int maxeval, double *results) {
+  __shared__ double red[3 * REF_THREADS / 64];
+  const int64_t job = blockIdx.x;  // (pattern, start)
+  const int64_t pat_id = job / n_starts;
+  RefinePowellEval ev;
+  ev.mode = mode;
+  ev.nvar = nvar;
+  ev.fx = fixed + job * nfixed;
+  ev.g = &g;
+  ev.pat = patterns + pat_id * g.k;
+  ev.sqn = sqnorm[pat_id];
+  ev.red = red;
+  ev.trace = nullptr;
+  ev.trace_capacity = 0;
+  ev.n_eval = 0;
+  NloptSimplex<NV_MAX, RefinePowellEval> ns(ev);
+  ns.optimize(nvar, x0 + job * nvar, lower ? lower + job * nvar : nullptr, upper ? upper + job * nvar : nullptr,
+              xstep.given ? xstep.v : nullptr, ftol_rel, maxeval);
+  if (threadIdx.x == 0) {
+    double *o = results + job * RESULT_STRIDE;
+    o[0] = ns.minf;
+    o[1] = (double)ns.nevals;
+    o[2] = (double)ns.status;
+    for (int i = 0; i < nvar; ++i) o[3 + i] = ns.x[i];
+  }
+}
+
+// ---- nlopt_simplex.h alone on analytic f64 objectives: kinds 0..4 of `PowellSelftestEval`, 5 = a sum of concave arms,
+// sum((i + 1) |d| / (1 + |d|)) with d = x[i] - 0.3 (i + 1), on which contractions fail and the simplex shrinks
+struct NloptSelftestEval {
+  int kind, n;
+  __device__ double eval(const double *x) const {
+    if (kind != 5) return PowellSelftestEval{kind, n}.eval(x);
+    double acc = 0.0;
+    for (int i = 0; i < n; ++i) {
+      const double d = fabs(x[i] - 0.3 * (double)(i + 1));
+      const double t = (double)(i + 1) * d / (1.0 + d);
+      acc = i == 0 ? t : acc + t;
+    }
+    return acc;
+  }
+};
+
+// result: minf, nevals, status, x[0..nvar)
+__global__ void nlopt_simplex_selftest_kernel(int kind, int nvar, const double *x0, const double *lower, const double *upper,
+                                              const double *xstep, double ftol_rel, int maxeval, double *result) {
+  if (threadIdx.x != 0) return;
+  NloptSelftestEval ev{kind, nvar};
+  NloptSimplex<NV_MAX, NloptSelftestEval> ns(ev);
+  ns.optimize(nvar, x0, lower, upper, xstep, ftol_rel, maxeval);
+  result[0] = ns.minf;
+  result[1] = (double)ns.nevals;
+  result[2] = (double)ns.status;
+  for (int i = 0; i < nvar; ++i) result[3 + i] = ns.x[i];
+}
+
 // ---- launchers
 static RefineGeom make_geom(const RefineLaunch &a) {
   RefineGeom g;
@@ -613,6 +678,23 @@ hipError_t launch_powell_selftest(int kind, int nvar, const double *x0, const do
                                   double xtol, double ftol, int maxiter, int maxfev, double *result, hipStream_t s) {
   hipLaunchKernelGGL(powell_selftest_kernel, dim3(1), dim3(64), 0, s, kind, nvar, x0, lower, upper, xtol, ftol, maxiter,
                      maxfev, result);
+  return hipGetLastError();
+}
+
+// a.fatol = ftol_rel, a.maxfun = maxeval (<= 0 = none), a.xstep
+hipError_t launch_refine_solve_nlopt(const RefineLaunch &a, hipStream_t s) {
+  if (a.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(refine_solve_nlopt_kernel, dim3((unsigned)a.n_jobs), dim3(REF_THREADS), 0, s, a.mode, a.nvar,
+                     a.nfixed, a.n_starts, a.x0, a.fixed, a.lower, a.upper, make_geom(a), a.patterns, a.sqnorm, a.xstep,
+                     a.fatol, a.maxfun, a.results);
+  return hipGetLastError();
+}
+
+hipError_t launch_nlopt_simplex_selftest(int kind, int nvar, const double *x0, const double *lower, const double *upper,
+                                         const double *xstep, double ftol_rel, int maxeval, double *result,
+                                         hipStream_t s) {
+  hipLaunchKernelGGL(nlopt_simplex_selftest_kernel, dim3(1), dim3(64), 0, s, kind, nvar, x0, lower, upper, xstep, ftol_rel,
+                     maxeval, result);
   return hipGetLastError();
 }
 

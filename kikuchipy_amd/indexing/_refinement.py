@@ -14,8 +14,14 @@ the reference's pattern-matching tutorial refines projection centres with) runs 
 (`kpdi_refine_solve_powell`, `_device_powell_options`); the environment variable KPDI_REFINE_POWELL=host, read at
 each call, sends it to the host path below instead.
 
+`method="LN_NELDERMEAD"` (what the reference's tutorials refine orientations and PCs together with: `initial_step`,
+`rtol`, `maxeval`) runs on the device too (`kpdi_refine_solve_nlopt`, `_DeviceNlopt`), without the `nlopt` module: the
+search is the one csrc/nlopt_simplex.h restates from the text of DESIGN.md section 21, which has NOT been compared with
+an installed NLopt.  KPDI_REFINE_NLOPT=host, read at each call, sends the call to the host path below, which needs
+`nlopt`.
+
 Every other optimiser the reference can dispatch to (SciPy's other local methods, Powell with `direc`, `callback` or
-`return_all`, its global methods, NLopt's LN_NELDERMEAD) keeps ITS optimiser on the host, called with the reference's
+`return_all`, its global methods) keeps ITS optimiser on the host, called with the reference's
 arguments, with the objective evaluated on the device (`_HostOptimizer`); `compute=False` returns a
 `DeferredRefinement` in place of the reference's lazy Dask array.
 """
@@ -301,6 +307,44 @@ def _device_powell_options(host):
     return out
 
 
+class _DeviceNlopt:
+    """`method="LN_NELDERMEAD"` on the device: what `_RefinementSetup.set_optimization_parameters`
+    (indexing/_refinement/_refinement.py:1095-1122) sets on its `nlopt.opt` - the relative tolerance, the initial
+    step(s), one for orientations or PCs and two for both, each repeated three times, and the maximum number of
+    evaluations - without the `nlopt` module."""
+
+    method_name = "LN_NELDERMEAD"
+
+    def __init__(self, initial_step, rtol, maxeval, mode):
+        self.rtol, self.initial_step, self.maxeval = float(rtol), None, None
+        if initial_step is not None:
+            step = np.atleast_1d(initial_step)
+            if step.size != {"ori": 1, "pc": 1, "ori_pc": 2}[mode]:
+                raise ValueError("The initial step must be a single number when refining orientations or PCs and a "
+                                 "list of two numbers when refining both")
+            self.initial_step = [float(v) for v in np.repeat(step, 3)]
+        if maxeval is not None:
+            if isinstance(maxeval, bool) or int(maxeval) != maxeval or not -2**31 < int(maxeval) < 2**31:
+                raise ValueError(f"maxeval must be an integer, got {maxeval!r}")
+            self.maxeval = int(maxeval)
+
+    @property
+    def plan(self):
+        return dict(method_name=self.method_name, type="local", package="nlopt", supports_bounds=True, kwargs={},
+                    host=self, note=", restated on the GPU")
+
+    def solve(self, ctx, mode_code, x0, fixed, lower, upper):
+        return ctx.refine_solve_nlopt(mode_code, x0, fixed, lower, upper, self.initial_step, self.rtol, self.maxeval or 0)
+
+    @staticmethod
+    def raise_for_status(status):
+        """What NLopt's Python binding does with the two negative results this search can end with."""
+        if np.any(status == -2):  # a start outside its bounds
+            raise ValueError("nlopt invalid argument")
+        if np.any(status == -1):  # an initial step that does not move its variable
+            raise RuntimeError("nlopt failure")
+
+
 def _host_solve(ctx, mode_code, host, x0, fixed, lower, upper):
     """The host-driven counterpart of `Context.refine_solve`: same (n, starts, 3 + nvar) result."""
     n, starts, nvar = x0.shape
@@ -350,7 +394,7 @@ def _info_message(mode, trust_region, shown_kwargs, n_pseudo, plan=None):
     """`_RefinementSetup.get_info_message` (:1244-1286)."""
     plan = plan or dict(method_name="Nelder-Mead", type="local", package="scipy", supports_bounds=True)
     package = {"scipy": "SciPy", "nlopt": "NLopt"}[plan["package"]]
-    info = f"Refinement information:\n  Method: {plan['method_name']} ({plan['type']}) from {package}"
+    info = f"Refinement information:\n  Method: {plan['method_name']} ({plan['type']}) from {package}{plan.get('note', '')}"
     if plan["supports_bounds"]:
         tr_str = np.array_str(np.asarray(trust_region), precision=5)
         info += "\n  Trust region (+/-): " + tr_str
@@ -421,7 +465,12 @@ def refine(mode, patterns, rotations, detector, master_pattern, energy=None, nav
     """
     if mode not in MODES:
         raise ValueError(f"mode must be one of {sorted(MODES)}")
-    nm, host, plan = _optimization_plan(method, method_kwargs, initial_step, rtol, maxeval, mode)
+    nlopt = None
+    if str(method or "").lower() == "ln_neldermead" and os.environ.get("KPDI_REFINE_NLOPT", "").lower() != "host":
+        nlopt = _DeviceNlopt(initial_step, rtol, maxeval, mode)
+        nm, host, plan = None, None, nlopt.plan
+    else:
+        nm, host, plan = _optimization_plan(method, method_kwargs, initial_step, rtol, maxeval, mode)
     shown = plan["kwargs"]
     master_pattern._is_suitable_for_projection(raise_if_not=True)
     patterns = np.asarray(patterns)
@@ -513,7 +562,7 @@ def refine(mode, patterns, rotations, detector, master_pattern, energy=None, nav
     def run():
         return _run_refinement(mode, n, starts, x0, fixed, lower, upper, pats, signal_mask, detector, master_pattern,
                                energy, nm, host, context, device, comm, verbose, n_pseudo, points, nav_shape,
-                               navigation_mask, contexts)
+                               navigation_mask, contexts, nlopt)
 
     if not compute:
         return DeferredRefinement(mode, run, n_pseudo > 0)
@@ -522,7 +571,7 @@ def refine(mode, patterns, rotations, detector, master_pattern, energy=None, nav
 
 
 def _run_refinement(mode, n, starts, x0, fixed, lower, upper, pats, signal_mask, detector, master_pattern, energy, nm, host,
-                    context, device, comm, verbose, n_pseudo, points, nav_shape, navigation_mask, contexts=None):
+                    context, device, comm, verbose, n_pseudo, points, nav_shape, navigation_mask, contexts=None, nlopt=None):
     """The solve + the assembly of the result (what `compute_refine_*_results` do in the reference,
     indexing/_refinement/_refinement.py:58-290).  Returns (RefinementResult, new detector | None, raw rows)."""
     lo_i, hi_i = 0, n
@@ -541,6 +590,8 @@ def _run_refinement(mode, n, starts, x0, fixed, lower, upper, pats, signal_mask,
         # rescale exactly when the patterns are float32 (_refinement.py:956)
         c.refine_set_patterns(pats[part], signal_mask, pats.dtype == np.float32, detector.detector_to_sample)
         block = [a if a is None else a[part] for a in (x0, fixed, lower, upper)]
+        if nlopt is not None:  # the LN_NELDERMEAD search on the device: one launch, each start its own search
+            return nlopt.solve(c, MODES[mode], *block)
         if host is None:  # the whole simplex search on the device
             return c.refine_solve(MODES[mode], *block, nm["xatol"], nm["fatol"], nm["maxiter"] or 0, nm["maxfev"] or 0)
         powell = _device_powell_options(host)
@@ -569,6 +620,8 @@ def _run_refinement(mode, n, starts, x0, fixed, lower, upper, pats, signal_mask,
             res = np.empty((0, starts, 3 + x0.shape[2]))
         if comm is not None and comm.world_size > 1:
             res = comm.all_gather_rows(res)
+        if nlopt is not None:  # on the complete result: every rank raises alike
+            nlopt.raise_for_status(res[:, :, 2])
         total = time.time() - t0
     finally:
         if context is None and ctx is not None:
