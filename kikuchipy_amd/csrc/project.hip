@@ -50,6 +50,16 @@ template <> __device__ __forceinline__ double cast_out<double>(double v) { retur
 template <> __device__ __forceinline__ uint8_t cast_out<uint8_t>(double v) { return (uint8_t)(int)v; }
 template <> __device__ __forceinline__ uint16_t cast_out<uint16_t>(double v) { return (uint16_t)(int)v; }
 
+// num / den given r = 1 / den: quotient estimate and one residual step, which gives the division's own rounding
+// (and exactly 1 for num == den, where num * r alone is 1 - 2^-53 for about one den in eight).
+// _rescale_with_min_max (pattern/_pattern.py:97-111) divides by imax - imin before it scales, so the brightest pixel
+// is exactly 1 * (omax - omin) + omin; a gain (omax - omin) / (imax - imin) multiplied in does not give that
+// (h * (255 / h) < 255 for about one h in eight) and integer outputs then truncate to out_max - 1.
+__device__ __forceinline__ double div_by(double num, double den, double r) {
+  const double q = num * r;
+  return fma(fma(-q, den, num), r, q);
+}
+
 __device__ __forceinline__ void block_minmax(double &lo, double &hi, double *red) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) {
@@ -141,39 +151,59 @@ __global__ __launch_bounds__(PROJ_THREADS, PROJ_MIN_BLOCKS) void project_kernel(
       const int c = tid + PROJ_THREADS * i;
       const int cc = min(c, last);
       v[i] = pixel(cc);
-      lo = fmin(lo, v[i]);  // a clamped slot repeats the last pixel: min/max unchanged
-      hi = fmax(hi, v[i]);
+      // A clamped slot repeats the last pixel, but not to the bit: every unrolled slot is its own copy of
+      // project_pixel, which the compiler contracts on its own, and a last pixel that was the pattern's maximum
+      // has come out one ulp higher in a clamped slot than in the slot that stores it - then no pixel is out_max
+      // (and a one-pixel pattern is not constant).  So a clamped slot hands slot 0's value to the min/max: a pixel
+      // of this thread, or (tid > last, so the last pixel is in slot 0) what the lane that stores the last pixel
+      // computed with these very instructions.
+      const double m = (i == 0 || c <= last) ? v[i] : v[0];
+      lo = fmin(lo, m);
+      hi = fmax(hi, m);
       // two pixels in flight per thread; without the fence the scheduler interleaves all the
       // slots and the kernel needs > 400 VGPRs (one wave per SIMD)
       if ((i % PROJ_FENCE) == PROJ_FENCE - 1) __builtin_amdgcn_sched_barrier(0);
     }
-    double gain = 1.0, offs = 0.0, base = 0.0;
+    double den = 1.0, rden = 1.0, span = 1.0, offs = 0.0, base = 0.0;
     if (rescale) {
       block_minmax(lo, hi, red);
-      gain = (omax - omin) / (hi - lo);
+      den = hi - lo;
+      rden = 1.0 / den;
+      span = omax - omin;
       base = lo;
       offs = omin;
     }
 #pragma unroll
     for (int i = 0; i < PROJ_VALUES; ++i) {
       const int c = tid + PROJ_THREADS * i;
-      const double w = rescale ? (v[i] - base) * gain + offs : v[i];
+      const double w = rescale ? div_by(v[i] - base, den, rden) * span + offs : v[i];
       if (c < npix) o[c] = cast_out<T>(w);
     }
   } else {
+    // Every pixel is computed twice, by two copies of project_pixel that the compiler contracts each on its own: the
+    // second pass need not give the bits of the first.  So a thread remembers which of its pixels were its darkest
+    // and brightest, and where one of them turns out to be the pattern's, the second pass takes the value from the
+    // first: (v - lo) / (hi - lo) is exactly 0 and 1 there, whatever the recomputation gives.
     double lo = INFINITY, hi = -INFINITY;
+    int at_lo = -1, at_hi = -1;
     if (rescale) {
       for (int c = tid; c < npix; c += PROJ_THREADS) {
         const double v = pixel(c);
-        lo = fmin(lo, v);
-        hi = fmax(hi, v);
+        if (v < lo) { lo = v; at_lo = c; }
+        if (v > hi) { hi = v; at_hi = c; }
       }
+      const double mine_lo = lo, mine_hi = hi;
       block_minmax(lo, hi, red);
+      if (mine_lo != lo) at_lo = -1;
+      if (mine_hi != hi) at_hi = -1;
     }
-    const double gain = (omax - omin) / (hi - lo);
+    const double den = hi - lo, rden = 1.0 / den, span = omax - omin;
     for (int c = tid; c < npix; c += PROJ_THREADS) {
       double v = pixel(c);
-      if (rescale) v = (v - lo) * gain + omin;
+      if (rescale) {
+        v = c == at_hi ? hi : c == at_lo ? lo : v;
+        v = div_by(v - lo, den, rden) * span + omin;
+      }
       o[c] = cast_out<T>(v);
     }
   }
