@@ -23,6 +23,18 @@
 // float32 FFT by its FFT round-off (~6e-5 on values ~100), which can flip the
 // final truncation on isolated pixels.
 //
+// Degenerate patterns give what the reference's arithmetic gives (np.min / np.max propagate NaN, fminf / fmaxf do not, so
+// all three kernels carry a NaN flag next to min and max - range_is_healthy and the sum of the rescale pass - and leave
+// the per-pixel path through workgroup-uniform branches, DegenerateRescale and nan_pixel):
+//   a NaN among the values that are rescaled (0 / 0 on a dead pixel, a NaN or inf pixel of a float pattern: inf - inf
+//   under the filter) -> min = max = NaN -> every pixel NaN: 0 in the integer dtypes (ndarray.astype on x86-64, not the
+//   undefined C cast), NaN in the float dtypes;
+//   a constant difference (pattern = background, a constant pattern) -> 0 / 0 on every pixel: the same;
+//   x / 0 alone -> an infinite range: the finite pixels become omin, the infinite ones NaN.
+// One exception: a constant pattern under the "frequency" filter, where the reference's float32 FFT returns the constant
+// plus round-off and the rescale stretches that to the full range; the correlation is exact there and gives 0 / 0.
+// tests/_preproc_restate.py restates all of this in NumPy, bit for bit; tests/test_gpu_preproc_kernels.py compares.
+//
 // preproc_fused_kernel: ONE WORKGROUP PER PATTERN, one pass over HBM:
 //   raw pattern (vector loads) -> LDS f32 -> static background (two block reductions) -> truncate
 //   -> Gaussian along the rows, written TRANSPOSED so that both 1-D passes read LDS with unit
@@ -76,6 +88,34 @@ __device__ __forceinline__ void block_minmax(float &mn, float &mx, float *red) {
   }
 }
 
+// fminf / fmaxf skip NaN, the reference's np.min / np.max do not.  The flag for it stays off the filter's per-pixel path
+// (a value live across the unrolled correlation cost the 60 x 60 form its fifth wave per SIMD: DESIGN.md 4.4):
+//   the reduced range is tested first - 0, infinite or NaN: DegenerateRescale, with the values still in place;
+//   a healthy range may still hide a NaN among the values.  The rescale pass adds up what it writes, one addition per
+//   pixel; every rescaled value of a pattern without a NaN lies in the output range, so the sum is NaN exactly when a
+//   value was, and one __syncthreads_or per pattern tells every thread.  The pattern is then rewritten as the reference
+//   has it, every pixel NaN; what the first pass stored for the NaN pixels (a cast of NaN) is overwritten unread.
+__device__ __forceinline__ bool range_is_healthy(float irange) { return irange > 0.f && irange < INFINITY; }
+// every pixel of a pattern that holds a NaN: 0 in the integer dtypes, NaN in the float dtypes
+template <typename T>
+__device__ __forceinline__ T nan_pixel() {
+  return astype_cast<T>(__builtin_nanf(""));
+}
+
+// The rescale of any other pattern, as the reference evaluates it: np.min / np.max are NaN when a value is (then every
+// pixel is), a range of 0 divides 0 by 0 on every pixel, an infinite range sends the finite pixels to omin and the
+// infinite ones to NaN; NaN is 0 in the integer dtypes (astype_cast: ndarray.astype on x86-64) and stays NaN in the
+// float dtypes.  `any_nan`: whether a value is NaN, the same in every thread.
+struct DegenerateRescale {
+  float imin, irange, orange, omin;
+  __device__ __forceinline__ DegenerateRescale(float mn, float mx, bool any_nan, float orange_, float omin_)
+      : imin(any_nan ? __builtin_nanf("") : mn), irange(any_nan ? __builtin_nanf("") : mx - mn), orange(orange_), omin(omin_) {}
+  template <typename T>
+  __device__ __forceinline__ T to(float v) const {
+    return astype_cast<T>(kpdi::rescale(v, imin, irange, orange, omin));
+  }
+};
+
 // rescale() of prep_device.h with the division by a WORKGROUP-UNIFORM divisor taken apart: an IEEE float32 division is, on this chip, a
 // reciprocal refined once, a quotient estimate and two residual corrections (what the compiler emits around
 // v_div_scale / v_div_fixup, which only matter for operands near the ends of the exponent range).  The refined reciprocal
@@ -107,7 +147,7 @@ __device__ __forceinline__ float rescale(float v, float imin, const UniformDivis
 
 template <typename T>
 __device__ __forceinline__ T cast_out(float v) {
-  return (T)v;  // C truncation == ndarray.astype for in-range values
+  return (T)v;  // C truncation == ndarray.astype for finite in-range values: healthy patterns only (range_is_healthy)
 }
 
 // a * ld + o as ONE v_mad_i32_i24 (all three far below 2^23; the compiler cannot know and emits a quarter-rate
@@ -267,15 +307,14 @@ __global__ __launch_bounds__(THREADS) void preproc_fused_kernel(PreArgs a, const
       }
   }
   // final values of a quad -> LDS (as float) and, when this was the last step, back to memory
-  auto finish = [&](float imin, float irange_value, bool store) {
-    const UniformDivisor irange(irange_value);
+  auto write_back = [&](auto convert, bool store) {
     for (int q = tid; q < nquad; q += THREADS) {
       float4 w = *reinterpret_cast<const float4 *>(x + 4 * q);
       float *wf = &w.x;
       Quad<T> u;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        u.v[e] = cast_out<T>(rescale(wf[e], imin, irange, orange, a.omin));
+        u.v[e] = convert(wf[e]);
         wf[e] = (float)u.v[e];
       }
       *reinterpret_cast<float4 *>(x + 4 * q) = w;
@@ -289,6 +328,26 @@ __global__ __launch_bounds__(THREADS) void preproc_fused_kernel(PreArgs a, const
         }
       }
     }
+  };
+  auto finish = [&](float imin, float imax, bool store) {
+    const float irange_value = imax - imin;
+    if (range_is_healthy(irange_value)) {  // (workgroup-uniform)
+      const UniformDivisor irange(irange_value);
+      float seen = 0.f;  // NaN when a value was
+      write_back(
+          [&](float v) {
+            const float r = rescale(v, imin, irange, orange, a.omin);
+            seen += r;
+            return cast_out<T>(r);
+          },
+          store);
+      if (__syncthreads_or(seen != seen)) write_back([&](float) { return nan_pixel<T>(); }, store);
+      return;
+    }
+    int nan = 0;
+    for (int i = tid; i < npix; i += THREADS) nan |= x[i] != x[i];
+    const DegenerateRescale slow(imin, imax, __syncthreads_or(nan) != 0, orange, a.omin);
+    write_back([&](float v) { return slow.template to<T>(v); }, store);
   };
 
   // ---- static background (pattern/_pattern.py:392-435)
@@ -318,7 +377,7 @@ __global__ __launch_bounds__(THREADS) void preproc_fused_kernel(PreArgs a, const
       *reinterpret_cast<float4 *>(x + 4 * q) = w;
     }
     block_minmax<THREADS>(mn, mx, red);
-    finish(mn, mx - mn, !a.do_dynamic);
+    finish(mn, mx, !a.do_dynamic);
   }
 
   // ---- dynamic background (pattern/_pattern.py:438-481)
@@ -351,7 +410,7 @@ __global__ __launch_bounds__(THREADS) void preproc_fused_kernel(PreArgs a, const
     mx = -INFINITY;
     if (a.reflect) cols(std::true_type{}); else cols(std::false_type{});
     block_minmax<THREADS>(mn, mx, red);
-    finish(mn, mx - mn, true);
+    finish(mn, mx, true);
   }
 
   // ---- fused preparation: what launch_prep would do with the pattern just written
@@ -413,7 +472,24 @@ __global__ __launch_bounds__(PP_THREADS) void static_stream_kernel(PreArgs a) {
   }
   block_minmax<PP_THREADS>(mn, mx, red);
   const float irange = mx - mn;
-  for (int i = tid; i < npix; i += PP_THREADS) p[i] = cast_out<T>(rescale(value(i), mn, irange, orange, a.omin));
+  if (range_is_healthy(irange)) {  // (workgroup-uniform)
+    float seen = 0.f;  // NaN when a value was
+    for (int i = tid; i < npix; i += PP_THREADS) {
+      const float r = rescale(value(i), mn, irange, orange, a.omin);
+      seen += r;
+      p[i] = cast_out<T>(r);
+    }
+    if (__syncthreads_or(seen != seen))
+      for (int i = tid; i < npix; i += PP_THREADS) p[i] = nan_pixel<T>();
+    return;
+  }
+  int nan = 0;
+  for (int i = tid; i < npix; i += PP_THREADS) {
+    const float y = value(i);
+    nan |= y != y;
+  }
+  const DegenerateRescale slow(mn, mx, __syncthreads_or(nan) != 0, orange, a.omin);
+  for (int i = tid; i < npix; i += PP_THREADS) p[i] = slow.template to<T>(value(i));
 }
 
 // persistent workgroups; scratch = [gridDim.x][2][npix] floats (row pass transposed | pattern - background)
@@ -451,7 +527,21 @@ __global__ __launch_bounds__(PP_THREADS) void dynamic_stream_kernel(PreArgs a, c
     if (a.reflect) cols(std::true_type{}); else cols(std::false_type{});
     block_minmax<PP_THREADS>(mn, mx, red);  // (its barriers also order the yb writes before the reads below)
     const float irange = mx - mn;
-    for (int i = tid; i < npix; i += PP_THREADS) p[i] = cast_out<T>(rescale(yb[i], mn, irange, orange, a.omin));
+    if (range_is_healthy(irange)) {  // (workgroup-uniform)
+      float seen = 0.f;  // NaN when a value was
+      for (int i = tid; i < npix; i += PP_THREADS) {
+        const float r = rescale(yb[i], mn, irange, orange, a.omin);
+        seen += r;
+        p[i] = cast_out<T>(r);
+      }
+      if (__syncthreads_or(seen != seen))
+        for (int i = tid; i < npix; i += PP_THREADS) p[i] = nan_pixel<T>();
+    } else {
+      int nan = 0;
+      for (int i = tid; i < npix; i += PP_THREADS) nan |= yb[i] != yb[i];
+      const DegenerateRescale slow(mn, mx, __syncthreads_or(nan) != 0, orange, a.omin);
+      for (int i = tid; i < npix; i += PP_THREADS) p[i] = slow.template to<T>(yb[i]);
+    }
     __syncthreads();  // the scratch is reused by the next pattern
   }
 }

@@ -15,6 +15,7 @@ filters/fft_barnes.py:119-177, benchmarks/indexing/test_dictionary_indexing.py:3
 import numpy as np
 import pytest
 
+import _prep_cases as P
 from oracle import c_oracle
 from oracle import kpdi_oracle as ko
 
@@ -95,8 +96,44 @@ def ctx():
     (np.float32, (60, 60), False, False, "ncc", {}),
     (np.uint8, (120, 120), True, False, "ncc", {}),         # 14 400 px: the 64-value register form
     (np.uint8, (136, 140), False, False, "ndp", {}),        # 19 040 px: fused pre-processing, separate preparation
+] + [
+    # the fused preparation epilogue under the other compute forms (H16 on / off, pix_map, out_row with -1 rows)
+    (np.uint8, shape, masked, navmask, "ncc", dict(compute=compute))
+    for compute in ("f16", "f16x2", "wide")
+    for shape, masked, navmask in (((60, 60), True, True),       # 16 values per thread, pix_map and -1 rows together
+                                   ((86, 120), False, False),    # 1024 threads
+                                   ((120, 120), True, False),
+                                   ((60, 120), False, False),    # 7200 columns on 256 threads: 64 values per thread
+                                   ((136, 140), False, False))   # 19 040 columns on 1024 threads: 32 values per thread
 ])
-def test_fused_equals_stepwise(ctx, dtype, shape, masked, navmask, metric, kw):
+def test_fused_equals_stepwise(ctx, dtype, shape, masked, navmask, metric, kw, monkeypatch):
+    kw = dict(kw)
+    compute = kw.pop("compute", None)
+    if compute is not None:
+        # KPDI_F32_WIDE is read by set_problem: a fresh context per setting (tests/test_gpu_prep_matrix.py)
+        monkeypatch.setenv("KPDI_F32_WIDE", "1" if compute == "wide" else "0")
+        L = codes()
+        with L.Context(0) as fresh:
+            fused_equals_stepwise(fresh, dtype, shape, masked, navmask, metric, kw, compute,
+                                  {"f16": L.COMPUTE_F16, "f16x2": L.COMPUTE_F16X2, "wide": L.COMPUTE_F32}[compute])
+        return
+    fused_equals_stepwise(ctx, dtype, shape, masked, navmask, metric, kw, None, None)
+
+
+def float64_topk(u, dic, mask, metric, keep_n):
+    """(scores, indices, form-2 tolerance) of the float64 evaluation of the pre-processed patterns `u` against `dic`; the
+    tolerance by the rule of tests/_prep_cases.py: twice the deviation of the same evaluation with its prepared operands
+    rounded to float16(2^12 value)."""
+    keep = np.arange(u[0].size) if mask is None else np.flatnonzero(~np.asarray(mask).ravel())
+    e, d = P.prepared(u, keep, metric), P.prepared(dic, keep, metric)
+    exact = e @ d.T
+    e16, d16 = ((v * 4096).astype(np.float32).astype(np.float16).astype(np.float64) for v in (e, d))
+    tol = 2.0 * float(np.abs((e16 @ d16.T) * 2.0 ** -24 - exact).max())
+    idx = np.argsort(-exact, axis=1, kind="stable")[:, :keep_n]
+    return np.take_along_axis(exact, idx, axis=1), idx, tol
+
+
+def fused_equals_stepwise(ctx, dtype, shape, masked, navmask, metric, kw, compute_name, compute):
     rng = np.random.default_rng(11)
     m, n = 37, 300
     hi = 65535 if dtype == np.uint16 else 255
@@ -105,17 +142,28 @@ def test_fused_equals_stepwise(ctx, dtype, shape, masked, navmask, metric, kw):
     dic = rng.random((n,) + shape, dtype=np.float32)
     mask = ~ko.circular_window(shape).astype(bool) if masked else None
     nav = (rng.random(m) < 0.3) if navmask else None
-    s1, i1, u1, steps, cnt1 = run_pipeline(ctx, exp, bg, dic, fused=False, metric=metric, mask=mask, nav=nav, **kw)
-    s2, i2, u2, _, cnt2 = run_pipeline(ctx, exp, bg, dic, fused=True, metric=metric, mask=mask, nav=nav, **kw)
+    s1, i1, u1, steps, cnt1 = run_pipeline(ctx, exp, bg, dic, fused=False, metric=metric, mask=mask, nav=nav, compute=compute, **kw)
+    s2, i2, u2, _, cnt2 = run_pipeline(ctx, exp, bg, dic, fused=True, metric=metric, mask=mask, nav=nav, compute=compute, **kw)
     assert np.array_equal(u1, u2)            # pre-processed patterns: bit for bit
     assert np.array_equal(steps[-1], u1)
     assert cnt1["preproc_launches"] == 0 and cnt2["preproc_launches"] == 1
-    assert np.array_equal(i1, i2)
-    assert np.abs(s1 - s2).max() <= 1e-6      # the two preparation kernels sum in different orders
-    # against the oracle fed the engine's own pre-processed patterns
+    if compute_name is not None:
+        assert cnt1["match_form"] == cnt2["match_form"] == P.FORMS[compute_name]
     kept = u2 if nav is None else u2[~nav]
-    rs, ri = ko.dictionary_indexing(kept, dic, metric=metric, keep_n=10, signal_mask=mask)
-    ko.assert_topk_parity(s2, i2, rs, ri, atol=ATOL)
+    if compute_name in ("f16", "f16x2"):
+        # the float16 forms: each run against the float64 evaluation of the same pre-processed patterns - the split-f16
+        # form within the project's 1e-5, the float16 form within the tolerance its own rounding gives (_prep_cases.py)
+        rs, ri, tol16 = float64_topk(kept, dic, mask, metric, 10)
+        tol = tol16 if compute_name == "f16" else ATOL
+        print(f"{compute_name} {shape}: tolerance {tol:.2e}; stepwise {np.abs(s1 - rs).max():.2e}, fused {np.abs(s2 - rs).max():.2e}")
+        ko.assert_topk_parity(s1, i1, rs, ri, atol=tol, tie=2 * tol)
+        ko.assert_topk_parity(s2, i2, rs, ri, atol=tol, tie=2 * tol)
+    else:
+        assert np.array_equal(i1, i2)
+        assert np.abs(s1 - s2).max() <= 1e-6      # the two preparation kernels sum in different orders
+        # against the oracle fed the engine's own pre-processed patterns
+        rs, ri = ko.dictionary_indexing(kept, dic, metric=metric, keep_n=10, signal_mask=mask)
+        ko.assert_topk_parity(s2, i2, rs, ri, atol=ATOL)
     # and the pre-processing against the oracle's (<= 1 grey level on <= 1e-3 of pixels; exact for static only)
     want = exp
     if kw.get("static", True):
