@@ -1,5 +1,5 @@
 #!/bin/bash
-# Where the f32 wide kernel's tile time goes: timing-only ablation builds (tools/build_variant.sh <tag> match16.hip -D...)
+# Where the f32 wide kernel's tile time goes: timing-only ablation builds (tools/build_variant.sh <tag> match32.hip -D...)
 # through tools/tile_ramp_probe.py wide (match ms against whole tiles per workgroup: slope = ms per tile).
 #   bash tools/f32_loop_ab.sh <out.txt> shipped noepi nodma_noepi ...     (run on the GPU box)
 cd "$(dirname "$0")/.." && R=$PWD
