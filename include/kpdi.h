@@ -642,6 +642,34 @@ int kpdi_refine_solve_nlopt(kpdi_ctx *ctx, int mode, int64_t n_patterns, int n_s
 int kpdi_nlopt_simplex_selftest(kpdi_ctx *ctx, int kind, int nvar, const double *x0,
                                 const double *lower, const double *upper, const double *xstep,
                                 double ftol_rel, int maxeval, double *result);
+/* scipy.optimize.differential_evolution of SciPy 1.15.3 with strategy="best1bin" and polish=False
+ * (csrc/differential_evolution.h) for every start of every pattern, each from numpy.random.RandomState(seeds[job]).
+ * There is no x0.  lower / upper: required and finite, lower == upper allowed (the variable is held).
+ * members: the population SciPy works out, max(5, popsize * max(1, nvar - number of held variables)), the same for
+ * every job, within 5..KPDI_DE_POP_MAX.  maxiter >= 0 generations.  mutation_hi = NaN: `mutation` is the number
+ * mutation_lo; else the dither pair, mutation_lo <= mutation_hi; both within [0, 2).  init: 0 "latinhypercube",
+ * 1 "random".  updating: 0 "immediate", 1 "deferred".  seeds: one per job, n_patterns x n_starts.
+ * Result rows and trace as kpdi_refine_solve_powell (fun, nfev, nit, x). */
+#define KPDI_DE_POP_MAX 256
+int kpdi_refine_solve_de(kpdi_ctx *ctx, int mode, int64_t n_patterns, int n_starts, const double *fixed,
+                         const double *lower, const double *upper, int members, int maxiter, double tol,
+                         double atol, double mutation_lo, double mutation_hi, double recombination, int init,
+                         int updating, const uint32_t *seeds, double *results, int64_t trace_job,
+                         double *trace, int trace_capacity);
+/* csrc/differential_evolution.h alone on an analytic f64 objective, nvar <= 6: kinds 0..4 of kpdi_powell_selftest,
+ * 5: the sum of (i + 1) (d d + 0.1 d), d = |x[i]|, whose minimum sits on the lower bound of a box from 0 (trial
+ * vectors leave the box and are drawn again), 6: +inf everywhere, 7: 0.1 everywhere.  Options as
+ * kpdi_refine_solve_de.  result: fun, nfev, nit, success (1 | 0), x[0..nvar). */
+int kpdi_de_selftest(kpdi_ctx *ctx, int kind, int nvar, const double *lower, const double *upper, int members,
+                     int maxiter, double tol, double atol, double mutation_lo, double mutation_hi,
+                     double recombination, int init, int updating, uint32_t seed, double *result);
+/* The random stream of csrc/differential_evolution.h alone, from numpy.random.RandomState(seed): `program` holds n
+ * rows (op, a, b) of doubles - 0: uniform(), 1: uniform(a, b), 2: randint(0, a) with 1 <= a < 2^31, 3: shuffle of a
+ * persistent arange(a) (made anew when a changes), 4: permutation(range(a)); a <= KPDI_DE_POP_MAX for 3 and 4.
+ * out: the raw 64 bits of what they return, one word per draw, `a` words for 3 and 4; out_words must be their exact
+ * count. */
+int kpdi_mt19937_selftest(kpdi_ctx *ctx, uint32_t seed, const double *program, int n, uint64_t *out,
+                          int64_t out_words);
 
 /* The top-k merge kernels alone, on lists the caller makes (tests/test_gpu_merge.py): everything is host memory.
  * kpdi_merge_selftest: n_src <= 3 sources; src_scores / src_idx / src_cnt are arrays of n_src host pointers

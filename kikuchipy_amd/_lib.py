@@ -188,6 +188,11 @@ SIGNATURES = {
     "kpdi_powell_selftest": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _i, _i, _vp]),
     "kpdi_refine_solve_nlopt": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),
     "kpdi_nlopt_simplex_selftest": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, C.c_double, _i, _vp]),
+    "kpdi_refine_solve_de": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double,
+                                  C.c_double, _i, _i, _vp, _vp, _i64, _vp, _i]),
+    "kpdi_de_selftest": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                              _i, _i, C.c_uint32, _vp]),
+    "kpdi_mt19937_selftest": (_i, [_vp, C.c_uint32, _vp, _i, _vp, _i64]),
     "kpdi_merge_selftest": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.c_uint32,
                                  _vp, _vp, _i, _vp, _vp]),
     "kpdi_merge64_selftest": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i64, _i, _i, _i64, _i64, _vp, _i, _i, _i,
@@ -983,6 +988,66 @@ class Context:
                                              float(ftol_rel), int(maxeval or 0), _ptr(res)))
         return res
 
+    @staticmethod
+    def _de_mutation(mutation):
+        """(lo, hi) as the library takes `mutation`: hi = NaN for one number, else the pair as given."""
+        if np.ndim(mutation) == 0:
+            return float(mutation), float("nan")
+        lo, hi = mutation
+        return float(lo), float(hi)
+
+    def refine_solve_de(self, mode, fixed, lower, upper, members, maxiter=1000, tol=0.01, atol=0.0, mutation=(0.5, 1.0),
+                        recombination=0.7, init=0, updating=0, seeds=0, trace_job=None, trace_capacity=0):
+        """`scipy.optimize.differential_evolution(strategy="best1bin", polish=False)` for every start on the device
+        (kpdi_refine_solve_de), job j from `numpy.random.RandomState(seeds[j])`.  lower, upper: (n_patterns, n_starts,
+        nvar), finite; members: the population; mutation: a number or the ordered dither pair; init: 0 latinhypercube,
+        1 random; updating: 0 immediate, 1 deferred; seeds: one integer for every job or one per job.  Returns the
+        (n_patterns, n_starts, 3 + nvar) rows fun, nfev, nit, x, and with `trace_job` the trace as `refine_solve_powell`."""
+        if lower is None or upper is None:
+            raise KpdiError("differential evolution searches within bounds: give lower and upper")
+        nvar, lo, f, _, hi, res = self._solve_arrays(mode, lower, fixed, None, upper)
+        n_jobs = lo.shape[0] * lo.shape[1]
+        seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32).ravel(), (n_jobs,)))
+        m_lo, m_hi = self._de_mutation(mutation)
+        trace = None
+        if trace_job is not None:
+            if int(trace_capacity) < 1:
+                raise KpdiError("a trace needs trace_capacity >= 1")
+            trace = np.zeros((int(trace_capacity), nvar + 1), dtype=np.float64)
+        check(self._f.refine_solve_de(self._h, int(mode), lo.shape[0], lo.shape[1], _ptr(f), _ptr(lo), _ptr(hi), int(members),
+                                      int(maxiter), float(tol), float(atol), m_lo, m_hi, float(recombination), int(init),
+                                      int(updating), _ptr(seeds), _ptr(res), int(trace_job or 0), _ptr(trace),
+                                      int(trace_capacity) if trace is not None else 0))
+        res = res[:, :, :3 + nvar]
+        if trace is None:
+            return res
+        total = int(res.reshape(-1, 3 + nvar)[int(trace_job), 1])
+        return res, trace[:min(total, trace.shape[0])], total
+
+    def de_selftest(self, kind, lower, upper, members, maxiter=1000, tol=0.01, atol=0.0, mutation=(0.5, 1.0),
+                    recombination=0.7, init=0, updating=0, seed=0):
+        """csrc/differential_evolution.h alone on an analytic objective (kpdi_de_selftest): fun, nfev, nit, success, x."""
+        lo = np.ascontiguousarray(lower, dtype=np.float64).ravel()
+        hi = np.ascontiguousarray(upper, dtype=np.float64).ravel()
+        if lo.size != hi.size:
+            raise KpdiError("lower and upper must have one value per variable")
+        m_lo, m_hi = self._de_mutation(mutation)
+        res = np.empty(4 + lo.size, dtype=np.float64)
+        check(self._f.de_selftest(self._h, int(kind), lo.size, _ptr(lo), _ptr(hi), int(members), int(maxiter), float(tol),
+                                  float(atol), m_lo, m_hi, float(recombination), int(init), int(updating), int(seed),
+                                  _ptr(res)))
+        return res
+
+    def mt19937_selftest(self, seed, program):
+        """The random stream of csrc/differential_evolution.h alone (kpdi_mt19937_selftest).  program: rows (op, a, b) -
+        0: uniform(), 1: uniform(a, b), 2: randint(0, a), 3: shuffle of a persistent arange(a), 4: permutation(range(a)).
+        Returns the raw 64 bits of every value drawn (uint64)."""
+        prog = np.ascontiguousarray(program, dtype=np.float64).reshape(-1, 3)
+        words = int(sum(int(a) if op >= 3 else 1 for op, a, _ in prog))
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        check(self._f.mt19937_selftest(self._h, int(seed), _ptr(prog), prog.shape[0], _ptr(out), words))
+        return out[:words]
+
     def merge_selftest(self, sources, m, k, out_scores, out_idx, out_offset=0, segments=None, seg_sources=0, force=-1):
         """merge.hip alone (kpdi_merge_selftest).  sources: up to three dicts of scores (float32), idx (int32), cnt
         (int32 (m, lists) or None), lists, len, row_stride, list_stride; out_scores / out_idx: (m, out_stride), prefilled.
@@ -1643,6 +1708,15 @@ class Group(Context):
 
     def nlopt_simplex_selftest(self, *args, **kwargs):
         return self.root.nlopt_simplex_selftest(*args, **kwargs)
+
+    def refine_solve_de(self, *args, **kwargs):
+        return self.root.refine_solve_de(*args, **kwargs)
+
+    def de_selftest(self, *args, **kwargs):
+        return self.root.de_selftest(*args, **kwargs)
+
+    def mt19937_selftest(self, *args, **kwargs):
+        return self.root.mt19937_selftest(*args, **kwargs)
 
     def orientation_similarity_map(self, *args, **kwargs):
         return self.root.orientation_similarity_map(*args, **kwargs)

@@ -373,6 +373,35 @@ int nlopt_check_search(const double *x0, size_t count, const double *xstep, int 
   return KPDI_OK;
 }
 
+// SciPy's own validation of the options the device solver takes (scipy/optimize/_differentialevolution.py:823-831)
+// and what the LDS population holds
+int de_check_options(const kpdi::DeOptions &de) {
+  if (de.members < 5 || de.members > KPDI_DE_POP_MAX)
+    return fail(KPDI_EINVAL, "differential evolution - the population must have 5..%d members, got %d", KPDI_DE_POP_MAX,
+                de.members);
+  if (de.maxiter < 0) return fail(KPDI_EINVAL, "differential evolution - maxiter must not be negative");
+  if (std::isnan(de.tol) || std::isnan(de.atol) || std::isnan(de.recombination))
+    return fail(KPDI_EINVAL, "differential evolution - tol, atol or recombination is NaN");
+  const bool pair = !std::isnan(de.mutation_hi);
+  if (!(de.mutation_lo >= 0.0 && de.mutation_lo < 2.0) || (pair && !(de.mutation_hi >= de.mutation_lo && de.mutation_hi < 2.0)))
+    return fail(KPDI_EINVAL, "differential evolution - the mutation constant must lie in [0, 2), a pair in order");
+  if (de.init != 0 && de.init != 1)
+    return fail(KPDI_EINVAL, "differential evolution - init must be 0 (latinhypercube) or 1 (random)");
+  if (de.updating != 0 && de.updating != 1)
+    return fail(KPDI_EINVAL, "differential evolution - updating must be 0 (immediate) or 1 (deferred)");
+  return KPDI_OK;
+}
+
+int de_check_bounds(const double *lower, const double *upper, size_t count) {
+  for (size_t i = 0; i < count; ++i) {
+    if (!std::isfinite(lower[i]) || !std::isfinite(upper[i]))
+      return fail(KPDI_EINVAL, "differential evolution - bounds must be finite for every variable");
+    if (lower[i] > upper[i])
+      return fail(KPDI_EINVAL, "differential evolution - one of the lower bounds is greater than an upper bound.");
+  }
+  return KPDI_OK;
+}
+
 // what a solver plugs into refine_solve: everything else of a solve is the same for every solver
 struct RefineSolver {
   int (*check_bounds)(const double *lower, const double *upper, size_t count);
@@ -386,9 +415,10 @@ struct RefineSolver {
 int refine_solve(kpdi_ctx *c, const RefineSolver &solver, int mode, int64_t n_patterns, int n_starts, const double *x0,
                  const double *fixed, const double *lower, const double *upper, double xtol, double ftol, int maxiter,
                  int maxfev, double *results, int64_t trace_job, double *trace, int trace_capacity,
-                 const kpdi::NloptStep *xstep = nullptr) {
+                 const kpdi::NloptStep *xstep = nullptr, const kpdi::DeOptions *de = nullptr) {
+  // de: differential evolution - no x0, `de->seeds` one seed per job on the HOST
   if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
-  if (!x0 || !results) return fail(KPDI_EINVAL, "NULL argument");
+  if ((!x0 && !de) || !results) return fail(KPDI_EINVAL, "NULL argument");
   if ((lower == nullptr) != (upper == nullptr)) return fail(KPDI_EINVAL, "give both bounds or neither");
   if (n_starts <= 0) return fail(KPDI_EINVAL, "need at least one start per pattern");
   int rc = use_device(c);
@@ -406,6 +436,7 @@ int refine_solve(kpdi_ctx *c, const RefineSolver &solver, int mode, int64_t n_pa
     return fail(KPDI_EINVAL, "the trace needs a capacity of at least 1 and a job within 0..%lld", (long long)jobs - 1);
   const size_t nx = (size_t)jobs * a.nvar, nf = (size_t)jobs * a.nfixed;
   if (lower && (rc = solver.check_bounds(lower, upper, nx))) return rc;
+  if (de && !lower) return fail(KPDI_EINVAL, "differential evolution searches within bounds: give both");
   const size_t total = nx * (lower ? 3 : 1) + nf + 1;
   const size_t result_doubles = (size_t)jobs * kpdi::REFINE_RESULT_STRIDE;
   const size_t trace_doubles = trace ? (size_t)trace_capacity * (a.nvar + 1) : 0;
@@ -413,16 +444,22 @@ int refine_solve(kpdi_ctx *c, const RefineSolver &solver, int mode, int64_t n_pa
   HIPCHK(c->ref_out.reserve((result_doubles + trace_doubles) * sizeof(double)));
   double *d_x = c->ref_in.as<double>(), *d_f = d_x + nx, *d_lo = d_f + nf, *d_hi = d_lo + nx;
   double *d_trace = c->ref_out.as<double>() + result_doubles;
-  HIPCHK(hipMemcpyAsync(d_x, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (x0) HIPCHK(hipMemcpyAsync(d_x, x0, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (nf) HIPCHK(hipMemcpyAsync(d_f, fixed, nf * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (lower) {
     HIPCHK(hipMemcpyAsync(d_lo, lower, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_hi, upper, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
+  if (de) {
+    a.de = *de;
+    HIPCHK(c->ref_idx.reserve((size_t)jobs * sizeof(uint32_t)));
+    HIPCHK(hipMemcpyAsync(c->ref_idx.p, de->seeds, (size_t)jobs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    a.de.seeds = c->ref_idx.as<uint32_t>();
+  }
   HIPCHK(hipMemsetAsync(c->ref_out.p, 0, (result_doubles + trace_doubles) * sizeof(double), c->stream));
   a.n_jobs = jobs;
   a.n_starts = n_starts;
-  a.x0 = d_x;
+  a.x0 = x0 ? d_x : nullptr;
   a.fixed = d_f;
   a.lower = lower ? d_lo : nullptr;
   a.upper = lower ? d_hi : nullptr;
@@ -561,6 +598,68 @@ int kpdi_refine_solve_nlopt(kpdi_ctx *c, int mode, int64_t n_patterns, int n_sta
   }
   return refine_solve(c, nlopt, mode, n_patterns, n_starts, x0, fixed, lower, upper, 0.0, ftol_rel, 0, maxeval, results, 0,
                       nullptr, 0, &step);
+}
+
+int kpdi_refine_solve_de(kpdi_ctx *c, int mode, int64_t n_patterns, int n_starts, const double *fixed, const double *lower,
+                         const double *upper, int members, int maxiter, double tol, double atol, double mutation_lo,
+                         double mutation_hi, double recombination, int init, int updating, const uint32_t *seeds,
+                         double *results, int64_t trace_job, double *trace, int trace_capacity) {
+  static const RefineSolver de_solver = {de_check_bounds,
+                                         [](int, int maxiter, int, int *it, int *fev) {
+                                           *it = maxiter;
+                                           *fev = 0;
+                                         },
+                                         kpdi::launch_refine_solve_de};
+  if (!lower || !upper || !seeds) return fail(KPDI_EINVAL, "NULL argument (bounds and seeds are required)");
+  const kpdi::DeOptions de{members, maxiter, init, updating, tol, atol, mutation_lo, mutation_hi, recombination, seeds};
+  int rc = de_check_options(de);
+  if (rc) return rc;
+  return refine_solve(c, de_solver, mode, n_patterns, n_starts, nullptr, fixed, lower, upper, tol, atol, maxiter, 0, results,
+                      trace_job, trace, trace_capacity, nullptr, &de);
+}
+
+int kpdi_de_selftest(kpdi_ctx *c, int kind, int nvar, const double *lower, const double *upper, int members, int maxiter,
+                     double tol, double atol, double mutation_lo, double mutation_hi, double recombination, int init,
+                     int updating, uint32_t seed, double *result) {
+  if (!c || !lower || !upper || !result) return fail(KPDI_EINVAL, "NULL argument");
+  if (kind < 0 || kind > 7) return fail(KPDI_EINVAL, "kind must be within 0..7");
+  if (nvar < 1 || nvar > 6) return fail(KPDI_EINVAL, "nvar must be within 1..6");
+  const kpdi::DeOptions de{members, maxiter, init, updating, tol, atol, mutation_lo, mutation_hi, recombination, nullptr};
+  int rc = de_check_options(de);
+  if (rc) return rc;
+  if ((rc = de_check_bounds(lower, upper, (size_t)nvar))) return rc;
+  rc = use_device(c);
+  if (rc) return rc;
+  SelftestIn in;
+  rc = selftest_upload(c, nvar, lower, lower, upper, 4 + nvar, &in);  // the x0 slot is not used
+  if (rc) return rc;
+  HIPCHK(kpdi::launch_de_selftest(kind, nvar, in.lo, in.hi, de, seed, c->ref_out.as<double>(), c->stream));
+  return selftest_download(c, result, 4 + nvar);
+}
+
+int kpdi_mt19937_selftest(kpdi_ctx *c, uint32_t seed, const double *program, int n, uint64_t *out, int64_t out_words) {
+  if (!c || !program || !out) return fail(KPDI_EINVAL, "NULL argument");
+  if (n < 1 || n > (1 << 16)) return fail(KPDI_EINVAL, "between 1 and 65536 draws");
+  int64_t words = 0;
+  for (int r = 0; r < n; ++r) {
+    const double op = program[3 * r], a = program[3 * r + 1], b = program[3 * r + 2];
+    if (!(op == 0 || op == 1 || op == 2 || op == 3 || op == 4)) return fail(KPDI_EINVAL, "draw %d: unknown op", r);
+    if (op == 1 && !(std::isfinite(a) && std::isfinite(b))) return fail(KPDI_EINVAL, "draw %d: uniform(a, b) needs finite a, b", r);
+    if (op >= 2 && !(a == std::floor(a) && a >= 1 && a < 2147483648.0)) return fail(KPDI_EINVAL, "draw %d: needs an integer a >= 1", r);
+    if (op >= 3 && a > KPDI_DE_POP_MAX) return fail(KPDI_EINVAL, "draw %d: at most %d entries", r, KPDI_DE_POP_MAX);
+    words += op >= 3 ? (int64_t)a : 1;
+  }
+  if (words != out_words) return fail(KPDI_EINVAL, "the program makes %lld words, room for %lld was given", (long long)words, (long long)out_words);
+  int rc = use_device(c);
+  if (rc) return rc;
+  HIPCHK(c->ref_in.reserve((size_t)3 * n * sizeof(double)));
+  HIPCHK(c->ref_out.reserve((size_t)(words + 1) * sizeof(uint64_t)));
+  HIPCHK(hipMemcpyAsync(c->ref_in.p, program, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(c->ref_out.p, 0, (size_t)(words + 1) * sizeof(uint64_t), c->stream));
+  HIPCHK(kpdi::launch_mt19937_selftest(seed, c->ref_in.as<double>(), n, c->ref_out.as<uint64_t>(), words, c->stream));
+  HIPCHK(hipMemcpyAsync(out, c->ref_out.p, (size_t)words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return KPDI_OK;
 }
 
 int kpdi_nlopt_simplex_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0, const double *lower,

@@ -317,6 +317,11 @@ struct NloptStep {  // the initial step of the LN_NELDERMEAD search, one value p
   int given;
   double v[6];
 };
+struct DeOptions {  // differential evolution (differential_evolution.h)
+  int members, maxiter, init, updating;  // population, generations, DE_INIT_*, DE_IMMEDIATE / DE_DEFERRED
+  double tol, atol, mutation_lo, mutation_hi, recombination;  // mutation_hi = NaN: `mutation` is one number
+  const uint32_t *seeds;  // [n_jobs] on the device (launch_refine_solve_de only)
+};
 struct RefineLaunch {
   int mode, nvar, nfixed, n_starts;
   int64_t n_jobs;        // solve: patterns * starts; objective: evaluations
@@ -333,6 +338,7 @@ struct RefineLaunch {
   double xatol, fatol;
   int maxiter, maxfun;
   NloptStep xstep;              // launch_refine_solve_nlopt only
+  DeOptions de;                 // launch_refine_solve_de only
   double *results;              // [n_jobs][REFINE_RESULT_STRIDE]: fun, nfev, nit, x[nvar]
 };
 constexpr int REFINE_RESULT_STRIDE = 9;
@@ -354,6 +360,15 @@ hipError_t launch_refine_solve_nlopt(const RefineLaunch &a, hipStream_t s);
 hipError_t launch_nlopt_simplex_selftest(int kind, int nvar, const double *x0, const double *lower, const double *upper,
                                          const double *xstep, double ftol_rel, int maxeval, double *result,
                                          hipStream_t s);
+// SciPy's differential evolution (differential_evolution.h): a.de, no x0, bounds required; trace as for Powell
+hipError_t launch_refine_solve_de(const RefineLaunch &a, int64_t trace_job, double *trace, int trace_capacity,
+                                  hipStream_t s);
+// result: fun, nfev, nit, success, x[0..nvar)
+hipError_t launch_de_selftest(int kind, int nvar, const double *lower, const double *upper, const DeOptions &de,
+                              unsigned seed, double *result, hipStream_t s);
+// out: capacity + 1 words, the last one the number of words the program makes
+hipError_t launch_mt19937_selftest(unsigned seed, const double *program, int n, uint64_t *out, long long capacity,
+                                   hipStream_t s);
 hipError_t launch_nelder_mead_selftest(int kind, int nvar, const double *x0, const double *lower, const double *upper,
                                        double xatol, double fatol, int maxiter, int maxfun, double *result,
                                        hipStream_t s);

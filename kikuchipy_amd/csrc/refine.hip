@@ -15,7 +15,9 @@
 // by `refine_solve_powell_kernel` (kpdi_powell_selftest pins it the same way); the third is the simplex search
 // NLopt offers as LN_NELDERMEAD, restated in nlopt_simplex.h from the text of DESIGN.md section 21 and run by
 // `refine_solve_nlopt_kernel` (kpdi_nlopt_simplex_selftest pins kernel against header; NLopt itself is not compared
-// with).  Every other optimiser stays on the host and calls `refine_objective_kernel`.
+// with); the fourth is scipy.optimize.differential_evolution with strategy="best1bin" over NumPy's legacy RandomState,
+// restated in differential_evolution.h and run by `refine_solve_de_kernel` (kpdi_de_selftest and kpdi_mt19937_selftest
+// pin it against SciPy and NumPy).  Every other optimiser stays on the host and calls `refine_objective_kernel`.
 //
 // One workgroup per (experimental pattern, start) runs the WHOLE optimisation: thread 0
 // owns the simplex (LDS) and decides the next point; all 256 threads evaluate the
@@ -33,6 +35,7 @@
 
 #include <climits>
 
+#include "differential_evolution.h"
 #include "nlopt_simplex.h"
 #include "powell.h"
 
@@ -609,6 +612,102 @@ __global__ void nlopt_simplex_selftest_kernel(int kind, int nvar, const double *
   for (int i = 0; i < nvar; ++i) result[3 + i] = ns.x[i];
 }
 
+// ---- SciPy's differential evolution (differential_evolution.h) on the device, run like Powell: every thread runs the
+// solver on the uniform objective values, so all 256 meet at the barriers inside `refine_objective`.  What Powell keeps
+// in private memory is too large here - the population, the trial population, the energies, the index array and the
+// 624 words of the random stream - and lives in LDS: thread 0 alone draws and writes, `DeTeam::sync` separates its
+// writes from the reads of the others.
+// LDS: DeStorage<6, 256> = 2500 (stream) + 2 x 12288 (population, trial) + 2 x 2048 (energies) + 2 x 1024 (index, fill)
+// + 48 = 33 272 B, + `red` = 32.6 KiB: four workgroups per CU (what __launch_bounds__(REF_THREADS, 4) leaves registers
+// for) take 130 of the CU's 160 KiB.  The population of the defaults is 45 (three variables) or 90 (six); larger ones than
+// DE_POP_MAX stay on the host.
+// The evaluations of one job stay serial: with updating="immediate" every trial is built from the population the trial
+// before it may have changed, and the number of draws of _ensure_constraint depends on the values.
+constexpr int DE_POP_MAX = KPDI_DE_POP_MAX;
+using DeState = DeStorage<NV_MAX, DE_POP_MAX>;
+static_assert(sizeof(DeState) + 3 * REF_THREADS / 64 * sizeof(double) <= 40 * 1024, "four workgroups per CU: 160 KiB of LDS");
+
+struct DeTeam {
+  __device__ bool leader() const { return threadIdx.x == 0; }
+  __device__ void sync() const { __syncthreads(); }
+};
+
+__global__ __launch_bounds__(REF_THREADS, 4) void refine_solve_de_kernel(
+    int mode, int nvar, int nfixed, int n_starts, const double *fixed, const double *lower, const double *upper,
+    RefineGeom g, const float *patterns, const double *sqnorm, DeOptions de, double *results, long long trace_job,
+    double *trace, int trace_capacity) {
+  __shared__ DeState st;
+  __shared__ double red[3 * REF_THREADS / 64];
+  const int64_t job = blockIdx.x;  // (pattern, start)
+  const int64_t pat_id = job / n_starts;
+  RefinePowellEval ev;
+  ev.mode = mode;
+  ev.nvar = nvar;
+  ev.fx = fixed + job * nfixed;
+  ev.g = &g;
+  ev.pat = patterns + pat_id * g.k;
+  ev.sqn = sqnorm[pat_id];
+  ev.red = red;
+  ev.trace = job == trace_job ? trace : nullptr;
+  ev.trace_capacity = trace_capacity;
+  ev.n_eval = 0;
+  DifferentialEvolution<NV_MAX, DE_POP_MAX, RefinePowellEval, DeTeam> solver(ev, st);
+  solver.solve(nvar, lower + job * nvar, upper + job * nvar, de.members, de.maxiter, de.tol, de.atol, de.mutation_lo,
+               de.mutation_hi, de.recombination, de.init, de.updating, de.seeds[job]);
+  if (threadIdx.x == 0) {
+    double *o = results + job * RESULT_STRIDE;
+    o[0] = solver.fun;
+    o[1] = (double)solver.nfev;
+    o[2] = (double)solver.nit;
+    for (int i = 0; i < nvar; ++i) o[3 + i] = solver.x[i];
+  }
+}
+
+// ---- differential_evolution.h alone on analytic f64 objectives: kinds 0..4 of `PowellSelftestEval`, 5 = a bowl whose
+// minimum sits on the lower bound of a box from 0, sum((i + 1) (d d + 0.1 d)) with d = |x[i]|, on which trial vectors
+// leave [0, 1] and are drawn again, 6 = +inf everywhere, 7 = 0.1 everywhere
+struct DeSelftestEval {
+  int kind, n;
+  __device__ double eval(const double *x) const {
+    if (kind == 6) return HUGE_VAL;
+    if (kind == 7) return 0.1;
+    if (kind != 5) return PowellSelftestEval{kind, n}.eval(x);
+    double acc = 0.0;
+    for (int i = 0; i < n; ++i) {
+      const double d = fabs(x[i]);
+      const double t = (double)(i + 1) * (d * d + 0.1 * d);
+      acc = i == 0 ? t : acc + t;
+    }
+    return acc;
+  }
+};
+
+// result: fun, nfev, nit, success, x[0..nvar)
+__global__ void de_selftest_kernel(int kind, int nvar, const double *lower, const double *upper, DeOptions de,
+                                   unsigned seed, double *result) {
+  __shared__ DeState st;
+  if (threadIdx.x != 0) return;
+  DeSelftestEval ev{kind, nvar};
+  DifferentialEvolution<NV_MAX, DE_POP_MAX, DeSelftestEval> solver(ev, st);
+  solver.solve(nvar, lower, upper, de.members, de.maxiter, de.tol, de.atol, de.mutation_lo, de.mutation_hi,
+               de.recombination, de.init, de.updating, seed);
+  result[0] = solver.fun;
+  result[1] = (double)solver.nfev;
+  result[2] = (double)solver.nit;
+  result[3] = solver.success ? 1.0 : 0.0;
+  for (int i = 0; i < nvar; ++i) result[4 + i] = solver.x[i];
+}
+
+// the random stream alone: `mt_program` from RandomState(seed); out[0..capacity) the words, out[capacity] their count
+__global__ void mt19937_selftest_kernel(unsigned seed, const double *program, int n, unsigned long long *out,
+                                        long long capacity) {
+  __shared__ Mt19937 mt;
+  __shared__ int index[DE_POP_MAX], scratch[DE_POP_MAX];
+  if (threadIdx.x != 0) return;
+  mt_seed(mt, seed);
+  out[capacity] = (unsigned long long)mt_program(mt, program, n, index, scratch, DE_POP_MAX, (uint64_t *)out, capacity);
+}
+
 // ---- launchers
 static RefineGeom make_geom(const RefineLaunch &a) {
   RefineGeom g;
@@ -695,6 +794,31 @@ hipError_t launch_nlopt_simplex_selftest(int kind, int nvar, const double *x0, c
                                          hipStream_t s) {
   hipLaunchKernelGGL(nlopt_simplex_selftest_kernel, dim3(1), dim3(64), 0, s, kind, nvar, x0, lower, upper, xstep, ftol_rel,
                      maxeval, result);
+  return hipGetLastError();
+}
+
+// a.de: the options and the device array of one seed per job; bounds are required
+hipError_t launch_refine_solve_de(const RefineLaunch &a, int64_t trace_job, double *trace, int trace_capacity,
+                                  hipStream_t s) {
+  if (a.n_jobs <= 0) return hipSuccess;
+  if (a.de.members < 5 || a.de.members > DE_POP_MAX || !a.lower || !a.upper || !a.de.seeds) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(refine_solve_de_kernel, dim3((unsigned)a.n_jobs), dim3(REF_THREADS), 0, s, a.mode, a.nvar, a.nfixed,
+                     a.n_starts, a.fixed, a.lower, a.upper, make_geom(a), a.patterns, a.sqnorm, a.de, a.results,
+                     (long long)trace_job, trace, trace_capacity);
+  return hipGetLastError();
+}
+
+hipError_t launch_de_selftest(int kind, int nvar, const double *lower, const double *upper, const DeOptions &de,
+                              unsigned seed, double *result, hipStream_t s) {
+  if (de.members < 5 || de.members > DE_POP_MAX || nvar < 1 || nvar > NV_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(de_selftest_kernel, dim3(1), dim3(64), 0, s, kind, nvar, lower, upper, de, seed, result);
+  return hipGetLastError();
+}
+
+hipError_t launch_mt19937_selftest(unsigned seed, const double *program, int n, uint64_t *out, long long capacity,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(mt19937_selftest_kernel, dim3(1), dim3(64), 0, s, seed, program, n, (unsigned long long *)out,
+                     capacity);
   return hipGetLastError();
 }
 

@@ -20,8 +20,16 @@ search is the one csrc/nlopt_simplex.h restates from the text of DESIGN.md secti
 an installed NLopt.  KPDI_REFINE_NLOPT=host, read at each call, sends the call to the host path below, which needs
 `nlopt`.
 
+`method="differential_evolution"` with its plain keywords (`strategy="best1bin"`, `maxiter`, `popsize`, `tol`, `atol`,
+`mutation`, `recombination`, `seed`, `polish`, `init="latinhypercube" | "random"`, `updating`) runs its evolution on the
+device as well (`kpdi_refine_solve_de`, `_device_de_options`): one launch for a block of points, each (pattern, start)
+from its own `numpy.random.RandomState`, bit for bit what SciPy returns for the same seed.  With `polish=True` (SciPy's
+default) the L-BFGS-B polish that `DifferentialEvolutionSolver.solve` ends with runs on the host afterwards, per job, and
+is the part still paid per evaluation (one objective launch and one synchronisation each); `polish=False` makes no
+objective call from the host.  KPDI_REFINE_DE=host, read at each call, sends the call to the host path below.
+
 Every other optimiser the reference can dispatch to (SciPy's other local methods, Powell with `direc`, `callback` or
-`return_all`, its global methods) keeps ITS optimiser on the host, called with the reference's
+`return_all`, its other global methods, differential evolution with anything else) keeps ITS optimiser on the host, called with the reference's
 arguments, with the objective evaluated on the device (`_HostOptimizer`); `compute=False` returns a
 `DeferredRefinement` in place of the reference's lazy Dask array.
 """
@@ -38,6 +46,7 @@ MODES = {"ori": _lib.REFINE_ORI, "pc": _lib.REFINE_PC, "ori_pc": _lib.REFINE_ORI
 # indexing/_refinement/__init__.py:33-66
 SUPPORTED_OPTIMIZATION_METHODS = ["minimize", "ln_neldermead", "basinhopping", "differential_evolution",
                                   "dual_annealing", "shgo"]
+DE_POP_MAX = 256  # KPDI_DE_POP_MAX of include/kpdi.h: the largest population the device solver holds
 
 
 # --------------------------------------------------------------------------- rotations
@@ -190,7 +199,8 @@ def _nelder_mead_options(method, method_kwargs, initial_step, maxeval):
 class _HostOptimizer:
     """Every optimiser of the reference other than plain Nelder-Mead (SciPy local methods with their
     options, the SciPy global methods, NLopt's LN_NELDERMEAD; plain Powell only when `_device_powell_options`
-    declines it or KPDI_REFINE_POWELL=host asks for this path): the OPTIMISER runs on the host exactly as
+    declines it or KPDI_REFINE_POWELL=host asks for this path, plain differential evolution only when
+    `_device_de_options` / `_de_members` decline it or KPDI_REFINE_DE=host asks for it): the OPTIMISER runs on the host exactly as
     in the reference (indexing/_refinement/_solvers.py:79-250, :464-600: same call, same keyword
     arguments), the OBJECTIVE - master-pattern projection + NCC of one pattern - is one call into the
     device per evaluation (`kpdi_refine_objective`).  Slow next to the on-device simplex search (one
@@ -305,6 +315,109 @@ def _device_powell_options(host):
     except (TypeError, ValueError):
         return None
     return out
+
+
+def _real(value):
+    """`value` as a float if it is a finite real number (no bool, no string), else None."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        return None
+    value = float(value)
+    return value if np.isfinite(value) else None
+
+
+def _integer(value, low, high):
+    """`value` as an int if it is an integer (no bool) within [low, high), else None."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        return None
+    return int(value) if low <= int(value) < high else None
+
+
+def _device_de_options(host):
+    """dict(maxiter, popsize, tol, atol, mutation, recombination, seed, polish, init, updating) if `host` is
+    `scipy.optimize.differential_evolution` with nothing but the keywords the device solver restates
+    (csrc/differential_evolution.h), else None.  `mutation` comes back as (lo, hi): (m, NaN) for a number, SciPy's sorted
+    dither pair otherwise; `init` 0 = "latinhypercube", 1 = "random"; `updating` 0 = "immediate", 1 = "deferred".
+    `rng`, a generator instance as `seed`, `callback`, `workers`, `constraints`, `x0`, `integrality`, `vectorized`, other
+    strategies and initialisations, every keyword this function does not know and every value SciPy would refuse keep
+    the optimiser on the host (where SciPy raises its own error)."""
+    if host is None or host.method != "differential_evolution":
+        return None
+    kw = host.kwargs
+    if set(kw) - {"strategy", "maxiter", "popsize", "tol", "atol", "mutation", "recombination", "seed", "polish", "init",
+                  "updating", "disp"}:
+        return None
+    if kw.get("strategy", "best1bin") != "best1bin" or kw.get("disp"):
+        return None
+    out = {}
+    out["maxiter"] = 1000 if kw.get("maxiter") is None else _integer(kw["maxiter"], 0, 2**31)
+    out["popsize"] = _integer(kw.get("popsize", 15), 1, 2**31)
+    out["tol"], out["atol"] = _real(kw.get("tol", 0.01)), _real(kw.get("atol", 0))
+    mutation = kw.get("mutation", (0.5, 1))
+    if isinstance(mutation, (tuple, list, np.ndarray)) and np.ndim(mutation) == 1 and len(mutation) == 2:
+        pair = sorted(m for m in (_real(mutation[0]), _real(mutation[1])) if m is not None)  # self.dither.sort()
+        out["mutation"] = tuple(pair) if len(pair) == 2 and all(0 <= m < 2 for m in pair) else None
+    else:
+        m = _real(mutation)
+        out["mutation"] = (m, float("nan")) if m is not None and 0 <= m < 2 else None
+    out["recombination"] = _real(kw.get("recombination", 0.7))
+    seed = kw.get("seed")
+    out["seed"] = None if seed is None else _integer(seed, 0, 2**32)
+    if seed is not None and out["seed"] is None:
+        return None
+    out["polish"] = kw.get("polish", True) if isinstance(kw.get("polish", True), bool) else None
+    init, updating = kw.get("init", "latinhypercube"), kw.get("updating", "immediate")
+    out["init"] = {"latinhypercube": 0, "random": 1}.get(init) if isinstance(init, str) else None
+    out["updating"] = {"immediate": 0, "deferred": 1}.get(updating) if isinstance(updating, str) else None
+    if any(value is None for name, value in out.items() if name != "seed"):
+        return None
+    return out
+
+
+def _de_members(popsize, lower, upper):
+    """`num_population_members` as SciPy works it out for every job (_differentialevolution.py:916-928: a variable
+    with lower == upper does not count), if it is the same for all of them and the device solver holds it, else None."""
+    nvar = lower.shape[-1]
+    held = np.count_nonzero(lower == upper, axis=-1)
+    members = np.unique(np.maximum(5, popsize * np.maximum(1, nvar - held)))
+    if members.size != 1 or members[0] > DE_POP_MAX:
+        return None
+    return int(members[0])
+
+
+def _de_seeds(seed, n_jobs):
+    """One 32-bit seed per job.  `seed=k`: every job starts from RandomState(k), as a fresh
+    `differential_evolution(..., seed=k)` call per job does in the reference.  `seed=None`: fresh entropy for each, not
+    reproducible, as in SciPy."""
+    if seed is None:
+        return np.random.SeedSequence().generate_state(n_jobs).astype(np.uint32)
+    return np.full(n_jobs, seed, dtype=np.uint32)
+
+
+def _job_objective(ctx, mode_code, i, fx):
+    """The objective of pattern i as SciPy calls it: one point -> a float, one launch."""
+    def fun(x):
+        return float(ctx.refine_objective(mode_code, [i], np.asarray(x, dtype=np.float64)[None], fx)[0])
+    return fun
+
+
+def _de_polish(ctx, mode_code, res, fixed, lower, upper):
+    """What `DifferentialEvolutionSolver.solve` does after the evolution (_differentialevolution.py:1224-1269), per job
+    and in place on the device's rows: L-BFGS-B from the best member within the bounds, its evaluations counted, its
+    result taken only if it is lower, successful and inside the bounds."""
+    import scipy.optimize
+
+    n, starts = res.shape[:2]
+    for i in range(n):
+        for s in range(starts):
+            fx = None if fixed is None else fixed[i, s][None]
+            limits = np.array([lower[i, s], upper[i, s]], dtype=float)
+            result = scipy.optimize.minimize(_job_objective(ctx, mode_code, i, fx), np.copy(res[i, s, 3:]),
+                                             method="L-BFGS-B", bounds=limits.T, constraints=())
+            res[i, s, 1] += result.nfev
+            if (result.fun < res[i, s, 0] and result.success and np.all(result.x <= limits[1])
+                    and np.all(limits[0] <= result.x)):
+                res[i, s, 0], res[i, s, 3:] = result.fun, result.x
+    return res
 
 
 class _DeviceNlopt:
@@ -599,6 +712,15 @@ def _run_refinement(mode, n, starts, x0, fixed, lower, upper, pats, signal_mask,
             # SciPy's Powell on the device: one launch, no objective call from the host
             return c.refine_solve_powell(MODES[mode], *block, powell["xtol"], powell["ftol"], powell["maxiter"] or 0,
                                          powell["maxfev"] or 0)
+        de = _device_de_options(host)
+        if de is not None and block[2] is not None and os.environ.get("KPDI_REFINE_DE", "").lower() != "host":
+            members = _de_members(de["popsize"], block[2], block[3])
+            if members is not None:
+                # SciPy's differential evolution on the device: one launch; only the polish calls the objective
+                res = c.refine_solve_de(MODES[mode], block[1], block[2], block[3], members, de["maxiter"], de["tol"],
+                                        de["atol"], de["mutation"], de["recombination"], de["init"], de["updating"],
+                                        _de_seeds(de["seed"], block[2].shape[0] * block[2].shape[1]))
+                return _de_polish(c, MODES[mode], res, *block[1:]) if de["polish"] else res
         # the reference's optimiser on the host, the objective on the device
         return _host_solve(c, MODES[mode], host, *block)
 
