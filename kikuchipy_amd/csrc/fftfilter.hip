@@ -21,6 +21,12 @@
 // is its 0 / 0; both give NaN before the cast.  C's cast of NaN to an integer is undefined, so the epilogue defines it:
 // integer dtypes get 0 (what NumPy's astype gives on x86-64 hosts for uint8 / uint16 / int8 / int16), float dtypes NaN.
 // Which path takes a shape: fftfilter_plan.h.
+//
+// Order of the f64 sum behind the mean, float32(sum / npix) (tests/_spectral_restate.py restates it): thread t of 256 adds,
+// path 0, the quads t, t + 256, ... of four consecutive pixels each (ff_load; a short last quad padded with zeros), path 1
+// the single pixels t, t + 256, ... (ff_stats_kernel); then block_reduce (pattern_dft.h).  Sums of integer patterns are
+// exact, so there the two paths give the same bits; float patterns may differ in the mean's last bit.  KPDI_FFT_FILTER_PATH=1
+// forces path 1, KPDI_PATTERN_BATCH=<patterns> caps a workspace batch (both read at each call, for the tests).
 #include "../../include/kpdi.h"
 #include "fftfilter_plan.h"
 #include "kernels.h"
@@ -28,6 +34,7 @@
 #include "prep_device.h"
 
 #include <algorithm>
+#include <cstdlib>
 #include <type_traits>
 
 namespace kpdi {
@@ -409,9 +416,17 @@ hipError_t launch_ff_t(const FfLaunch &a, const FfPlan &plan, hipStream_t s) {
 
 }  // namespace
 
+FfPlan fft_filter_launch_plan(int domain, int sy, int sx, int64_t n) {
+  bool force = false;
+  int64_t cap = 0;
+  if (const char *e = getenv("KPDI_FFT_FILTER_PATH")) force = atoi(e) == 1;  // tests: path 1 for any shape
+  if (const char *e = getenv("KPDI_PATTERN_BATCH")) cap = atoll(e) > 0 ? atoll(e) : 0;  // tests: several batches
+  return ff_plan(domain, sy, sx, n, force, cap);
+}
+
 hipError_t launch_fft_filter(const FfLaunch &a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  const FfPlan plan = ff_plan(a.domain, a.sy, a.sx, a.n);
+  const FfPlan plan = fft_filter_launch_plan(a.domain, a.sy, a.sx, a.n);
   if (plan.path < 0 || (plan.path == 0 && a.n >= (int64_t)INT32_MAX) ||
       (plan.path == 1 && plan.batch * std::max(plan.blocks_half, plan.blocks_pix) >= (int64_t)INT32_MAX))
     return hipErrorInvalidValue;

@@ -44,10 +44,12 @@ inline size_t ff_ws_pattern_bytes(int domain, int sy, int sx) {
 // path 1 LDS: the twiddles of the longer axis + the reduction
 inline size_t ff_ws_lds_bytes(int sy, int sx) { return (size_t)(sx > sy ? sx : sy) * 8 + FF_RED_BYTES; }
 
-// `n` patterns of sy x sx
-inline FfPlan ff_plan(int domain, int sy, int sx, int64_t n) {
+// `n` patterns of sy x sx.  `force_workspace`: path 1 for a shape path 0 takes (tests: KPDI_FFT_FILTER_PATH=1);
+// `max_batch` > 0: a cap on the patterns per batch of path 1 (tests: KPDI_PATTERN_BATCH)
+inline FfPlan ff_plan(int domain, int sy, int sx, int64_t n, bool force_workspace = false, int64_t max_batch = 0) {
   if (sy < 1 || sx < 1 || n < 1 || (domain != FF_DOMAIN_FREQUENCY && domain != FF_DOMAIN_SPATIAL)) return FfPlan{{-1}};
-  FfPlan p{pattern_path(ff_lds_path_bytes(domain, sy, sx), ff_ws_lds_bytes(sy, sx), ff_ws_pattern_bytes(domain, sy, sx), n)};
+  FfPlan p{pattern_path(ff_lds_path_bytes(domain, sy, sx), ff_ws_lds_bytes(sy, sx), ff_ws_pattern_bytes(domain, sy, sx), n,
+                        force_workspace, max_batch)};
   if (p.path == 1) {
     const size_t inter = (size_t)sy * half_cols(sx), npix = (size_t)sy * sx;
     p.blocks_half = (int)((inter + FF_THREADS - 1) / FF_THREADS);

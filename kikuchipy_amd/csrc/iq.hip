@@ -12,10 +12,18 @@
 // is applied to S here, so inertia = sum W S / sum c S is the full-spectrum sum exactly.  Sums of the DFT run in f32,
 // per-pattern statistics and the weighted sums in f64.
 // Which path takes a shape: iq_plan.h.
+//
+// Order of the f64 sums (tests/_spectral_restate.py restates it).  The pattern's sum, on both paths: thread t of 256 adds
+// the pixels t, t + 256, ... in turn, then block_reduce (pattern_dft.h).  The two weighted sums: path 0, thread t adds the
+// terms of the coefficients t, t + 256, ... in turn, then block_reduce; path 1, one term per thread, block_reduce per
+// workgroup of 256 coefficients (iq_cols_kernel), then the workgroups in order from 0 (iq_final_kernel).
+// KPDI_IQ_PATH=1 forces path 1, KPDI_PATTERN_BATCH=<patterns> caps a workspace batch (both read at each call, for the tests).
 #include "../../include/kpdi.h"
 #include "iq_plan.h"
 #include "kernels.h"
 #include "pattern_dft.h"
+
+#include <cstdlib>
 
 namespace kpdi {
 
@@ -205,9 +213,17 @@ hipError_t launch_iq_t(const IqLaunch &a, const IqPlan &plan, hipStream_t s) {
 
 }  // namespace
 
+IqPlan image_quality_launch_plan(int sy, int sx, int64_t n) {
+  bool force = false;
+  int64_t cap = 0;
+  if (const char *e = getenv("KPDI_IQ_PATH")) force = atoi(e) == 1;  // tests: path 1 for any shape
+  if (const char *e = getenv("KPDI_PATTERN_BATCH")) cap = atoll(e) > 0 ? atoll(e) : 0;  // tests: several batches
+  return iq_plan(sy, sx, n, force, cap);
+}
+
 hipError_t launch_image_quality(const IqLaunch &a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  const IqPlan plan = iq_plan(a.sy, a.sx, a.n);
+  const IqPlan plan = image_quality_launch_plan(a.sy, a.sx, a.n);
   if (plan.path < 0 || (plan.path == 0 && a.n >= (int64_t)INT32_MAX) ||
       (plan.path == 1 && plan.batch * plan.blocks_per_pattern >= (int64_t)INT32_MAX))
     return hipErrorInvalidValue;

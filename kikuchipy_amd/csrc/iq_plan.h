@@ -34,10 +34,12 @@ inline size_t iq_ws_pattern_bytes(int sy, int sx) {
   return inter * 8 + 3 * 8 + blocks * 2 * 8;
 }
 
-// `n` patterns of sy x sx; path = -1 when no path can take the shape
-inline IqPlan iq_plan(int sy, int sx, int64_t n) {
+// `n` patterns of sy x sx; path = -1 when no path can take the shape.  `force_workspace`: path 1 for a shape path 0
+// takes (tests: KPDI_IQ_PATH=1); `max_batch` > 0: a cap on the patterns per batch of path 1 (tests: KPDI_PATTERN_BATCH)
+inline IqPlan iq_plan(int sy, int sx, int64_t n, bool force_workspace = false, int64_t max_batch = 0) {
   if (sy < 1 || sx < 1 || n < 1) return IqPlan{{-1}};
-  IqPlan p{pattern_path(iq_lds_path_bytes(sy, sx), iq_ws_lds_bytes(sy, sx), iq_ws_pattern_bytes(sy, sx), n)};
+  IqPlan p{pattern_path(iq_lds_path_bytes(sy, sx), iq_ws_lds_bytes(sy, sx), iq_ws_pattern_bytes(sy, sx), n, force_workspace,
+                        max_batch)};
   if (p.path == 1) p.blocks_per_pattern = (int)(((size_t)sy * half_cols(sx) + IQ_THREADS - 1) / IQ_THREADS);
   return p;
 }

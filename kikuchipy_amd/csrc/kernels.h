@@ -6,6 +6,8 @@
 #include <vector>
 
 #include "clahe_plan.h"
+#include "fftfilter_plan.h"
+#include "iq_plan.h"
 #include "neighbours_plan.h"
 #include "downsample_plan.h"
 #include "select_plan.h"
@@ -403,6 +405,9 @@ struct IqLaunch {
   void *workspace; size_t workspace_bytes;  // path 1 of iq_plan.h
   float *out;             // [n]
 };
+// the plan launch_image_quality follows and kpdi_image_quality reserves the workspace by (read at each call:
+// KPDI_IQ_PATH=1 forces path 1, KPDI_PATTERN_BATCH=<patterns> caps a batch of path 1)
+IqPlan image_quality_launch_plan(int sy, int sx, int64_t n);
 hipError_t launch_image_quality(const IqLaunch &a, hipStream_t s);
 
 // ---- sums over detector rectangles (regionsum.hip) ---------------------------------
@@ -425,6 +430,9 @@ struct FfLaunch {
   float omin, omax;       // the dtype range (rescale_intensity)
   void *workspace; size_t workspace_bytes;  // path 1 of fftfilter_plan.h
 };
+// the plan launch_fft_filter follows and kpdi_fft_filter reserves the workspace by (read at each call:
+// KPDI_FFT_FILTER_PATH=1 forces path 1, KPDI_PATTERN_BATCH=<patterns> caps a batch of path 1)
+FfPlan fft_filter_launch_plan(int domain, int sy, int sx, int64_t n);
 hipError_t launch_fft_filter(const FfLaunch &a, hipStream_t s);
 
 // ---- intensity rescaling / normalization (intensity.hip) ----------------------------

@@ -188,7 +188,7 @@ int kpdi_image_quality(kpdi_ctx *c, int normalize, const double *weights, double
   if (rc) return rc;
   if (!iq_out) return fail(KPDI_EINVAL, "iq_out is NULL");
   const int sy = c->sy, sx = c->sx, h = kpdi::half_cols(sx);
-  const kpdi::IqPlan plan = kpdi::iq_plan(sy, sx, c->m_all);
+  const kpdi::IqPlan plan = kpdi::image_quality_launch_plan(sy, sx, c->m_all);  // (what launch_image_quality follows)
   if (plan.path < 0) return fail(KPDI_EINVAL, "image quality of %d x %d patterns: no kernel path takes this shape", sy, sx);
   rc = start_pattern_op(c);
   if (rc) return rc;
@@ -293,7 +293,8 @@ int kpdi_fft_filter(kpdi_ctx *c, int function_domain, const double *table, int t
     return fail(KPDI_EINVAL, "folded transfer function of %d x %d, patterns of %d x %d need %d x %d", ty, tx, sy, sx, sy, h);
   if (!freq && (ty < 1 || tx < 1 || (int64_t)ty * tx > (1 << 20)))
     return fail(KPDI_EINVAL, "spatial kernel of %d x %d", ty, tx);
-  const kpdi::FfPlan plan = kpdi::ff_plan(freq ? kpdi::FF_DOMAIN_FREQUENCY : kpdi::FF_DOMAIN_SPATIAL, sy, sx, c->m_all);
+  const kpdi::FfPlan plan =  // (what launch_fft_filter follows)
+      kpdi::fft_filter_launch_plan(freq ? kpdi::FF_DOMAIN_FREQUENCY : kpdi::FF_DOMAIN_SPATIAL, sy, sx, c->m_all);
   if (plan.path < 0) return fail(KPDI_EINVAL, "FFT filter of %d x %d patterns: no kernel path takes this shape", sy, sx);
   rc = start_pattern_op(c);
   if (rc) return rc;

@@ -42,10 +42,13 @@ struct PatternPath {
 };
 
 // `n` patterns: path 0 when its `lds` bytes fit, else path 1 (`ws_lds` bytes of LDS, `per` bytes of workspace per
-// pattern) in batches of as many patterns as PATTERN_WORKSPACE_CAP admits
-inline PatternPath pattern_path(size_t lds, size_t ws_lds, size_t per, int64_t n) {
+// pattern) in batches of as many patterns as PATTERN_WORKSPACE_CAP admits.  `force_workspace`: path 1 for a shape that
+// path 0 would take; `max_batch` > 0: at most that many patterns per batch (`workspace_bytes` follows).  Both are for
+// the tests, which reach the workspace path and a second batch at small shapes with them.
+inline PatternPath pattern_path(size_t lds, size_t ws_lds, size_t per, int64_t n, bool force_workspace = false,
+                                int64_t max_batch = 0) {
   PatternPath p{};
-  if (lds <= PATTERN_LDS_CAP) {
+  if (lds <= PATTERN_LDS_CAP && !force_workspace) {
     p.path = 0;
     p.lds_bytes = lds;
     p.batch = n;
@@ -59,6 +62,7 @@ inline PatternPath pattern_path(size_t lds, size_t ws_lds, size_t per, int64_t n
   p.path = 1;
   const int64_t fit = (int64_t)(PATTERN_WORKSPACE_CAP / per);
   p.batch = n < fit ? n : fit;
+  if (max_batch > 0 && p.batch > max_batch) p.batch = max_batch;
   p.workspace_bytes = (size_t)p.batch * per;
   return p;
 }

@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from _spectral_restate import block_sum  # the workgroup reduction's order, restated once
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 #        name: (navigation shape, pattern shape)
@@ -99,14 +101,7 @@ def mean_signal(x):
     t = np.zeros((m, THREADS))
     for r in range(rows):
         t = t + padded[:, r]
-    t = t.reshape(m, THREADS // 64, 64)
-    lanes = np.arange(64)
-    for o in (32, 16, 8, 4, 2, 1):
-        t = t + t[:, :, lanes ^ o]
-    s = np.zeros(m)
-    for w in range(THREADS // 64):
-        s = s + t[:, w, 0]
-    return s / float(k)
+    return block_sum(t) / float(k)
 
 
 def mean_navigation(x):

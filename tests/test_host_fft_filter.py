@@ -255,9 +255,18 @@ int main() {
       for (int sx : sizes)
         for (long n : ns) {
           kpdi::FfPlan p = kpdi::ff_plan(d, sy, sx, n);
-          std::printf("%d %d %d %ld %d %zu %ld %d %d %zu %zu %zu\n", d, sy, sx, n, p.path, p.lds_bytes, (long)p.batch,
+          std::printf("%d %d %d %ld %d %zu %ld %d %d %zu %zu %zu", d, sy, sx, n, p.path, p.lds_bytes, (long)p.batch,
                       p.blocks_half, p.blocks_pix, p.workspace_bytes, kpdi::ff_ws_pattern_bytes(d, sy, sx),
                       kpdi::ff_lds_path_bytes(d, sy, sx));
+          // the switches of the tests: unset (false, 0) is the plan above; forced to the workspace; forced and capped
+          kpdi::FfPlan u = kpdi::ff_plan(d, sy, sx, n, false, 0), f = kpdi::ff_plan(d, sy, sx, n, true, 0),
+                       c = kpdi::ff_plan(d, sy, sx, n, true, 3), k = kpdi::ff_plan(d, sy, sx, n, false, 3);
+          const bool same = u.path == p.path && u.lds_bytes == p.lds_bytes && u.batch == p.batch &&
+                            u.workspace_bytes == p.workspace_bytes &&
+                            (p.path != 1 || (u.blocks_half == p.blocks_half && u.blocks_pix == p.blocks_pix));
+          std::printf(" %d %d %zu %ld %d %d %zu %d %ld %zu %d %ld %zu\n", (int)same, f.path, f.lds_bytes, (long)f.batch,
+                      f.blocks_half, f.blocks_pix, f.workspace_bytes, c.path, (long)c.batch, c.workspace_bytes, k.path,
+                      (long)k.batch, k.workspace_bytes);
         }
   std::printf("bad %d\n", kpdi::ff_plan(2, 60, 60, 1).path);
 }
@@ -278,7 +287,8 @@ def test_path_choice(tmp_path):
     assert lines[-2] == "bad -1"
     big = {}
     for line in lines[:-2]:
-        d, sy, sx, n, path, lds, batch, bh, bp, ws, per, lds0 = map(int, line.split())
+        d, sy, sx, n, path, lds, batch, bh, bp, ws, per, lds0 = map(int, line.split()[:12])
+        same, fpath, flds, fbatch, fbh, fbp, fws, cpath, cbatch, cws, kpath, kbatch, kws = map(int, line.split()[12:])
         inter, npix4 = sy * (sx // 2 + 1), (sy * sx + 3) // 4 * 4
         if d == 0:  # the pattern, two complex intermediates, the twiddles
             assert lds0 >= npix4 * 4 + 2 * inter * 8 + (sy + sx) * 8
@@ -296,6 +306,19 @@ def test_path_choice(tmp_path):
             assert bh * threads >= inter > (bh - 1) * threads
             assert bp * threads >= sy * sx > (bp - 1) * threads
             assert batch == n or (batch + 1) * per > ws_cap  # a batch is as large as the cap admits
+        # KPDI_FFT_FILTER_PATH / KPDI_PATTERN_BATCH unset change nothing; forced and capped plans meet the invariants of
+        # the workspace path, and a cap alone leaves a shape of path 0 alone
+        assert same == 1, (d, sy, sx, n)
+        assert fpath == cpath == 1 and flds <= lds_cap, (d, sy, sx)
+        assert 1 <= fbatch <= n and fws == fbatch * per <= ws_cap
+        assert fbh * threads >= inter > (fbh - 1) * threads and fbp * threads >= sy * sx > (fbp - 1) * threads
+        assert fbatch == n or (fbatch + 1) * per > ws_cap
+        assert cbatch == min(fbatch, 3) and cws == cbatch * per
+        if path == 1:
+            assert (fbatch, fws, fbh, fbp, flds) == (batch, ws, bh, bp, lds)
+            assert (kpath, kbatch, kws) == (1, min(batch, 3), min(batch, 3) * per)
+        else:
+            assert (kpath, kbatch, kws) == (0, n, 0)
         big[(d, sy, sx, n)] = (path, batch)
     assert seen == {(0, 0), (0, 1), (1, 0), (1, 1)}
     # the hot shape stays in LDS in both domains; 240 x 240 and 1024 x 1024 take the workspace in the frequency domain

@@ -144,8 +144,16 @@ int main() {
     for (int sx : sizes)
       for (long n : ns) {
         kpdi::IqPlan p = kpdi::iq_plan(sy, sx, n);
-        std::printf("%d %d %ld %d %zu %ld %d %zu %zu %zu\n", sy, sx, n, p.path, p.lds_bytes, (long)p.batch,
+        std::printf("%d %d %ld %d %zu %ld %d %zu %zu %zu", sy, sx, n, p.path, p.lds_bytes, (long)p.batch,
                     p.blocks_per_pattern, p.workspace_bytes, kpdi::iq_ws_pattern_bytes(sy, sx), kpdi::iq_lds_path_bytes(sy, sx));
+        // the switches of the tests: unset (false, 0) is the plan above; forced to the workspace; forced and capped
+        kpdi::IqPlan u = kpdi::iq_plan(sy, sx, n, false, 0), f = kpdi::iq_plan(sy, sx, n, true, 0),
+                     c = kpdi::iq_plan(sy, sx, n, true, 3), k = kpdi::iq_plan(sy, sx, n, false, 3);
+        const bool same = u.path == p.path && u.lds_bytes == p.lds_bytes && u.batch == p.batch &&
+                          u.workspace_bytes == p.workspace_bytes && (p.path != 1 || u.blocks_per_pattern == p.blocks_per_pattern);
+        std::printf(" %d %d %zu %ld %d %zu %d %ld %zu %d %ld %zu\n", (int)same, f.path, f.lds_bytes, (long)f.batch,
+                    f.blocks_per_pattern, f.workspace_bytes, c.path, (long)c.batch, c.workspace_bytes, k.path, (long)k.batch,
+                    k.workspace_bytes);
       }
 }
 """
@@ -164,7 +172,8 @@ def test_path_choice(tmp_path):
     for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n"):
         if not line:
             continue
-        sy, sx, n, path, lds, batch, bpp, ws, per, lds0 = map(int, line.split())
+        sy, sx, n, path, lds, batch, bpp, ws, per, lds0 = map(int, line.split()[:10])
+        same, fpath, flds, fbatch, fbpp, fws, cpath, cbatch, cws, kpath, kbatch, kws = map(int, line.split()[10:])
         inter = sy * (sx // 2 + 1)
         # what the LDS path holds: the intermediate (8 B per complex value), the f32 pattern, the twiddles
         assert lds0 >= inter * 8 + sy * sx * 4 + (sy + sx) * 8
@@ -178,6 +187,19 @@ def test_path_choice(tmp_path):
             assert 1 <= batch <= n and ws == batch * per <= ws_cap
             assert bpp * threads >= inter > (bpp - 1) * threads
             assert batch == n or (batch + 1) * per > ws_cap  # a batch is as large as the cap admits
+        # KPDI_IQ_PATH / KPDI_PATTERN_BATCH unset change nothing; forced and capped plans meet the invariants of the
+        # workspace path, and a cap alone leaves a shape of path 0 alone
+        assert same == 1, (sy, sx, n)
+        assert fpath == cpath == 1 and flds <= lds_cap, (sy, sx)
+        assert 1 <= fbatch <= n and fws == fbatch * per <= ws_cap
+        assert fbpp * threads >= inter > (fbpp - 1) * threads
+        assert fbatch == n or (fbatch + 1) * per > ws_cap
+        assert cbatch == min(fbatch, 3) and cws == cbatch * per
+        if path == 1:
+            assert (fbatch, fws, fbpp, flds) == (batch, ws, bpp, lds)
+            assert (kpath, kbatch, kws) == (1, min(batch, 3), min(batch, 3) * per)
+        else:
+            assert (kpath, kbatch, kws) == (0, n, 0)
     assert seen == {0, 1}
 
 
