@@ -403,6 +403,26 @@ int kpdi_set_navigation_mask(kpdi_ctx *ctx, const uint8_t *nav_mask);
 int kpdi_kinematical_master_pattern(kpdi_ctx *ctx, const double *unit_vectors, const double *theta, const double *intensity,
                                     int64_t m, int half_size, int hemispheres, double *out);
 
+/* ---- cubochoric sampling of the fundamental zone of a rotation group (get_sample_fundamental; Rosca, Morawiec &
+ * De Graef 2014; Singh & De Graef 2016) -----------------------------------------------------------------------------------
+ * Independent of the resident patterns.  The grid has (2 n + 1)^3 points, n = `semi_edge_steps`, over the cube of
+ * semi-edge pi^(2/3) / 2, surface included; a point goes cube -> homochoric ball -> axis-angle -> unit quaternion
+ * (q0 >= 0, qv), all in float64 (csrc/sampling_plan.h).  `faces` (n_faces x 4, host float64) holds one row
+ * (ax, ay, az, tan(omega/4)) per face pair of the zone, a a unit rotation axis of the group and omega the smallest
+ * rotation angle about it; a point is kept iff |qv . a| <= tan(omega/4) q0 + 1e-9 for every row (closed: both faces of
+ * a pair are kept).  n_faces = 0 keeps every point (the group 1).
+ * kpdi_sample_fundamental_count: the number of kept points into `*count`.
+ * kpdi_sample_fundamental_fill: the kept quaternions into `out` (capacity x 4, host float64) in lexicographic grid order,
+ *   x slowest - the host sampler's order, whatever the launch looks like (per-workgroup counts, a device scan, no atomics:
+ *   csrc/sampling.hip) - and their number into `*count`.  After a count call of the same grid and faces on this context
+ *   the points are not counted again.  KPDI_EINVAL with `*count` set when `capacity` is smaller than the kept number.
+ * KPDI_EINVAL before anything runs: NULL, semi_edge_steps outside [1, 2048], n_faces outside [0, 23], capacity < 0.
+ * KPDI_ENOMEM, nothing launched and the context usable, when the per-workgroup counts or the kept quaternions (32 bytes
+ * each) exceed the free device memory. */
+int kpdi_sample_fundamental_count(kpdi_ctx *ctx, int semi_edge_steps, const double *faces, int n_faces, int64_t *count);
+int kpdi_sample_fundamental_fill(kpdi_ctx *ctx, int semi_edge_steps, const double *faces, int n_faces, double *out,
+                                 int64_t capacity, int64_t *count);
+
 /* ---- geometrical simulations: Kikuchi lines and zone axes on the detector (KikuchiPatternSimulator.on_detector,
  * simulations/kikuchi_pattern_simulator.py:217-380; _kikuchi_pattern_features.py; _kikuchi_pattern_simulation.py:468-534) -----
  * Independent of the resident patterns.  All arrays are host memory, float64 unless said otherwise, row vectors.
@@ -963,6 +983,7 @@ typedef struct kpdi_counters {
   double kinematical_ms;         /* the kernel of the last kpdi_kinematical_master_pattern, between two events (profiling on) */
   double geometrical_visibility_ms;   /* the kernels of the last kpdi_geometrical_visibility (profiling on) */
   double geometrical_coordinates_ms;  /* the kernels of the last kpdi_geometrical_coordinates, summed over its passes (profiling on) */
+  double sampling_ms;            /* the kernels of the last kpdi_sample_fundamental_count or _fill: the passes it ran (profiling on) */
 } kpdi_counters;
 /* sizeof(kpdi_counters) as the LIBRARY was built: a binding whose struct differs must refuse to call kpdi_get_counters
  * (the struct has grown between versions; kpdi_version() changes with it) */

@@ -27,6 +27,7 @@ CENTRE_NONE, CENTRE_NAVIGATION, CENTRE_SIGNAL = 0, 1, 2  # kpdi_decomposition_*:
 DECOMPOSITION_MAX_SIDE = 8192  # csrc/decomp_plan.h, DEC_MAX_SIDE
 HEMISPHERE_CODES = {"upper": 0, "lower": 1, "both": 2}  # kpdi_kinematical_master_pattern
 KINEMATICAL_MAX_HALF_SIZE = 4096  # csrc/kinematical_plan.h, KIN_MAX_HALF_SIZE
+SAMPLING_MAX_STEPS, SAMPLING_MAX_FACES = 2048, 23  # csrc/sampling_plan.h, SMP_MAX_STEPS and SMP_MAX_FACES
 GEOMETRICAL_LINES, GEOMETRICAL_ZONE_AXES = 0, 1  # kpdi_geometrical_visibility
 GEOMETRICAL_UPPER, GEOMETRICAL_INSIDE = 1, 2     # bits of its flags
 GEOMETRICAL_PC_DOUBLES = 8  # csrc/geometrical_plan.h, GEO_PC_DOUBLES
@@ -90,6 +91,7 @@ class Counters(C.Structure):
         ("kinematical_ms", C.c_double),
         ("geometrical_visibility_ms", C.c_double),
         ("geometrical_coordinates_ms", C.c_double),
+        ("sampling_ms", C.c_double),
     ]
 
     def as_dict(self):
@@ -157,6 +159,8 @@ SIGNATURES = {
     "kpdi_select_patterns": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i]),
     "kpdi_set_navigation_mask": (_i, [_vp, _vp]),
     "kpdi_kinematical_master_pattern": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
+    "kpdi_sample_fundamental_count": (_i, [_vp, _i, _vp, _i, C.POINTER(_i64)]),
+    "kpdi_sample_fundamental_fill": (_i, [_vp, _i, _vp, _i, _vp, _i64, C.POINTER(_i64)]),
     "kpdi_geometrical_visibility": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "kpdi_geometrical_coordinates": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.c_double,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -656,6 +660,20 @@ class Context:
         out = np.empty((2, size, size) if code == 2 else (size, size), dtype=np.float64)
         check(self._f.kinematical_master_pattern(self._h, _ptr(u), _ptr(th), _ptr(inten), u.shape[0], half_size, code,
                                                  _ptr(out)))
+        return out
+
+    def sample_fundamental(self, semi_edge_steps, faces):
+        """The cubochoric grid of `semi_edge_steps` points per semi-edge, kept where |q_v . a| <= tan(w / 4) q_0 + 1e-9
+        for every row (a_x, a_y, a_z, tan(w / 4)) of `faces` ((f, 4) float64, f = 0 keeps every point): (N, 4) float64
+        unit quaternions, q_0 >= 0, in lexicographic grid order (include/kpdi.h, kpdi_sample_fundamental_count and
+        _fill).  Independent of the resident patterns."""
+        fa = np.ascontiguousarray(faces, dtype=np.float64).reshape(-1, 4)
+        n, nf = int(semi_edge_steps), int(fa.shape[0])
+        count = _i64(0)
+        check(self._f.sample_fundamental_count(self._h, n, _ptr(fa) if nf else None, nf, C.byref(count)))
+        out = np.empty((count.value, 4), dtype=np.float64)
+        check(self._f.sample_fundamental_fill(self._h, n, _ptr(fa) if nf else None, nf, _ptr(out), count.value,
+                                              C.byref(count)))
         return out
 
     @staticmethod
@@ -1723,6 +1741,9 @@ class Group(Context):
 
     def kinematical_master_pattern(self, *args, **kwargs):
         return self.root.kinematical_master_pattern(*args, **kwargs)
+
+    def sample_fundamental(self, *args, **kwargs):
+        return self.root.sample_fundamental(*args, **kwargs)
 
     def geometrical_visibility(self, *args, **kwargs):
         return self.root.geometrical_visibility(*args, **kwargs)

@@ -255,6 +255,15 @@ struct kpdi_ctx {
   // kpdi_geometrical_*: the feature indices, the per-point entries, the visibility flags (partial rows, then the OR) and the
   // outputs of one pass of the coordinate kernel
   kpdi::DevBuf geo_vec, geo_points, geo_flags, geo_out;
+  // kpdi_sample_fundamental_*: the per-workgroup counts and offsets, the kept quaternions; and what the offsets were
+  // counted for (the fill call that follows a count call of the same grid and faces does not count again)
+  kpdi::DevBuf smp_counts, smp_offsets, smp_out;
+  struct SampledZone {
+    bool valid = false;
+    int steps = 0;
+    kpdi::SmpFaces faces{};
+    int64_t kept = 0;
+  } smp_counted;
 
   // dictionary chunk
   kpdi::DevBuf dict_raw, dict_y;

@@ -14,6 +14,7 @@
 #include "decomp_plan.h"
 #include "kinematical_plan.h"
 #include "geometrical_plan.h"
+#include "sampling_plan.h"
 #include "prep_plan.h"
 
 namespace kpdi {
@@ -561,6 +562,18 @@ struct KinLaunch {
 };
 KinPlan kinematical_launch_plan(int64_t m, int half_size, int hemispheres);  // reads the developer switch
 hipError_t launch_kinematical_master_pattern(const KinLaunch &l, hipStream_t s);
+
+// ---- cubochoric sampling of a fundamental zone (sampling.hip) -------------------------------
+struct SmpLaunch {
+  SmpFaces faces;        // the face pairs of the rotation group (smp_in_zone of sampling_plan.h)
+  int steps;             // grid points per semi-edge
+  uint32_t *counts;      // [smp_plan.blocks], device
+  int64_t *offsets;      // [smp_plan.blocks + 1]: exclusive offsets, then the number of kept points; device
+  double *out;           // [kept][4], device (the emit pass only)
+  int64_t kept;          // rows of `out`: what the count pass left in offsets[blocks]
+};
+hipError_t launch_sampling_count(const SmpLaunch &l, hipStream_t s);  // the count pass and the scan
+hipError_t launch_sampling_emit(const SmpLaunch &l, hipStream_t s);
 
 // ---- geometrical simulations (geometrical.hip) ---------------------------------------------
 struct GeoVisLaunch {

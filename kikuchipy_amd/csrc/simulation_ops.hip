@@ -1,6 +1,7 @@
 // simulation_ops.hip - host side of libkpdi.so, the simulations that need no resident patterns: the kinematical master
 // pattern (kinematical.hip) and the geometrical simulations (geometrical.hip), their tables formed on the host
-// (kinematical_plan.h, geometrical_plan.h).
+// (kinematical_plan.h, geometrical_plan.h), and the orientation sampling that feeds a dictionary (sampling.hip,
+// sampling_plan.h).
 #include "context.h"
 
 using namespace kpdi;
@@ -219,6 +220,138 @@ int kpdi_geometrical_coordinates(kpdi_ctx *c, const double *hkl, int64_t m, cons
     return fail(KPDI_EHIP, "geometrical coordinates kernel: %s (%lld lines, %lld zone axes, %lld map points)", hipGetErrorString(e),
                 (long long)m, (long long)z, (long long)n_points);
   }
+  return rc;
+}
+
+// ---- cubochoric sampling of a fundamental zone (sampling.hip) ------------------------------------------------------------
+
+// device memory the sampler may still take.  KPDI_SAMPLING_FREE_BYTES (tests: the refusal at a small grid) replaces the query
+static int sampling_free_bytes(size_t *free_bytes) {
+  if (const char *e = getenv("KPDI_SAMPLING_FREE_BYTES")) {
+    *free_bytes = (size_t)strtoull(e, nullptr, 10);
+    return KPDI_OK;
+  }
+  size_t total_bytes = 0;
+  HIPCHK(hipMemGetInfo(free_bytes, &total_bytes));
+  return KPDI_OK;
+}
+
+// what `buf` has to grow by to hold `bytes` (DevBuf::reserve frees before it allocates)
+static size_t sampling_growth(const kpdi::DevBuf &buf, size_t bytes) { return bytes > buf.cap ? bytes - buf.cap : 0; }
+
+static int sampling_inputs_refused(kpdi_ctx *c, int steps, const double *faces, int n_faces) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (steps < 1 || steps > kpdi::SMP_MAX_STEPS)
+    return fail(KPDI_EINVAL, "semi_edge_steps %d: between 1 and %d", steps, kpdi::SMP_MAX_STEPS);
+  if (n_faces < 0 || n_faces > kpdi::SMP_MAX_FACES)
+    return fail(KPDI_EINVAL, "%d faces: between 0 and %d", n_faces, kpdi::SMP_MAX_FACES);
+  if (n_faces > 0 && !faces) return fail(KPDI_EINVAL, "faces is NULL");
+  return KPDI_OK;
+}
+
+static kpdi::SmpFaces sampling_faces(const double *faces, int n_faces) {
+  kpdi::SmpFaces f{};
+  f.n = n_faces;
+  if (n_faces > 0) memcpy(f.f, faces, (size_t)n_faces * kpdi::SMP_FACE_DOUBLES * sizeof(double));
+  return f;
+}
+
+static bool sampling_counted(const kpdi_ctx *c, int steps, const kpdi::SmpFaces &f) {
+  const auto &s = c->smp_counted;
+  return s.valid && s.steps == steps && s.faces.n == f.n && memcmp(s.faces.f, f.f, sizeof(f.f)) == 0;
+}
+
+// the count pass and the scan: c->smp_offsets and c->smp_counted describe (steps, f) afterwards
+static int sampling_count(kpdi_ctx *c, int steps, const kpdi::SmpFaces &f, double *kernel_ms) {
+  const kpdi::SmpPlan plan = kpdi::smp_plan(steps);
+  c->smp_counted.valid = false;
+  size_t free_bytes = 0;
+  int rc = sampling_free_bytes(&free_bytes);
+  if (rc) return rc;
+  const size_t need = sampling_growth(c->smp_counts, plan.count_bytes) + sampling_growth(c->smp_offsets, plan.offset_bytes);
+  if (need > free_bytes)
+    return fail(KPDI_ENOMEM, "sampling with semi_edge_steps %d: the counts of %lld workgroups need %zu bytes more, %zu bytes of "
+                "device memory are free", steps, (long long)plan.blocks, need, free_bytes);
+  HIPCHK(c->smp_counts.reserve(plan.count_bytes));
+  HIPCHK(c->smp_offsets.reserve(plan.offset_bytes));
+  kpdi::SmpLaunch l{};
+  l.faces = f;
+  l.steps = steps;
+  l.counts = c->smp_counts.as<uint32_t>();
+  l.offsets = c->smp_offsets.as<int64_t>();
+  EventPair timer(c, c->profiling != 0);
+  HIPCHK(timer.begin());
+  const hipError_t e = kpdi::launch_sampling_count(l, c->stream);
+  (void)timer.end();
+  if (e != hipSuccess) return fail(KPDI_EHIP, "sampling count kernels: %s (semi_edge_steps %d)", hipGetErrorString(e), steps);
+  int64_t kept = 0;
+  rc = results_to_host(c, &kept, l.offsets + plan.blocks, sizeof(kept));
+  if (rc) return rc;
+  float ms = 0.f;
+  if (timer.elapsed(&ms) == hipSuccess) *kernel_ms += ms;
+  c->smp_counted.valid = true;
+  c->smp_counted.steps = steps;
+  c->smp_counted.faces = f;
+  c->smp_counted.kept = kept;
+  return KPDI_OK;
+}
+
+int kpdi_sample_fundamental_count(kpdi_ctx *c, int semi_edge_steps, const double *faces, int n_faces, int64_t *count) {
+  int rc = sampling_inputs_refused(c, semi_edge_steps, faces, n_faces);
+  if (rc) return rc;
+  if (!count) return fail(KPDI_EINVAL, "count is NULL");
+  rc = use_device(c);
+  if (rc) return rc;
+  double kernel_ms = 0.0;
+  rc = sampling_count(c, semi_edge_steps, sampling_faces(faces, n_faces), &kernel_ms);
+  if (rc) return rc;
+  if (c->profiling) c->cnt.sampling_ms = kernel_ms;
+  *count = c->smp_counted.kept;
+  return KPDI_OK;
+}
+
+int kpdi_sample_fundamental_fill(kpdi_ctx *c, int semi_edge_steps, const double *faces, int n_faces, double *out,
+                                 int64_t capacity, int64_t *count) {
+  int rc = sampling_inputs_refused(c, semi_edge_steps, faces, n_faces);
+  if (rc) return rc;
+  if (!count) return fail(KPDI_EINVAL, "count is NULL");
+  if (capacity < 0 || (capacity > 0 && !out)) return fail(KPDI_EINVAL, "out is NULL or capacity %lld is negative", (long long)capacity);
+  rc = use_device(c);
+  if (rc) return rc;
+  const kpdi::SmpFaces f = sampling_faces(faces, n_faces);
+  double kernel_ms = 0.0;
+  if (!sampling_counted(c, semi_edge_steps, f)) {
+    rc = sampling_count(c, semi_edge_steps, f, &kernel_ms);
+    if (rc) return rc;
+  }
+  const int64_t kept = c->smp_counted.kept;
+  *count = kept;
+  if (kept > capacity)
+    return fail(KPDI_EINVAL, "sampling with semi_edge_steps %d keeps %lld orientations, out holds %lld", semi_edge_steps,
+                (long long)kept, (long long)capacity);
+  if (kept == 0) return KPDI_OK;
+  const size_t out_bytes = (size_t)kept * 4 * sizeof(double);
+  size_t free_bytes = 0;
+  rc = sampling_free_bytes(&free_bytes);
+  if (rc) return rc;
+  if (sampling_growth(c->smp_out, out_bytes) > free_bytes)
+    return fail(KPDI_ENOMEM, "sampling with semi_edge_steps %d: %lld orientations need %zu bytes, %zu bytes of device memory are "
+                "free", semi_edge_steps, (long long)kept, out_bytes, free_bytes);
+  HIPCHK(c->smp_out.reserve(out_bytes));
+  kpdi::SmpLaunch l{};
+  l.faces = f;
+  l.steps = semi_edge_steps;
+  l.counts = c->smp_counts.as<uint32_t>();
+  l.offsets = c->smp_offsets.as<int64_t>();
+  l.out = c->smp_out.as<double>();
+  l.kept = kept;
+  hipError_t e = hipSuccess;
+  double emit_ms = 0.0;
+  rc = launch_to_host(c, [&] { return kpdi::launch_sampling_emit(l, c->stream); }, out, c->smp_out.p, out_bytes, &emit_ms, &e);
+  if (e != hipSuccess)
+    return fail(KPDI_EHIP, "sampling emit kernel: %s (semi_edge_steps %d, %lld orientations)", hipGetErrorString(e), semi_edge_steps,
+                (long long)kept);
+  if (rc == KPDI_OK && c->profiling) c->cnt.sampling_ms = kernel_ms + emit_ms;
   return rc;
 }
 
