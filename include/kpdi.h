@@ -620,9 +620,9 @@ int kpdi_refine_solve(kpdi_ctx *ctx, int mode, int64_t n_patterns, int n_starts,
                       const double *x0, const double *fixed, const double *lower,
                       const double *upper, double xatol, double fatol, int maxiter, int maxfev,
                       double *results);
-/* The optimiser alone on an analytic f64 objective (kind 0: Rosenbrock, 1: weighted bowl),
- * nvar <= 6: lets a test compare the device's simplex path with SciPy's bit for bit.
- * result: fun, nfev, nit, x[0..nvar). */
+/* The optimiser (csrc/nelder_mead.h) alone on an analytic f64 objective (kinds 0..4 of
+ * kpdi_powell_selftest), nvar <= 6: lets a test compare the device's simplex path with
+ * SciPy's bit for bit.  result: fun, nfev, nit, x[0..nvar). */
 int kpdi_nelder_mead_selftest(kpdi_ctx *ctx, int kind, int nvar, const double *x0,
                               const double *lower, const double *upper, double xatol,
                               double fatol, int maxiter, int maxfev, double *result);

@@ -526,6 +526,7 @@ int kpdi_nelder_mead_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0,
                               const double *upper, double xatol, double fatol, int maxiter, int maxfev,
                               double *result) {
   if (!c || !x0 || !result) return fail(KPDI_EINVAL, "NULL argument");
+  if (kind < 0 || kind > 4) return fail(KPDI_EINVAL, "kind must be within 0..4");
   if (nvar < 1 || nvar > 6) return fail(KPDI_EINVAL, "nvar must be within 1..6");
   if ((lower == nullptr) != (upper == nullptr)) return fail(KPDI_EINVAL, "give both bounds or neither");
   int rc = use_device(c);

@@ -6,26 +6,22 @@
 //   similarity_metrics/_normalized_cross_correlation.py:200-225   NCC of a centred pattern
 //   _utils/numba.py:43-57 (rotation_from_euler), _utils/_gnonomic_bounds.py:25-65,
 //   signals/util/_master_pattern.py:133-204 (direction cosines for one PC)
-// The optimiser the reference calls is scipy.optimize.minimize(method="Nelder-Mead"), a
-// third-party dependency (pyproject: scipy >= 1.7); `NelderMead` below restates SciPy
-// 1.15.3's `_minimize_neldermead` (scipy/optimize/_optimize.py) operation for operation in
-// f64 without fused multiply-add, so that on the same objective values it walks the same
-// simplex path (kpdi_nelder_mead_selftest pins that bit for bit against SciPy).  The second
-// device optimiser is scipy.optimize.minimize(method="Powell"), restated in powell.h and run
-// by `refine_solve_powell_kernel` (kpdi_powell_selftest pins it the same way); the third is the simplex search
-// NLopt offers as LN_NELDERMEAD, restated in nlopt_simplex.h from the text of DESIGN.md section 21 and run by
-// `refine_solve_nlopt_kernel` (kpdi_nlopt_simplex_selftest pins kernel against header; NLopt itself is not compared
-// with); the fourth is scipy.optimize.differential_evolution with strategy="best1bin" over NumPy's legacy RandomState,
-// restated in differential_evolution.h and run by `refine_solve_de_kernel` (kpdi_de_selftest and kpdi_mt19937_selftest
-// pin it against SciPy and NumPy).  Every other optimiser stays on the host and calls `refine_objective_kernel`.
+// The optimisers are plain C++17 headers, each restating its original operation for operation in f64 without fused
+// multiply-add and each pinned on the analytic objectives of analytic_objectives.h by a self-test kernel below:
+//   nelder_mead.h             scipy.optimize.minimize(method="Nelder-Mead"), what the reference calls by default
+//   powell.h                  scipy.optimize.minimize(method="Powell")
+//   nlopt_simplex.h           the search NLopt offers as LN_NELDERMEAD, from the text of DESIGN.md section 21
+//   differential_evolution.h  scipy.optimize.differential_evolution, strategy="best1bin", NumPy's legacy RandomState
+// Every other optimiser stays on the host and calls `refine_objective_kernel`.
 //
-// One workgroup per (experimental pattern, start) runs the WHOLE optimisation: thread 0
-// owns the simplex (LDS) and decides the next point; all 256 threads evaluate the
-// objective there (each pixel: direction cosine for the current PC -> rotate -> Lambert ->
-// one 16-byte master-pattern gather -> float32 value; three f64 block sums give the NCC).
-// No host round trip and no kernel launch per evaluation: a refinement of M patterns is
-// one launch.  The objective is f64-VALU-bound like project.hip; the centred pattern
-// (k x 4 B) and the master pattern stay in L2.
+// One workgroup per (experimental pattern, start) runs the WHOLE optimisation.  In
+// `refine_solve_kernel` thread 0 owns the simplex (LDS) and decides the next point; in the
+// other three solve kernels every thread runs the optimiser on the same values.  All 256
+// threads evaluate the objective (each pixel: direction cosine for the current PC -> rotate
+// -> Lambert -> one 16-byte master-pattern gather -> float32 value; three f64 block sums give
+// the NCC).  No host round trip and no kernel launch per evaluation: a refinement of M
+// patterns is one launch.  The objective is f64-VALU-bound like project.hip; the centred
+// pattern (k x 4 B) and the master pattern stay in L2.
 #include "kernels.h"
 #include "../../include/kpdi.h"
 
@@ -35,7 +31,9 @@
 
 #include <climits>
 
+#include "analytic_objectives.h"
 #include "differential_evolution.h"
+#include "nelder_mead.h"
 #include "nlopt_simplex.h"
 #include "powell.h"
 
@@ -200,193 +198,22 @@ __device__ inline void unpack_variables(int mode, const double *x, const double 
   }
 }
 
-// ---- SciPy's Nelder-Mead as a state machine: `begin` / `feed(f)` are called by ONE thread;
-// after each call either `done` is set or `xeval` holds the next point to evaluate.
-struct NelderMead {
-  enum { S_INIT, S_REFLECT, S_EXPAND, S_CONTRACT_OUT, S_CONTRACT_IN, S_SHRINK, S_DONE };
-  int n, state, j, fcalls, iterations, maxiter, maxfun, bounded;
-  double xatol, fatol;
-  double sim[NV_MAX + 1][NV_MAX], fsim[NV_MAX + 1];
-  double lb[NV_MAX], ub[NV_MAX];
-  double xbar[NV_MAX], xr[NV_MAX], xt[NV_MAX], fxr;
-  double xeval[NV_MAX];
-
-  __device__ void clip(double *x) const {
-    if (!bounded) return;
-    for (int i = 0; i < n; ++i) x[i] = fmin(fmax(x[i], lb[i]), ub[i]);  // np.clip
-  }
-  // the evaluation-count guard of _wrap_scalar_function_maxfun_validation: false = "raised"
-  __device__ bool request(const double *x) {
-    if (fcalls >= maxfun) return false;
-    ++fcalls;
-    for (int i = 0; i < n; ++i) xeval[i] = x[i];
-    return true;
-  }
-  // np.argsort on <= 7 values = insertion sort: stable, NaN last
-  __device__ void sort() {
-    for (int a = 1; a <= n; ++a) {
-      const double f = fsim[a];
-      double x[NV_MAX];
-      for (int i = 0; i < n; ++i) x[i] = sim[a][i];
-      int b = a - 1;
-      while (b >= 0 && (f < fsim[b] || (fsim[b] != fsim[b] && f == f))) {
-        fsim[b + 1] = fsim[b];
-        for (int i = 0; i < n; ++i) sim[b + 1][i] = sim[b][i];
-        --b;
-      }
-      fsim[b + 1] = f;
-      for (int i = 0; i < n; ++i) sim[b + 1][i] = x[i];
-    }
-  }
-  __device__ void finish() { state = S_DONE; }
-  __device__ void raised() {  // `except _MaxFuncCallError: pass` + `finally:` sort
-    sort();
-    loop_top();
-  }
-  __device__ void end_iteration() {
-    ++iterations;
-    sort();
-    loop_top();
-  }
-  __device__ void accept(const double *x, double f) {
-    for (int i = 0; i < n; ++i) sim[n][i] = x[i];
-    fsim[n] = f;
-  }
-  __device__ void loop_top() {
-    if (!(fcalls < maxfun && iterations < maxiter)) return finish();
-    double dx = 0.0, df = 0.0;
-    for (int a = 1; a <= n; ++a) {
-      for (int i = 0; i < n; ++i) dx = fmax(dx, fabs(sim[a][i] - sim[0][i]));
-      df = fmax(df, fabs(fsim[0] - fsim[a]));
-    }
-    if (dx <= xatol && df <= fatol) return finish();
-    for (int i = 0; i < n; ++i) {
-      double s = sim[0][i];
-      for (int a = 1; a < n; ++a) s += sim[a][i];  // np.add.reduce(sim[:-1], 0)
-      xbar[i] = s / (double)n;
-      xr[i] = 2.0 * xbar[i] - 1.0 * sim[n][i];  // (1 + rho) * xbar - rho * sim[-1]
-    }
-    clip(xr);
-    state = S_REFLECT;
-    if (!request(xr)) raised();
-  }
-  __device__ void shrink_step() {
-    for (int i = 0; i < n; ++i) sim[j][i] = sim[0][i] + 0.5 * (sim[j][i] - sim[0][i]);
-    clip(sim[j]);
-    state = S_SHRINK;
-    if (!request(sim[j])) raised();
-  }
-  __device__ void begin(int nvar, const double *x0, const double *lower, const double *upper, double xa, double fa,
-                        int max_iter, int max_fun) {
-    n = nvar;
-    xatol = xa;
-    fatol = fa;
-    maxiter = max_iter;
-    maxfun = max_fun;
-    bounded = lower != nullptr;
-    double x[NV_MAX];
-    for (int i = 0; i < n; ++i) {
-      x[i] = x0[i];
-      if (bounded) {
-        lb[i] = lower[i];
-        ub[i] = upper[i];
-      }
-    }
-    clip(x);
-    for (int i = 0; i < n; ++i) sim[0][i] = x[i];
-    for (int k = 0; k < n; ++k) {
-      for (int i = 0; i < n; ++i) sim[k + 1][i] = x[i];
-      sim[k + 1][k] = x[k] != 0.0 ? (1.0 + 0.05) * x[k] : 0.00025;
-    }
-    if (bounded)  // reflect vertices above the upper bound into the interior, then clip
-      for (int a = 0; a <= n; ++a) {
-        for (int i = 0; i < n; ++i)
-          if (sim[a][i] > ub[i]) sim[a][i] = 2.0 * ub[i] - sim[a][i];
-        clip(sim[a]);
-      }
-    for (int a = 0; a <= n; ++a) fsim[a] = INFINITY;
-    fcalls = 0;
-    iterations = 1;
-    state = S_INIT;
-    j = 0;
-    if (!request(sim[0])) {
-      sort();
-      loop_top();
-    }
-  }
-  __device__ void feed(double f) {
-    switch (state) {
-      case S_INIT:
-        fsim[j] = f;
-        ++j;
-        if (j <= n && request(sim[j])) return;
-        sort();
-        loop_top();
-        return;
-      case S_REFLECT:
-        fxr = f;
-        if (fxr < fsim[0]) {
-          for (int i = 0; i < n; ++i) xt[i] = 3.0 * xbar[i] - 2.0 * sim[n][i];  // (1 + rho chi) xbar - rho chi sim[-1]
-          clip(xt);
-          state = S_EXPAND;
-          if (!request(xt)) raised();
-        } else if (fxr < fsim[n - 1]) {
-          accept(xr, fxr);
-          end_iteration();
-        } else if (fxr < fsim[n]) {
-          for (int i = 0; i < n; ++i) xt[i] = 1.5 * xbar[i] - 0.5 * sim[n][i];  // (1 + psi rho) xbar - psi rho sim[-1]
-          clip(xt);
-          state = S_CONTRACT_OUT;
-          if (!request(xt)) raised();
-        } else {
-          for (int i = 0; i < n; ++i) xt[i] = 0.5 * xbar[i] + 0.5 * sim[n][i];  // (1 - psi) xbar + psi sim[-1]
-          clip(xt);
-          state = S_CONTRACT_IN;
-          if (!request(xt)) raised();
-        }
-        return;
-      case S_EXPAND:
-        if (f < fxr) accept(xt, f); else accept(xr, fxr);
-        end_iteration();
-        return;
-      case S_CONTRACT_OUT:
-        if (f <= fxr) {
-          accept(xt, f);
-          end_iteration();
-        } else {
-          j = 1;
-          shrink_step();
-        }
-        return;
-      case S_CONTRACT_IN:
-        if (f < fsim[n]) {
-          accept(xt, f);
-          end_iteration();
-        } else {
-          j = 1;
-          shrink_step();
-        }
-        return;
-      case S_SHRINK:
-        fsim[j] = f;
-        ++j;
-        if (j <= n) shrink_step(); else end_iteration();
-        return;
-      default:
-        return;
-    }
-  }
-  // OptimizeResult: fun = np.min(fsim), x = sim[0]
-  __device__ double fun() const {
-    double m = fsim[0];
-    for (int a = 1; a <= n; ++a) m = fsim[a] < m ? fsim[a] : m;
-    return m;
-  }
-};
-
-// result row: fun, nfev, nit, x[0..nvar)
+// result row of job `job`: fun, nfev, a third number (nit, or the status of the LN_NELDERMEAD search), x[0..nvar).
+// Called by one thread.
 constexpr int RESULT_STRIDE = REFINE_RESULT_STRIDE;
 static_assert(RESULT_STRIDE == 3 + NV_MAX, "result row = fun, nfev, nit + control variables");
+
+__device__ __forceinline__ void write_result(double *results, int64_t job, double fun, double nfev, double third,
+                                             const double *x, int nvar) {
+  double *o = results + job * RESULT_STRIDE;
+  o[0] = fun;
+  o[1] = nfev;
+  o[2] = third;
+  for (int i = 0; i < nvar; ++i) o[3 + i] = x[i];
+}
+
+// ---- SciPy's Nelder-Mead (nelder_mead.h) on the device: a state machine that thread 0 steps
+using NelderMeadState = NelderMead<NV_MAX>;
 
 __global__ __launch_bounds__(REF_THREADS) void refine_solve_kernel(int mode, int nvar, int nfixed, int n_starts,
                                                                     const double *x0, const double *fixed,
@@ -394,7 +221,7 @@ __global__ __launch_bounds__(REF_THREADS) void refine_solve_kernel(int mode, int
                                                                     RefineGeom g, const float *patterns,
                                                                     const double *sqnorm, double xatol, double fatol,
                                                                     int maxiter, int maxfun, double *results) {
-  __shared__ NelderMead nm;
+  __shared__ NelderMeadState nm;
   __shared__ double red[3 * REF_THREADS / 64];
   const int64_t job = blockIdx.x;  // (pattern, start)
   const int64_t pat_id = job / n_starts;
@@ -405,7 +232,7 @@ __global__ __launch_bounds__(REF_THREADS) void refine_solve_kernel(int mode, int
     nm.begin(nvar, x0 + job * nvar, lower ? lower + job * nvar : nullptr, upper ? upper + job * nvar : nullptr, xatol,
              fatol, maxiter, maxfun);
   __syncthreads();
-  while (nm.state != NelderMead::S_DONE) {
+  while (nm.state != NelderMeadState::S_DONE) {
     double q[4], pc[3];
     unpack_variables(mode, nm.xeval, fx, q, pc);
     const double f = refine_objective(q, pc, g, pat, sqn, red);
@@ -413,13 +240,7 @@ __global__ __launch_bounds__(REF_THREADS) void refine_solve_kernel(int mode, int
     if (threadIdx.x == 0) nm.feed(f);
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    double *o = results + job * RESULT_STRIDE;
-    o[0] = nm.fun();
-    o[1] = (double)nm.fcalls;
-    o[2] = (double)nm.iterations;
-    for (int i = 0; i < nvar; ++i) o[3 + i] = nm.sim[0][i];
-  }
+  if (threadIdx.x == 0) write_result(results, job, nm.fun(), (double)nm.fcalls, (double)nm.iterations, nm.sim[0], nvar);
 }
 
 // batched objective: one workgroup per evaluation
@@ -436,42 +257,25 @@ __global__ __launch_bounds__(REF_THREADS) void refine_objective_kernel(int mode,
   if (threadIdx.x == 0) out[e] = f;
 }
 
-// ---- the optimiser alone on analytic f64 objectives (pins NelderMead against SciPy)
-__device__ inline double selftest_objective(int kind, int n, const double *x) {
-  double acc = 0.0;
-  if (kind == 0) {  // Rosenbrock: sum(100 (x[i+1] - x[i]^2)^2 + (1 - x[i])^2)
-    for (int i = 0; i + 1 < n; ++i) {
-      const double d = x[i + 1] - x[i] * x[i], e = 1.0 - x[i];
-      const double t = 100.0 * (d * d) + e * e;
-      acc = i == 0 ? t : acc + t;
-    }
-  } else {  // weighted bowl: sum((i + 1) (x[i] - 0.3 (i + 1))^2)
-    for (int i = 0; i < n; ++i) {
-      const double d = x[i] - 0.3 * (double)(i + 1);
-      const double t = (double)(i + 1) * (d * d);
-      acc = i == 0 ? t : acc + t;
-    }
-  }
-  return acc;
-}
-
+// ---- the self-tests: one optimiser alone, in one thread, on an analytic f64 objective (analytic_objectives.h); the
+// host and GPU tests compare the row with SciPy's (with the restatement's for LN_NELDERMEAD) bit for bit.
+// nelder_mead.h, kinds 0..4.  result: fun, nfev, nit, x[0..nvar)
 __global__ void nelder_mead_selftest_kernel(int kind, int nvar, const double *x0, const double *lower, const double *upper,
                                             double xatol, double fatol, int maxiter, int maxfun, double *result) {
-  __shared__ NelderMead nm;
+  __shared__ NelderMeadState nm;
   if (threadIdx.x != 0) return;
+  const AnalyticObjective ev{kind, nvar};
   nm.begin(nvar, x0, lower, upper, xatol, fatol, maxiter, maxfun);
-  while (nm.state != NelderMead::S_DONE) nm.feed(selftest_objective(kind, nvar, nm.xeval));
-  result[0] = nm.fun();
-  result[1] = (double)nm.fcalls;
-  result[2] = (double)nm.iterations;
-  for (int i = 0; i < nvar; ++i) result[3 + i] = nm.sim[0][i];
+  while (nm.state != NelderMeadState::S_DONE) nm.feed(ev.eval(nm.xeval));
+  write_result(result, 0, nm.fun(), (double)nm.fcalls, (double)nm.iterations, nm.sim[0], nvar);
 }
 
-// ---- SciPy's Powell (powell.h) on the device.  `refine_objective` returns the same bits in every thread and has
+// ---- the other three solvers on the device.  `refine_objective` returns the same bits in every thread and has
 // barriers inside, so the optimiser is not handed to one thread: EVERY thread runs it, as straight-line code on those
 // uniform values, with its state in private memory.  Control flow is then uniform by construction - all 256 threads
 // ask for the same evaluations in the same order and meet at the same barriers - and nothing is shared but `red`.
-struct RefinePowellEval {
+// RefineEval is the `E` of the three headers: the objective of one job.
+struct RefineEval {
   int mode, nvar;
   const double *fx;
   const RefineGeom *g;
@@ -481,6 +285,26 @@ struct RefinePowellEval {
   double *trace;  // rows (x[0..nvar), f) of this job's evaluations, or nullptr
   int trace_capacity;
   long long n_eval;
+  // the job of this workgroup; its evaluations are traced when it is `trace_job` (and `trace` is given)
+  __device__ __forceinline__ static RefineEval of_job(int mode, int nvar, int nfixed, int n_starts, const double *fixed,
+                                                      const RefineGeom &g, const float *patterns, const double *sqnorm,
+                                                      double *red, long long trace_job, double *trace,
+                                                      int trace_capacity) {
+    const int64_t job = blockIdx.x;  // (pattern, start)
+    const int64_t pat_id = job / n_starts;
+    RefineEval ev;
+    ev.mode = mode;
+    ev.nvar = nvar;
+    ev.fx = fixed + job * nfixed;
+    ev.g = &g;
+    ev.pat = patterns + pat_id * g.k;
+    ev.sqn = sqnorm[pat_id];
+    ev.red = red;
+    ev.trace = job == trace_job ? trace : nullptr;
+    ev.trace_capacity = trace_capacity;
+    ev.n_eval = 0;
+    return ev;
+  }
   __device__ double eval(const double *x) {
     double q[4], pc[3];
     unpack_variables(mode, x, fx, q, pc);
@@ -495,59 +319,39 @@ struct RefinePowellEval {
   }
 };
 
+// ---- SciPy's Powell (powell.h)
 __global__ __launch_bounds__(REF_THREADS, 4) void refine_solve_powell_kernel(
     int mode, int nvar, int nfixed, int n_starts, const double *x0, const double *fixed, const double *lower,
     const double *upper, RefineGeom g, const float *patterns, const double *sqnorm, double xtol, double ftol, int maxiter,
     int maxfev, double *results, long long trace_job, double *trace, int trace_capacity) {
   __shared__ double red[3 * REF_THREADS / 64];
   const int64_t job = blockIdx.x;  // (pattern, start)
-  const int64_t pat_id = job / n_starts;
-  RefinePowellEval ev;
-  ev.mode = mode;
-  ev.nvar = nvar;
-  ev.fx = fixed + job * nfixed;
-  ev.g = &g;
-  ev.pat = patterns + pat_id * g.k;
-  ev.sqn = sqnorm[pat_id];
-  ev.red = red;
-  ev.trace = job == trace_job ? trace : nullptr;
-  ev.trace_capacity = trace_capacity;
-  ev.n_eval = 0;
-  Powell<NV_MAX, RefinePowellEval> pw(ev);
+  RefineEval ev = RefineEval::of_job(mode, nvar, nfixed, n_starts, fixed, g, patterns, sqnorm, red, trace_job, trace,
+                                     trace_capacity);
+  Powell<NV_MAX, RefineEval> pw(ev);
   pw.minimize(nvar, x0 + job * nvar, lower ? lower + job * nvar : nullptr, upper ? upper + job * nvar : nullptr, xtol,
               ftol, maxiter, maxfev);
-  if (threadIdx.x == 0) {
-    double *o = results + job * RESULT_STRIDE;
-    o[0] = pw.fval;
-    o[1] = (double)pw.fcalls;
-    o[2] = (double)pw.iter;
-    for (int i = 0; i < nvar; ++i) o[3 + i] = pw.x[i];
-  }
+  if (threadIdx.x == 0) write_result(results, job, pw.fval, (double)pw.fcalls, (double)pw.iter, pw.x, nvar);
 }
 
-// ---- powell.h alone on analytic f64 objectives: kinds 0 and 1 of `selftest_objective`, 2 = kind 1 rounded to float32
-// and back (plateaus and ties, like the real objective's float32 noise), 3 = kind 1 but NaN where x[0] > 1.9, 4 = NaN
-struct PowellSelftestEval {
-  int kind, n;
-  __device__ double eval(const double *x) const {
-    if (kind == 4 || (kind == 3 && x[0] > 1.9)) return __builtin_nan("");
-    const double f = selftest_objective(kind == 0 ? 0 : 1, n, x);
-    return kind == 2 ? (double)(float)f : f;
-  }
-};
+// self-test row of powell.h and differential_evolution.h: fun, nfev, nit, a flag (status / success), x[0..nvar)
+__device__ __forceinline__ void write_selftest_result(double *result, double fun, double nfev, double nit, double flag,
+                                                      const double *x, int nvar) {
+  result[0] = fun;
+  result[1] = nfev;
+  result[2] = nit;
+  result[3] = flag;
+  for (int i = 0; i < nvar; ++i) result[4 + i] = x[i];
+}
 
-// result: fun, nfev, nit, status, x[0..nvar)
+// powell.h alone, kinds 0..4
 __global__ void powell_selftest_kernel(int kind, int nvar, const double *x0, const double *lower, const double *upper,
                                        double xtol, double ftol, int maxiter, int maxfev, double *result) {
   if (threadIdx.x != 0) return;
-  PowellSelftestEval ev{kind, nvar};
-  Powell<NV_MAX, PowellSelftestEval> pw(ev);
+  AnalyticObjective ev{kind, nvar};
+  Powell<NV_MAX, AnalyticObjective> pw(ev);
   pw.minimize(nvar, x0, lower, upper, xtol, ftol, maxiter, maxfev);
-  result[0] = pw.fval;
-  result[1] = (double)pw.fcalls;
-  result[2] = (double)pw.iter;
-  result[3] = (double)pw.status;
-  for (int i = 0; i < nvar; ++i) result[4 + i] = pw.x[i];
+  write_selftest_result(result, pw.fval, (double)pw.fcalls, (double)pw.iter, (double)pw.status, pw.x, nvar);
 }
 
 // ---- the LN_NELDERMEAD search (nlopt_simplex.h) on the device, run like Powell: every thread walks the same simplex on
@@ -559,57 +363,21 @@ __global__ __launch_bounds__(REF_THREADS, 4) void refine_solve_nlopt_kernel(
     int maxeval, double *results) {
   __shared__ double red[3 * REF_THREADS / 64];
   const int64_t job = blockIdx.x;  // (pattern, start)
-  const int64_t pat_id = job / n_starts;
-  RefinePowellEval ev;
-  ev.mode = mode;
-  ev.nvar = nvar;
-  ev.fx = fixed + job * nfixed;
-  ev.g = &g;
-  ev.pat = patterns + pat_id * g.k;
-  ev.sqn = sqnorm[pat_id];
-  ev.red = red;
-  ev.trace = nullptr;
-  ev.trace_capacity = 0;
-  ev.n_eval = 0;
-  NloptSimplex<NV_MAX, RefinePowellEval> ns(ev);
+  RefineEval ev = RefineEval::of_job(mode, nvar, nfixed, n_starts, fixed, g, patterns, sqnorm, red, -1, nullptr, 0);
+  NloptSimplex<NV_MAX, RefineEval> ns(ev);
   ns.optimize(nvar, x0 + job * nvar, lower ? lower + job * nvar : nullptr, upper ? upper + job * nvar : nullptr,
               xstep.given ? xstep.v : nullptr, ftol_rel, maxeval);
-  if (threadIdx.x == 0) {
-    double *o = results + job * RESULT_STRIDE;
-    o[0] = ns.minf;
-    o[1] = (double)ns.nevals;
-    o[2] = (double)ns.status;
-    for (int i = 0; i < nvar; ++i) o[3 + i] = ns.x[i];
-  }
+  if (threadIdx.x == 0) write_result(results, job, ns.minf, (double)ns.nevals, (double)ns.status, ns.x, nvar);
 }
 
-// ---- nlopt_simplex.h alone on analytic f64 objectives: kinds 0..4 of `PowellSelftestEval`, 5 = a sum of concave arms,
-// sum((i + 1) |d| / (1 + |d|)) with d = x[i] - 0.3 (i + 1), on which contractions fail and the simplex shrinks
-struct NloptSelftestEval {
-  int kind, n;
-  __device__ double eval(const double *x) const {
-    if (kind != 5) return PowellSelftestEval{kind, n}.eval(x);
-    double acc = 0.0;
-    for (int i = 0; i < n; ++i) {
-      const double d = fabs(x[i] - 0.3 * (double)(i + 1));
-      const double t = (double)(i + 1) * d / (1.0 + d);
-      acc = i == 0 ? t : acc + t;
-    }
-    return acc;
-  }
-};
-
-// result: minf, nevals, status, x[0..nvar)
+// nlopt_simplex.h alone, kinds 0..4 and 5 = ANALYTIC_ARMS.  result: minf, nevals, status, x[0..nvar)
 __global__ void nlopt_simplex_selftest_kernel(int kind, int nvar, const double *x0, const double *lower, const double *upper,
                                               const double *xstep, double ftol_rel, int maxeval, double *result) {
   if (threadIdx.x != 0) return;
-  NloptSelftestEval ev{kind, nvar};
-  NloptSimplex<NV_MAX, NloptSelftestEval> ns(ev);
+  AnalyticObjective ev{kind, nvar};
+  NloptSimplex<NV_MAX, AnalyticObjective> ns(ev);
   ns.optimize(nvar, x0, lower, upper, xstep, ftol_rel, maxeval);
-  result[0] = ns.minf;
-  result[1] = (double)ns.nevals;
-  result[2] = (double)ns.status;
-  for (int i = 0; i < nvar; ++i) result[3 + i] = ns.x[i];
+  write_result(result, 0, ns.minf, (double)ns.nevals, (double)ns.status, ns.x, nvar);
 }
 
 // ---- SciPy's differential evolution (differential_evolution.h) on the device, run like Powell: every thread runs the
@@ -639,63 +407,26 @@ __global__ __launch_bounds__(REF_THREADS, 4) void refine_solve_de_kernel(
   __shared__ DeState st;
   __shared__ double red[3 * REF_THREADS / 64];
   const int64_t job = blockIdx.x;  // (pattern, start)
-  const int64_t pat_id = job / n_starts;
-  RefinePowellEval ev;
-  ev.mode = mode;
-  ev.nvar = nvar;
-  ev.fx = fixed + job * nfixed;
-  ev.g = &g;
-  ev.pat = patterns + pat_id * g.k;
-  ev.sqn = sqnorm[pat_id];
-  ev.red = red;
-  ev.trace = job == trace_job ? trace : nullptr;
-  ev.trace_capacity = trace_capacity;
-  ev.n_eval = 0;
-  DifferentialEvolution<NV_MAX, DE_POP_MAX, RefinePowellEval, DeTeam> solver(ev, st);
+  RefineEval ev = RefineEval::of_job(mode, nvar, nfixed, n_starts, fixed, g, patterns, sqnorm, red, trace_job, trace,
+                                     trace_capacity);
+  DifferentialEvolution<NV_MAX, DE_POP_MAX, RefineEval, DeTeam> solver(ev, st);
   solver.solve(nvar, lower + job * nvar, upper + job * nvar, de.members, de.maxiter, de.tol, de.atol, de.mutation_lo,
                de.mutation_hi, de.recombination, de.init, de.updating, de.seeds[job]);
-  if (threadIdx.x == 0) {
-    double *o = results + job * RESULT_STRIDE;
-    o[0] = solver.fun;
-    o[1] = (double)solver.nfev;
-    o[2] = (double)solver.nit;
-    for (int i = 0; i < nvar; ++i) o[3 + i] = solver.x[i];
-  }
+  if (threadIdx.x == 0) write_result(results, job, solver.fun, (double)solver.nfev, (double)solver.nit, solver.x, nvar);
 }
 
-// ---- differential_evolution.h alone on analytic f64 objectives: kinds 0..4 of `PowellSelftestEval`, 5 = a bowl whose
-// minimum sits on the lower bound of a box from 0, sum((i + 1) (d d + 0.1 d)) with d = |x[i]|, on which trial vectors
-// leave [0, 1] and are drawn again, 6 = +inf everywhere, 7 = 0.1 everywhere
-struct DeSelftestEval {
-  int kind, n;
-  __device__ double eval(const double *x) const {
-    if (kind == 6) return HUGE_VAL;
-    if (kind == 7) return 0.1;
-    if (kind != 5) return PowellSelftestEval{kind, n}.eval(x);
-    double acc = 0.0;
-    for (int i = 0; i < n; ++i) {
-      const double d = fabs(x[i]);
-      const double t = (double)(i + 1) * (d * d + 0.1 * d);
-      acc = i == 0 ? t : acc + t;
-    }
-    return acc;
-  }
-};
-
-// result: fun, nfev, nit, success, x[0..nvar)
+// differential_evolution.h alone, kinds 0..4 and its own 5..7 (`analytic_kind_de`): 5 = ANALYTIC_HUG, on which trial
+// vectors leave [0, 1] and are drawn again, 6 = +inf everywhere, 7 = 0.1 everywhere
 __global__ void de_selftest_kernel(int kind, int nvar, const double *lower, const double *upper, DeOptions de,
                                    unsigned seed, double *result) {
   __shared__ DeState st;
   if (threadIdx.x != 0) return;
-  DeSelftestEval ev{kind, nvar};
-  DifferentialEvolution<NV_MAX, DE_POP_MAX, DeSelftestEval> solver(ev, st);
+  AnalyticObjective ev{analytic_kind_de(kind), nvar};
+  DifferentialEvolution<NV_MAX, DE_POP_MAX, AnalyticObjective> solver(ev, st);
   solver.solve(nvar, lower, upper, de.members, de.maxiter, de.tol, de.atol, de.mutation_lo, de.mutation_hi,
                de.recombination, de.init, de.updating, seed);
-  result[0] = solver.fun;
-  result[1] = (double)solver.nfev;
-  result[2] = (double)solver.nit;
-  result[3] = solver.success ? 1.0 : 0.0;
-  for (int i = 0; i < nvar; ++i) result[4 + i] = solver.x[i];
+  write_selftest_result(result, solver.fun, (double)solver.nfev, (double)solver.nit, solver.success ? 1.0 : 0.0, solver.x,
+                        nvar);
 }
 
 // the random stream alone: `mt_program` from RandomState(seed); out[0..capacity) the words, out[capacity] their count

@@ -1,6 +1,6 @@
 """One table of differential-evolution cases for the host test (csrc/differential_evolution.h compiled with the host
 compiler) and the GPU test (`kpdi_de_selftest`), with the analytic objectives in the operation order of the C++ ones
-(`DeSelftestEval` in csrc/refine.hip, `Analytic` in tests/test_host_de.py): each row runs through
+(`AnalyticObjective` in csrc/analytic_objectives.h, kinds numbered through `analytic_kind_de`): each row runs through
 `scipy.optimize.differential_evolution(fun, bounds, polish=False, **kw)` and through the restatement, and the two must
 agree bit for bit.  Also the programs of random draws both tests run against `numpy.random.RandomState`."""
 

@@ -4,8 +4,8 @@ restatement of DESIGN.md section 21 (tests/_nlopt_simplex_restate.py), and all t
 itself is not part of any of this (tools/compare_nlopt.py runs the table through it where it is installed).
 
 The analytic objectives are those of tests/_powell_cases.py (kinds 0 to 4, in the operation order of
-`selftest_objective`, csrc/refine.hip) and kind 5, `arms`: a sum of concave arms on which contractions fail, so that
-the simplex shrinks."""
+`AnalyticObjective`, csrc/analytic_objectives.h) and kind 5, `arms` (ANALYTIC_ARMS there): a sum of concave arms on
+which contractions fail, so that the simplex shrinks."""
 
 import collections
 import math

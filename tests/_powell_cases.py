@@ -1,6 +1,6 @@
 """One table of Powell cases for the host test (csrc/powell.h compiled with the host compiler) and the GPU test
-(`kpdi_powell_selftest`), with the analytic objectives in the operation order of `selftest_objective` (csrc/refine.hip):
-each row runs through `scipy.optimize.minimize(method="Powell")` and through the restatement, and the two must agree
+(`kpdi_powell_selftest`), with the analytic objectives in the operation order of `AnalyticObjective`
+(csrc/analytic_objectives.h), which both of them evaluate; this module is their independent statement: each row runs through `scipy.optimize.minimize(method="Powell")` and through the restatement, and the two must agree
 bit for bit."""
 
 import numpy as np

@@ -16,7 +16,8 @@ from kikuchipy_amd.indexing import _refinement as rf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# The objectives in the operation order of tests/_de_cases.py.  Lines on stdin (floats as C99 hex or "nan"):
+# The objectives are csrc/analytic_objectives.h (kinds numbered as in tests/_de_cases.py: `analytic_kind_de`), in the
+# operation order of tests/_de_cases.py.  Lines on stdin (floats as C99 hex or "nan"):
 #   case kind n members maxiter tol atol mutation_lo mutation_hi recombination init updating seed lower[n] upper[n]
 #     -> success nfev nit redraws fun x[n]                (floats as their 64 bits)
 #   state seed                            -> pos key[624]
@@ -27,39 +28,10 @@ DRIVER = r"""
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "analytic_objectives.h"
 #include "differential_evolution.h"
 
-struct Analytic {
-  int kind, n;
-  double eval(const double *x) {
-    if (kind == 4) return __builtin_nan("");
-    if (kind == 3 && x[0] > 1.9) return __builtin_nan("");
-    if (kind == 6) return HUGE_VAL;
-    if (kind == 7) return 0.1;
-    double acc = 0.0;
-    if (kind == 0) {
-      for (int i = 0; i + 1 < n; ++i) {
-        const double d = x[i + 1] - x[i] * x[i], e = 1.0 - x[i];
-        const double t = 100.0 * (d * d) + e * e;
-        acc = i == 0 ? t : acc + t;
-      }
-    } else if (kind == 5) {
-      for (int i = 0; i < n; ++i) {
-        const double d = std::fabs(x[i]);
-        const double t = (double)(i + 1) * (d * d + 0.1 * d);
-        acc = i == 0 ? t : acc + t;
-      }
-    } else {
-      for (int i = 0; i < n; ++i) {
-        const double d = x[i] - 0.3 * (double)(i + 1);
-        const double t = (double)(i + 1) * (d * d);
-        acc = i == 0 ? t : acc + t;
-      }
-    }
-    if (kind == 2) acc = (double)(float)acc;
-    return acc;
-  }
-};
+using Analytic = kpdi::AnalyticObjective;
 
 constexpr int CAP = 256;
 using Solver = kpdi::DifferentialEvolution<6, CAP, Analytic>;
@@ -72,7 +44,7 @@ int main() {
     if (!std::strncmp(p, "case ", 5)) {
       p += 5;
       Analytic f;
-      f.kind = (int)std::strtol(p, &p, 10);
+      f.kind = kpdi::analytic_kind_de((int)std::strtol(p, &p, 10));
       f.n = (int)std::strtol(p, &p, 10);
       const int members = (int)std::strtol(p, &p, 10), maxiter = (int)std::strtol(p, &p, 10);
       const double tol = std::strtod(p, &p), atol = std::strtod(p, &p);

@@ -17,44 +17,18 @@ from kikuchipy_amd.indexing import _refinement as rf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# The six objectives in the operation order of tests/_nlopt_simplex_cases.py.  One line per case on stdin:
+# The six objectives are csrc/analytic_objectives.h, in the operation order of tests/_nlopt_simplex_cases.py.  One line
+# per case on stdin:
 #   kind n has_lower has_upper has_xstep ftol_rel maxeval x0[n] [lower[n]] [upper[n]] [xstep[n]]   (floats as C99 hex)
 # one line per case out: status nevals minf x[n] (floats as their 64 bits), then "count <name> <hits>" per branch.
 DRIVER = r"""
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include "analytic_objectives.h"
 #include "nlopt_simplex.h"
 
-struct Analytic {
-  int kind, n;
-  double eval(const double *x) {
-    if (kind == 4) return __builtin_nan("");
-    if (kind == 3 && x[0] > 1.9) return __builtin_nan("");
-    double acc = 0.0;
-    if (kind == 0) {
-      for (int i = 0; i + 1 < n; ++i) {
-        const double d = x[i + 1] - x[i] * x[i], e = 1.0 - x[i];
-        const double t = 100.0 * (d * d) + e * e;
-        acc = i == 0 ? t : acc + t;
-      }
-    } else if (kind == 5) {
-      for (int i = 0; i < n; ++i) {
-        const double d = std::fabs(x[i] - 0.3 * (double)(i + 1));
-        const double t = (double)(i + 1) * d / (1.0 + d);
-        acc = i == 0 ? t : acc + t;
-      }
-    } else {
-      for (int i = 0; i < n; ++i) {
-        const double d = x[i] - 0.3 * (double)(i + 1);
-        const double t = (double)(i + 1) * (d * d);
-        acc = i == 0 ? t : acc + t;
-      }
-    }
-    if (kind == 2) acc = (double)(float)acc;
-    return acc;
-  }
-};
+using Analytic = kpdi::AnalyticObjective;
 
 static unsigned long long bits(double v) {
   unsigned long long u;
