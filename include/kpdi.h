@@ -204,6 +204,32 @@ int kpdi_image_quality(kpdi_ctx *ctx, int normalize, const double *weights, doub
  * KPDI_EINVAL before anything runs.  Kernels and paths: csrc/regionsum.hip, csrc/regionsum_plan.h. */
 int kpdi_region_sums(kpdi_ctx *ctx, const int32_t *rects, int n_rects, void *sums_out);
 
+/* ---- axis reductions (EBSD.sum / mean / max / min / std / var: HyperSpy's BaseSignal methods) ------------------------
+ * Reduces the resident patterns, taken as the C-contiguous array (ny, nx, sy, sx) with ny * nx == m_all, over the axes
+ * of `axis_mask` (bit k: array axis k; 1 ... 15), AFTER the recorded background steps (they run first, as in
+ * kpdi_get_experimental); the navigation mask is ignored and the patterns are only read.  `out`: the kept axes in
+ * order, C-contiguous, of NumPy's result dtype -
+ *   KPDI_REDUCE_SUM: uint64 (uint8 / uint16 patterns), int64 (int8 / int16), float32, float64;
+ *   KPDI_REDUCE_MEAN / STD / VAR: float64 for integer patterns, else the patterns' dtype (no ddof);
+ *   KPDI_REDUCE_MAX / MIN: the patterns' dtype -
+ * and `out_bytes` its size, which is checked.  Integer sums are exact (64-bit); std / var of integers come from the exact
+ * sums of x and x^2; float patterns are accumulated in float64 in a fixed order and rounded once (std / var: in two
+ * passes, about the mean); NaN propagates through every op.  The same call gives the same bits.  A bad argument gives
+ * KPDI_EINVAL before anything runs and leaves the context as it was.  Kernels and plan: csrc/reduce.hip,
+ * csrc/reduce_plan.h. */
+#define KPDI_REDUCE_SUM 0
+#define KPDI_REDUCE_MEAN 1
+#define KPDI_REDUCE_MAX 2
+#define KPDI_REDUCE_MIN 3
+#define KPDI_REDUCE_STD 4
+#define KPDI_REDUCE_VAR 5
+int kpdi_reduce_experimental(kpdi_ctx *ctx, int op, int axis_mask, int ny, int nx, void *out, size_t out_bytes);
+/* The plan such a call follows, without a context: desc[0 ... 16] = regime (0: the inner axis survives, 1: contiguous
+ * runs are reduced), A, R1, M, R2, B of in[A][R1][M][R2][B] -> out[A][M][B], slice, slices, vector elements, lanes per
+ * output, grid x, grid y, passes, planes, workspace bytes, result bytes, lanes per output of the combine kernel.
+ * KPDI_EINVAL for what the call would refuse. */
+int kpdi_reduce_plan_describe(int dtype, int op, int axis_mask, int ny, int nx, int sy, int sx, int64_t *desc);
+
 /* ---- FFT filter (EBSD.fft_filter, signals/ebsd.py:805-930; pattern/chunk.py:75-127) ------------------------------
  * Filters every resident pattern in place, AFTER the recorded background steps (they run first), and rescales it to
  * the range of its dtype as the reference's rescale_intensity(dtype_out=<dtype>) does; the navigation mask is ignored

@@ -145,6 +145,8 @@ SIGNATURES = {
     "kpdi_get_experimental": (_i, [_vp, _vp]),
     "kpdi_image_quality": (_i, [_vp, _i, _vp, C.c_double, _vp]),
     "kpdi_region_sums": (_i, [_vp, _vp, _i, _vp]),
+    "kpdi_reduce_experimental": (_i, [_vp, _i, _i, _i, _i, _vp, _sz]),
+    "kpdi_reduce_plan_describe": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp]),
     "kpdi_fft_filter": (_i, [_vp, _i, _vp, _i, _i]),
     "kpdi_rescale_intensity": (_i, [_vp, _vp, _vp, C.c_double, C.c_double, _i]),
     "kpdi_normalize_intensity": (_i, [_vp, C.c_double, _i, _i]),
@@ -335,6 +337,35 @@ def dtype_code(dtype):
 
 DTYPE_FROM_CODE = {code: dt for dt, code in DTYPE_CODES.items()}
 
+REDUCE_OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3, "std": 4, "var": 5}  # KPDI_REDUCE_*
+REDUCE_PLAN_FIELDS = ("regime", "A", "R1", "M", "R2", "B", "slice", "n_slices", "vec", "group", "grid_x", "grid_y", "passes",
+                      "planes", "workspace_bytes", "result_bytes", "combine_lanes")
+REDUCE_COLS, REDUCE_RUNS = 0, 1  # csrc/reduce_plan.h: the inner axis survives / contiguous runs are reduced
+REDUCE_COLS_SLICE, REDUCE_RUNS_VECS, REDUCE_THREADS = 128, 16, 256  # RED_COLS_SLICE, RED_RUNS_VECS, RED_THREADS
+REDUCE_COMBINE_SERIAL, REDUCE_COMBINE_LANES = 32, 16  # RED_COMBINE_SERIAL, RED_COMBINE_LANES
+
+
+def reduce_dtype(dtype, op):
+    """NumPy's result dtype of `op` over patterns of `dtype` (checked under NumPy 2.2.6): sum -> uint64 / int64 / the
+    float dtype; mean, std, var -> float64 / the float dtype; max, min -> the dtype."""
+    dtype = np.dtype(dtype)
+    if op not in REDUCE_OPS:
+        raise ValueError(f"op {op!r} must be one of {list(REDUCE_OPS)}")
+    if dtype.kind == "f" or op in ("max", "min"):
+        return dtype
+    if op == "sum":
+        return np.dtype(np.uint64 if dtype.kind == "u" else np.int64)
+    return np.dtype(np.float64)
+
+
+def reduce_plan_describe(dtype, op, axis_mask, ny, nx, sy, sx):
+    """The plan of a `Context.reduce` (csrc/reduce_plan.h) as a dict of `REDUCE_PLAN_FIELDS`; host arithmetic, needs no
+    GPU.  `axis_mask`: bit k = axis k of (ny, nx, sy, sx) is reduced."""
+    desc = (C.c_int64 * len(REDUCE_PLAN_FIELDS))()
+    check(load().kpdi_reduce_plan_describe(dtype_code(dtype), REDUCE_OPS[op], int(axis_mask), int(ny), int(nx), int(sy),
+                                           int(sx), desc))
+    return dict(zip(REDUCE_PLAN_FIELDS, (int(v) for v in desc)))
+
 
 def _cstr(s):
     return None if s is None else os.fsencode(s)
@@ -513,6 +544,24 @@ class Context:
         dt = self._exp_dtype if kind == "f" else np.dtype(np.uint64 if kind == "u" else np.int64)
         out = np.zeros((self._exp_shape[0], len(r)), dtype=dt)
         check(self._f.region_sums(self._h, _ptr(r), len(r), _ptr(out)))
+        return out
+
+    def reduce(self, op, axes, navigation_shape):
+        """`op` ("sum", "mean", "max", "min", "std", "var") of the resident patterns (after the recorded background
+        steps), taken as an array of `navigation_shape` + (sy, sx), over its `axes` (array axes, each once): the kept
+        axes in order, of NumPy's result dtype (include/kpdi.h, kpdi_reduce_experimental)."""
+        nav = tuple(int(n) for n in navigation_shape)
+        if len(nav) > 2:
+            raise KpdiError(f"navigation shape {nav}: at most two navigation axes")
+        shape = nav + tuple(self._detector)
+        reduced = {int(ax) for ax in axes}
+        if not reduced or min(reduced) < 0 or max(reduced) >= len(shape):
+            raise KpdiError(f"axes {sorted(reduced)} of an array of {len(shape)} axes")
+        first = 2 - len(nav)  # the library's array is always (ny, nx, sy, sx)
+        ny, nx = ((1,) * first + nav)
+        out = np.empty([n for k, n in enumerate(shape) if k not in reduced], dtype=reduce_dtype(self._exp_dtype, op))
+        check(self._f.reduce_experimental(self._h, REDUCE_OPS[op], sum(1 << (ax + first) for ax in reduced), ny, nx,
+                                          _ptr(out), out.nbytes))
         return out
 
     def fft_filter(self, function_domain, table):

@@ -247,6 +247,8 @@ struct kpdi_ctx {
   kpdi::DevBuf int_out, int_ws;
   // kpdi_select_patterns: the caller's index list (the selected patterns go through int_out)
   kpdi::DevBuf sel_idx;
+  // kpdi_reduce_experimental: the per-slice partials, the means of a two-pass op and the result (reduce_plan.h)
+  kpdi::DevBuf red_ws;
   // kpdi_decomposition_*: the Gram matrix or a product, the means (and the partial sums of the mean pattern), and the
   // caller's basis / loadings / factors
   kpdi::DevBuf dec_out, dec_mean, dec_in, dec_in2;

@@ -420,6 +420,14 @@ struct RsLaunch {
 };
 hipError_t launch_region_sums(const RsLaunch &a, hipStream_t s);
 
+// ---- axis reductions (reduce.hip) ---------------------------------------------------
+struct RedLaunch {
+  const void *patterns; int dtype; int ny, nx, sy, sx;  // ny x nx x sy x sx of `dtype`, device, only read
+  int op, axis_mask;                                    // KPDI_REDUCE_*, bit k: array axis k is reduced
+  void *workspace; size_t workspace_bytes;              // reduce_plan(...).workspace_bytes; the result is left at its out_off
+};
+hipError_t launch_reduce(const RedLaunch &a, hipStream_t s);  // the plan it follows: reduce_plan.h
+
 // ---- FFT filter (fftfilter.hip) ---------------------------------------------------
 struct FfLaunch {
   void *patterns; int dtype; int64_t n; int sy, sx;  // n x sy x sx of `dtype`, device, filtered in place

@@ -2,8 +2,10 @@
 // read-back, image quality, region sums, FFT filter, intensity rescaling / normalisation and range, adaptive histogram
 // equalization, the neighbour ops, downsampling, the dynamic background, decomposition, dtype changes and selections - on
 // top of the kernels in preproc.hip, iq.hip, regionsum.hip, fftfilter.hip, intensity.hip, clahe.hip, neighbours.hip,
-// downsample.hip, decomp.hip and select.hip.  Every op checks its arguments, then runs the recorded background steps (start_pattern_op).
+// downsample.hip, decomp.hip, select.hip and reduce.hip (axis reductions).  Every op checks its arguments, then runs the
+// recorded background steps (start_pattern_op).
 #include "context.h"
+#include "reduce_plan.h"
 
 using namespace kpdi;
 
@@ -280,6 +282,59 @@ int kpdi_region_sums(kpdi_ctx *c, const int32_t *rects, int n_rects, void *sums_
     return fail(KPDI_EHIP, "region-sum kernel: %s (dtype %d, %dx%d, %d rectangles)", hipGetErrorString(e), c->exp_dtype, sy,
                 sx, n_rects);
   return results_to_host(c, sums_out, c->iq_out.p, obytes);  // (synchronises: `rects` is read)
+}
+
+int kpdi_reduce_experimental(kpdi_ctx *c, int op, int axis_mask, int ny, int nx, void *out, size_t out_bytes) {
+  int rc = check_patterns(c, "an axis reduction");
+  if (rc) return rc;
+  if (op < KPDI_REDUCE_SUM || op > KPDI_REDUCE_VAR) return fail(KPDI_EINVAL, "unknown reduction op %d", op);
+  if (axis_mask < 1 || axis_mask > 15)
+    return fail(KPDI_EINVAL, "axis mask %d: between 1 and 15, one bit per reduced axis of (ny, nx, sy, sx)", axis_mask);
+  if (ny < 1 || nx < 1 || (int64_t)ny * nx != c->m_all)
+    return fail(KPDI_EINVAL, "an axis reduction: a map of %d x %d points, %lld patterns are resident", ny, nx, (long long)c->m_all);
+  if (!out) return fail(KPDI_EINVAL, "out is NULL");
+  const kpdi::RedPlan plan = kpdi::reduce_plan(c->exp_dtype, op, axis_mask, ny, nx, c->sy, c->sx);
+  if (plan.regime < 0)
+    return fail(KPDI_EINVAL, "an axis reduction of %d x %d x %d x %d over the axes of mask %d: no kernel path takes this shape", ny, nx,
+                c->sy, c->sx, axis_mask);
+  const size_t obytes = (size_t)plan.n_out * plan.out_esize;
+  if (out_bytes != obytes)
+    return fail(KPDI_EINVAL, "out_bytes is %zu, the result has %lld values of %d bytes", out_bytes, (long long)plan.n_out, plan.out_esize);
+  rc = start_pattern_op(c);
+  if (rc) return rc;
+  HIPCHK(c->red_ws.reserve(plan.workspace_bytes));
+  kpdi::RedLaunch a{};
+  a.patterns = c->exp_raw.p;
+  a.dtype = c->exp_dtype;
+  a.ny = ny;
+  a.nx = nx;
+  a.sy = c->sy;
+  a.sx = c->sx;
+  a.op = op;
+  a.axis_mask = axis_mask;
+  a.workspace = c->red_ws.p;
+  a.workspace_bytes = c->red_ws.cap;
+  {
+    kpdi::ScopedTimer t(c, &c->ev_pre);
+    hipError_t e = kpdi::launch_reduce(a, c->stream);
+    if (e != hipSuccess)
+      return fail(KPDI_EHIP, "reduction kernel: %s (dtype %d, op %d, mask %d, %dx%dx%dx%d)", hipGetErrorString(e), c->exp_dtype, op,
+                  axis_mask, ny, nx, c->sy, c->sx);
+  }
+  return results_to_host(c, out, (const char *)c->red_ws.p + plan.out_off, obytes);
+}
+
+int kpdi_reduce_plan_describe(int dtype, int op, int axis_mask, int ny, int nx, int sy, int sx, int64_t *desc) {
+  if (!desc) return fail(KPDI_EINVAL, "desc is NULL");
+  const kpdi::RedPlan p = kpdi::reduce_plan(dtype, op, axis_mask, ny, nx, sy, sx);
+  if (p.regime < 0)
+    return fail(KPDI_EINVAL, "an axis reduction of %d x %d x %d x %d of dtype %d with op %d over the axes of mask %d: no kernel path "
+                             "takes it", ny, nx, sy, sx, dtype, op, axis_mask);
+  const int64_t d[17] = {p.regime, p.sh.A, p.sh.R1, p.sh.M, p.sh.R2, p.sh.B, p.slice, p.n_slices, p.vec, p.group,
+                         p.grid_x, p.grid_y, p.passes, p.planes, (int64_t)p.workspace_bytes, (int64_t)p.n_out * p.out_esize,
+                         p.combine_lanes};
+  std::copy(d, d + 17, desc);
+  return KPDI_OK;
 }
 
 int kpdi_fft_filter(kpdi_ctx *c, int function_domain, const double *table, int ty, int tx) {

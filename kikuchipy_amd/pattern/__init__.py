@@ -9,6 +9,7 @@ from kikuchipy_amd.pattern._pattern import (  # noqa: F401
     get_image_quality,
     normalize_intensity,
     normalize_intensity_stack,
+    reduce_stack,
     region_sums,
     remove_dynamic_background,
     remove_static_background,

@@ -258,6 +258,46 @@ def region_sums(patterns, rects, *, context=None, device=0, contexts=None):
     return _process(patterns, lambda c: None, context, device, contexts, collect=lambda c: c.region_sums(r))
 
 
+def reduce_stack(patterns, op, axes, *, context=None, device=0, contexts=None):
+    """`getattr(np, op)(patterns, axis=axes)` for `op` "sum", "mean", "max", "min", "std" or "var" over the array axes
+    `axes` (ints, negative ones from the end, each once) of patterns with up to two leading axes, on the GPU
+    (csrc/reduce.hip): NumPy's result shape and dtype (`_lib.reduce_dtype`).  Integer sums, means, maxima and minima
+    are NumPy's bits; integer std / var come from the exact sums of x and x^2; float patterns are accumulated in
+    float64 in a fixed order and rounded once, NaN propagates.  A reduction over detector axes only splits over
+    `contexts` like the other read-only ops, with the same bits; one that takes in a leading axis runs on one context
+    (partial sums of several GPUs would be combined in another order) and refuses more."""
+    patterns = as_patterns(patterns)
+    if patterns.ndim < 2 or patterns.ndim > 4:
+        raise ValueError("patterns need the two detector axes and at most two leading axes")
+    _lib.reduce_dtype(patterns.dtype, op)  # (refuses an unknown op)
+    if isinstance(axes, numbers.Integral):
+        axes = (axes,)
+    reduced = set()
+    for ax in axes:
+        if not isinstance(ax, numbers.Integral) or isinstance(ax, bool) or not -patterns.ndim <= ax < patterns.ndim:
+            raise ValueError(f"axis {ax!r} is out of bounds for patterns of {patterns.ndim} axes")
+        reduced.add(int(ax) % patterns.ndim)
+    if not reduced:
+        raise ValueError("no axis to reduce over")
+    lead = patterns.ndim - 2
+    if min(reduced) >= lead:  # every pattern on its own: a stack (n, sy, sx) per context
+        per_pattern = [ax - lead + 1 for ax in sorted(reduced)]
+        return _process(patterns, lambda c: None, context, device, contexts,
+                        collect=lambda c: c.reduce(op, per_pattern, (c._exp_shape[0],)))
+    if contexts and len(contexts) > 1:
+        raise ValueError("a reduction over a navigation axis runs on one GPU")
+    if isinstance(patterns, ResidentPatterns):
+        _upload(patterns.context if context is None else context, patterns)
+        return patterns.context.reduce(op, sorted(reduced), patterns.navigation_shape)
+    ctx = contexts[0] if contexts else _context(context, device)
+    try:
+        _upload(ctx, patterns)
+        return ctx.reduce(op, sorted(reduced), patterns.shape[:-2])
+    finally:
+        if context is None and not contexts:
+            ctx.close()
+
+
 _FUNCTION_DOMAINS = ["frequency", "spatial"]
 
 

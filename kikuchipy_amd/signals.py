@@ -18,10 +18,12 @@ signal resident instead: the patterns live in the HBM of the signal's engine con
 pre-processing method works on them where they are (`inplace=True` moves no pattern at all, `inplace=False` copies
 device to device into a new resident signal), selections (`inav`, `isig`, `crop`, `extract_grid`) run as a gather on
 the GPU, `dictionary_indexing` matches them without an upload, and `data` downloads lazily.  Who owns the buffer and
-what invalidates the host copy: DESIGN.md section 20.
+what invalidates the host copy: DESIGN.md section 20.  `EBSD.sum` / `mean` / `max` / `min` / `std` / `var` reduce over
+any set of axes where the patterns are; only the small result comes back.
 """
 
 import copy
+import numbers
 import warnings
 
 import numpy as np
@@ -81,6 +83,56 @@ class _Axes:
 
     def __repr__(self):
         return f"<axes: navigation {self.navigation_shape} | signal {self.signal_shape}>"
+
+
+def reduction_axes(axis, navigation_dimension):
+    """The array axes (sorted, each once) that `axis` of `EBSD.sum` / `mean` / `max` / `min` / `std` / `var` names on a
+    signal with `navigation_dimension` navigation axes.  Axes count in HyperSpy's natural order - navigation axes first,
+    then signal axes, each group in (x, y) order, the reverse of the array's: for (ny, nx, sy, sx) the indices 0, 1, 2, 3
+    are the array axes 1, 0, 3, 2, so (0, 1) is the map and (2, 3) the detector; with one navigation axis (0 | 1, 2) is
+    (x | dx, dy), with none (0, 1) is (dx, dy).  `axis`: an int (negative: from the end of that list), one of "x", "y",
+    "dx", "dy", or a tuple / list of these; None: every navigation axis.  Anything else raises ValueError."""
+    nd = int(navigation_dimension)
+    order = list(range(nd))[::-1] + [nd + 1, nd]
+    names = dict(zip(("x", "y")[:nd] + ("dx", "dy"), order))
+    if axis is None:
+        return tuple(range(nd))
+    reduced = set()
+    for ax in axis if isinstance(axis, (tuple, list)) else (axis,):
+        if isinstance(ax, str) and ax in names:
+            reduced.add(names[ax])
+        elif isinstance(ax, numbers.Integral) and not isinstance(ax, bool) and -len(order) <= ax < len(order):
+            reduced.add(order[ax])
+        else:
+            raise ValueError(f"axis {ax!r} is not an axis of a signal with {nd} navigation and 2 signal axes: an int in "
+                             f"[{-len(order)}, {len(order)}) or one of {list(names)}")
+    if not reduced:
+        raise ValueError(f"axis {axis!r} names no axis")
+    return tuple(sorted(reduced))
+
+
+class ReducedSignal:
+    """What an axis reduction of an `EBSD` signal leaves once a detector axis is gone (HyperSpy returns a `BaseSignal`
+    there): `data` on the host - the kept axes in array order, shape (1,) when none is kept, as HyperSpy leaves one
+    "Scalar" axis - `axes_manager` (shapes in HyperSpy's (x, y) order), `change_dtype` and `deepcopy`."""
+
+    def __init__(self, data, navigation_shape=(), signal_shape=()):
+        self.data = np.asarray(data)
+        self._navigation_shape_rc = tuple(navigation_shape)
+        self._signal_shape_rc = tuple(signal_shape)
+
+    def __repr__(self):
+        return f"<ReducedSignal, shape: {self.data.shape}, dtype: {self.data.dtype}>"
+
+    @property
+    def axes_manager(self):
+        return _Axes(self._navigation_shape_rc[::-1], self._signal_shape_rc[::-1])
+
+    def change_dtype(self, dtype):
+        self.data = self.data.astype(dtype)
+
+    def deepcopy(self):
+        return ReducedSignal(np.array(self.data, copy=True), self._navigation_shape_rc, self._signal_shape_rc)
 
 
 class VirtualBSEImage:
@@ -659,6 +711,77 @@ class EBSD:
         accepted and has nothing to show."""
         q = self._read(devices, lambda p, engines: _pattern.get_image_quality(p, normalize, **engines), flat=True)
         return q.reshape(self._navigation_shape_rc)
+
+    # ------------------------------------------------------------------ axis reductions
+    def _reduce(self, op, axis, out, devices):
+        """What `sum`, `mean`, `max`, `min`, `std` and `var` share (`kikuchipy_amd.pattern.reduce_stack`): the patterns
+        are read where they are and only the result travels; this signal stays as it is, resident if it was.  The
+        result is host-backed: an `EBSD` while both detector axes survive - `static_background` carried over, `xmap`
+        dropped, the detector a deep copy, with the single PC `pc_average` once the navigation shape changed - else a
+        `ReducedSignal`."""
+        if out is not None:
+            raise NotImplementedError("`out` is not implemented: the result is always a new, host-backed signal")
+        nav, sig = self._navigation_shape_rc, self._signal_shape_rc
+        if axis is None and not nav:
+            return self
+        axes = reduction_axes(axis, len(nav))
+        if min(axes) >= len(nav):  # every pattern on its own: splits over GPUs like the other read-only ops
+            data = self._read(devices, lambda p, engines: _pattern.reduce_stack(p, op, axes, **engines))
+        elif self._resident is not None:
+            self._own_device_only(devices)
+            data = _pattern.reduce_stack(self._resident.kept(False), op, axes, context=self.context)
+        else:
+            ids = _lib.resolve_devices(devices)
+            if ids is not None and len(ids) > 1:
+                raise ValueError(f"a reduction over a navigation axis runs on one GPU, `devices` names {len(ids)}: partial "
+                                 "results of several GPUs would be combined in another order")
+            if ids is None or ids[0] == (self._device or 0):
+                data = _pattern.reduce_stack(np.asarray(self.data), op, axes, context=self.context)
+            else:
+                data = _pattern.reduce_stack(np.asarray(self.data), op, axes, device=ids[0])
+        nav_kept = tuple(n for k, n in enumerate(nav) if k not in axes)
+        sig_kept = tuple(n for k, n in enumerate(sig, len(nav)) if k not in axes)
+        if len(sig_kept) < 2:
+            if not nav_kept and not sig_kept:
+                return ReducedSignal(data.reshape(1), (), (1,))
+            return ReducedSignal(data, nav_kept, sig_kept)
+        result = EBSD(data, self.static_background, None, self.step_sizes, self.scan_unit, self._device, self._devices)
+        if self._detector is not None:
+            result._detector = self._detector.deepcopy()
+            if nav_kept != nav:
+                result._detector.pc = result._detector.pc_average
+        if hasattr(self, "original_metadata"):
+            result.original_metadata = self.original_metadata
+        return result
+
+    def sum(self, axis=None, out=None, rechunk=False, *, devices=None):
+        """HyperSpy's `BaseSignal.sum` with its parameters in its order: the sum over `axis` (`reduction_axes`: ints in
+        HyperSpy's order, "x", "y", "dx", "dy" or a tuple of these; None: every navigation axis) in NumPy's result
+        dtype - uint64 / int64 for integer patterns, exact.  `out` other than None raises NotImplementedError, `rechunk`
+        is accepted and ignored.  What comes back: `_reduce`."""
+        return self._reduce("sum", axis, out, devices)
+
+    def mean(self, axis=None, out=None, rechunk=False, *, devices=None):
+        """`BaseSignal.mean`, as `sum`: float64 for integer patterns (NumPy's bits), else the patterns' dtype.
+        `s.mean(axis=(0, 1))` is the mean pattern - the reference's static background when the vendor file has none -
+        and `s.mean(axis=(2, 3))` the mean-intensity map."""
+        return self._reduce("mean", axis, out, devices)
+
+    def max(self, axis=None, out=None, rechunk=False, *, devices=None):
+        """`BaseSignal.max`, as `sum`, in the patterns' dtype; NaN if one is met, as `np.max`."""
+        return self._reduce("max", axis, out, devices)
+
+    def min(self, axis=None, out=None, rechunk=False, *, devices=None):
+        """`BaseSignal.min`, as `max`."""
+        return self._reduce("min", axis, out, devices)
+
+    def std(self, axis=None, out=None, rechunk=False, *, devices=None):
+        """`BaseSignal.std`, as `mean` (no `ddof`: HyperSpy's takes none)."""
+        return self._reduce("std", axis, out, devices)
+
+    def var(self, axis=None, out=None, rechunk=False, *, devices=None):
+        """`BaseSignal.var`, as `std`."""
+        return self._reduce("var", axis, out, devices)
 
     def _region_sums(self, rects, devices=None):
         """`kikuchipy_amd.pattern.region_sums` of this signal's patterns: navigation shape + (n_rects,)."""
