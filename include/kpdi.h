@@ -449,6 +449,43 @@ int kpdi_sample_fundamental_count(kpdi_ctx *ctx, int semi_edge_steps, const doub
 int kpdi_sample_fundamental_fill(kpdi_ctx *ctx, int semi_edge_steps, const double *faces, int n_faces, double *out,
                                  int64_t capacity, int64_t *count);
 
+/* ---- disorientation angles, zone reduction and kernel average misorientation maps (kikuchipy_amd/orientations.py;
+ * DESIGN.md section 25; csrc/orientations.hip, csrc/orientations_plan.h) ---------------------------------------------------
+ * Independent of the resident patterns, all in float64.  Quaternions are rows (a, b, c, d) of host float64; a row is
+ * normalised first, a row whose norm is not a positive finite number gives NaN wherever it enters.  `ops` (n_ops x 4,
+ * 1 <= n_ops <= 24) are the proper operations of a rotation group as unit quaternions, the equivalents of g are s g.
+ * The disorientation angle of g1 under ops1 and g2 under ops2 is the smallest rotation angle of (s2 g2)(s1 g1)^-1: the
+ * candidate (s1, s2) with the largest |(s1 g1) . (s2 g2)| (the lowest s1 n_ops2 + s2 among equal maxima) evaluated again
+ * as 2 atan2(|v|, |w|) of that product.  Equal groups: pass ops1 = the identity alone, one side's equivalents suffice.
+ * `degrees` != 0 multiplies the angle by 180 / pi.
+ * kpdi_orientation_pairs: `count` = prod(shape[0 .. ndim)) angles into `out`; output element (i_0, ..., i_ndim-1), C
+ *   order, takes row sum_d i_d stride1[d] of q1 (rows1 x 4) and row sum_d i_d stride2[d] of q2 (rows2 x 4): NumPy
+ *   broadcasting as strides, 0 where an input is broadcast.  ndim in [0, 8], every row addressed inside its input.
+ * kpdi_orientation_outer: the n x m angles of every row of q1 with every row of q2 into `out` (host, row-major, of
+ *   `dtype_out` KPDI_F64 or KPDI_F32: the float64 angle rounded once).  Output that does not fit in half of the free
+ *   device memory is walked in passes of rows; KPDI_ORIENT_PASS_ROWS=r in the environment, read at each call, forces
+ *   passes of r rows.  The result does not depend on the passes.
+ * kpdi_orientation_reduce: per row the equivalent s g with the largest |a| (the lowest s among equal maxima) with a >= 0
+ *   (a half turn: its first non-zero component positive) into `out` (n x 4) and s into `index` (n; -1 for a NaN row).
+ * kpdi_orientation_kam: per point of a ny x nx map the mean angle to its neighbours at `offsets` (n_offsets x (dy, dx)
+ *   int32, in window order; at most 1024), a float64 sum in that order, into `out` (ny x nx).  Left out of the mean:
+ *   neighbours outside the map, where `in_data` (ny x nx bytes, or NULL: all in) is 0, and those further than
+ *   `max_angle` (radians; negative: no limit).  NaN for a point not in the data or with no neighbour left.
+ * KPDI_EINVAL before anything runs: NULL, counts below 1, n_ops outside [1, 24], ndim outside [0, 8], a stride that
+ *   leaves its input, a dtype_out other than the two floats, more than 1024 offsets.  KPDI_ENOMEM, nothing launched and
+ *   the context usable, when the inputs and one output row (outer) or the whole output (the others) exceed the free
+ *   device memory. */
+int kpdi_orientation_pairs(kpdi_ctx *ctx, const double *q1, int64_t rows1, const double *q2, int64_t rows2, int ndim,
+                           const int64_t *shape, const int64_t *stride1, const int64_t *stride2, const double *ops1,
+                           int n_ops1, const double *ops2, int n_ops2, int degrees, double *out);
+int kpdi_orientation_outer(kpdi_ctx *ctx, const double *q1, int64_t n, const double *q2, int64_t m, const double *ops1,
+                           int n_ops1, const double *ops2, int n_ops2, int degrees, int dtype_out, void *out);
+int kpdi_orientation_reduce(kpdi_ctx *ctx, const double *q, int64_t n, const double *ops, int n_ops, double *out,
+                            int32_t *index);
+int kpdi_orientation_kam(kpdi_ctx *ctx, const double *q, int ny, int nx, const double *ops, int n_ops,
+                         const int32_t *offsets, int n_offsets, const uint8_t *in_data, double max_angle, int degrees,
+                         double *out);
+
 /* ---- geometrical simulations: Kikuchi lines and zone axes on the detector (KikuchiPatternSimulator.on_detector,
  * simulations/kikuchi_pattern_simulator.py:217-380; _kikuchi_pattern_features.py; _kikuchi_pattern_simulation.py:468-534) -----
  * Independent of the resident patterns.  All arrays are host memory, float64 unless said otherwise, row vectors.
@@ -1010,6 +1047,7 @@ typedef struct kpdi_counters {
   double geometrical_visibility_ms;   /* the kernels of the last kpdi_geometrical_visibility (profiling on) */
   double geometrical_coordinates_ms;  /* the kernels of the last kpdi_geometrical_coordinates, summed over its passes (profiling on) */
   double sampling_ms;            /* the kernels of the last kpdi_sample_fundamental_count or _fill: the passes it ran (profiling on) */
+  double orientation_ms;         /* the kernels of the last kpdi_orientation_* call, summed over its passes (profiling on) */
 } kpdi_counters;
 /* sizeof(kpdi_counters) as the LIBRARY was built: a binding whose struct differs must refuse to call kpdi_get_counters
  * (the struct has grown between versions; kpdi_version() changes with it) */

@@ -28,6 +28,9 @@ from kikuchipy_amd.simulations import (  # noqa: E402,F401
 from kikuchipy_amd.io import load  # noqa: E402,F401
 from kikuchipy_amd import filters, imaging  # noqa: E402,F401
 from kikuchipy_amd.sampling import get_sample_fundamental  # noqa: E402,F401
+from kikuchipy_amd import orientations  # noqa: E402,F401
+from kikuchipy_amd.orientations import (  # noqa: E402,F401
+    disorientation_angle, disorientation_angle_outer, kernel_average_misorientation_map, reduce_to_fundamental_zone)
 
 from kikuchipy_amd._lib import clear_engine_cache  # noqa: E402,F401
 
@@ -49,12 +52,17 @@ __all__ = [
     "SimilarityMetric",
     "clear_engine_cache",
     "dictionary_indexing",
+    "disorientation_angle",
+    "disorientation_angle_outer",
     "filters",
     "get_sample_fundamental",
     "imaging",
+    "kernel_average_misorientation_map",
     "load",
     "merge_crystal_maps",
     "orientation_similarity_map",
+    "orientations",
+    "reduce_to_fundamental_zone",
     "remove_dynamic_background",
     "remove_static_background",
 ]

@@ -28,6 +28,7 @@ DECOMPOSITION_MAX_SIDE = 8192  # csrc/decomp_plan.h, DEC_MAX_SIDE
 HEMISPHERE_CODES = {"upper": 0, "lower": 1, "both": 2}  # kpdi_kinematical_master_pattern
 KINEMATICAL_MAX_HALF_SIZE = 4096  # csrc/kinematical_plan.h, KIN_MAX_HALF_SIZE
 SAMPLING_MAX_STEPS, SAMPLING_MAX_FACES = 2048, 23  # csrc/sampling_plan.h, SMP_MAX_STEPS and SMP_MAX_FACES
+ORIENTATION_MAX_OPS, ORIENTATION_MAX_DIMS, ORIENTATION_MAX_OFFSETS = 24, 8, 1024  # csrc/orientations_plan.h, ORI_MAX_*
 GEOMETRICAL_LINES, GEOMETRICAL_ZONE_AXES = 0, 1  # kpdi_geometrical_visibility
 GEOMETRICAL_UPPER, GEOMETRICAL_INSIDE = 1, 2     # bits of its flags
 GEOMETRICAL_PC_DOUBLES = 8  # csrc/geometrical_plan.h, GEO_PC_DOUBLES
@@ -92,6 +93,7 @@ class Counters(C.Structure):
         ("geometrical_visibility_ms", C.c_double),
         ("geometrical_coordinates_ms", C.c_double),
         ("sampling_ms", C.c_double),
+        ("orientation_ms", C.c_double),
     ]
 
     def as_dict(self):
@@ -163,6 +165,10 @@ SIGNATURES = {
     "kpdi_kinematical_master_pattern": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp]),
     "kpdi_sample_fundamental_count": (_i, [_vp, _i, _vp, _i, C.POINTER(_i64)]),
     "kpdi_sample_fundamental_fill": (_i, [_vp, _i, _vp, _i, _vp, _i64, C.POINTER(_i64)]),
+    "kpdi_orientation_pairs": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    "kpdi_orientation_outer": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "kpdi_orientation_reduce": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp]),
+    "kpdi_orientation_kam": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, C.c_double, _i, _vp]),
     "kpdi_geometrical_visibility": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "kpdi_geometrical_coordinates": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.c_double,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -723,6 +729,62 @@ class Context:
         out = np.empty((count.value, 4), dtype=np.float64)
         check(self._f.sample_fundamental_fill(self._h, n, _ptr(fa) if nf else None, nf, _ptr(out), count.value,
                                               C.byref(count)))
+        return out
+
+    @staticmethod
+    def _orientation_ops(ops):
+        o = np.ascontiguousarray(ops, dtype=np.float64).reshape(-1, 4)
+        return o, int(o.shape[0])
+
+    def orientation_pairs(self, q1, q2, shape, stride1, stride2, ops1, ops2, degrees=False):
+        """Disorientation angles of a broadcast pair call (include/kpdi.h, kpdi_orientation_pairs): `q1` (rows1, 4) and
+        `q2` (rows2, 4) float64; output element (i_0, ...) of `shape` takes the rows sum_d i_d stride1[d] and
+        sum_d i_d stride2[d]; `ops1`, `ops2` (n, 4) the groups' operations (equal groups: `ops1` the identity alone).
+        Returns float64 of `shape`."""
+        a = np.ascontiguousarray(q1, dtype=np.float64).reshape(-1, 4)
+        b = np.ascontiguousarray(q2, dtype=np.float64).reshape(-1, 4)
+        (o1, n1), (o2, n2) = self._orientation_ops(ops1), self._orientation_ops(ops2)
+        shape = tuple(int(v) for v in shape)
+        sh, s1, s2 = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (shape, stride1, stride2))
+        out = np.empty(shape, dtype=np.float64)
+        check(self._f.orientation_pairs(self._h, _ptr(a), a.shape[0], _ptr(b), b.shape[0], len(shape), _ptr(sh), _ptr(s1),
+                                        _ptr(s2), _ptr(o1), n1, _ptr(o2), n2, int(bool(degrees)), _ptr(out)))
+        return out
+
+    def orientation_outer(self, q1, q2, ops1, ops2, degrees=False, dtype_out=np.float64):
+        """The (n, m) disorientation angles of every row of `q1` with every row of `q2` (include/kpdi.h,
+        kpdi_orientation_outer), float64 or float32."""
+        a = np.ascontiguousarray(q1, dtype=np.float64).reshape(-1, 4)
+        b = np.ascontiguousarray(q2, dtype=np.float64).reshape(-1, 4)
+        (o1, n1), (o2, n2) = self._orientation_ops(ops1), self._orientation_ops(ops2)
+        dt = np.dtype(dtype_out)
+        out = np.empty((a.shape[0], b.shape[0]), dtype=dt)
+        check(self._f.orientation_outer(self._h, _ptr(a), a.shape[0], _ptr(b), b.shape[0], _ptr(o1), n1, _ptr(o2), n2,
+                                        int(bool(degrees)), dtype_code(dt), _ptr(out)))
+        return out
+
+    def orientation_reduce(self, q, ops):
+        """((n, 4) float64 equivalents with the largest |a|, a >= 0; (n,) int32 operation indices, -1 for NaN rows) of the
+        rows of `q` (include/kpdi.h, kpdi_orientation_reduce)."""
+        a = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, 4)
+        o, n = self._orientation_ops(ops)
+        out, index = np.empty_like(a), np.empty(a.shape[0], dtype=np.int32)
+        check(self._f.orientation_reduce(self._h, _ptr(a), a.shape[0], _ptr(o), n, _ptr(out), _ptr(index)))
+        return out, index
+
+    def orientation_kam(self, q, ny, nx, ops, offsets, in_data=None, max_angle=None, degrees=False):
+        """The (ny, nx) float64 map of mean disorientation angles to the neighbours at `offsets` ((k, 2) int32 (dy, dx))
+        (include/kpdi.h, kpdi_orientation_kam); `max_angle` in radians or None."""
+        a = np.ascontiguousarray(q, dtype=np.float64).reshape(-1, 4)
+        o, n = self._orientation_ops(ops)
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1, 2)
+        mask = None if in_data is None else np.ascontiguousarray(in_data, dtype=np.uint8).reshape(-1)
+        if a.shape[0] != int(ny) * int(nx) or (mask is not None and mask.size != a.shape[0]):
+            raise KpdiError(f"{a.shape[0]} rotations for a map of {ny} x {nx} points")
+        out = np.empty((int(ny), int(nx)), dtype=np.float64)
+        check(self._f.orientation_kam(self._h, _ptr(a), int(ny), int(nx), _ptr(o), n, _ptr(off) if off.shape[0] else None,
+                                      int(off.shape[0]), _ptr(mask), -1.0 if max_angle is None else float(max_angle),
+                                      int(bool(degrees)), _ptr(out)))
         return out
 
     @staticmethod
@@ -1793,6 +1855,18 @@ class Group(Context):
 
     def sample_fundamental(self, *args, **kwargs):
         return self.root.sample_fundamental(*args, **kwargs)
+
+    def orientation_pairs(self, *args, **kwargs):
+        return self.root.orientation_pairs(*args, **kwargs)
+
+    def orientation_outer(self, *args, **kwargs):
+        return self.root.orientation_outer(*args, **kwargs)
+
+    def orientation_reduce(self, *args, **kwargs):
+        return self.root.orientation_reduce(*args, **kwargs)
+
+    def orientation_kam(self, *args, **kwargs):
+        return self.root.orientation_kam(*args, **kwargs)
 
     def geometrical_visibility(self, *args, **kwargs):
         return self.root.geometrical_visibility(*args, **kwargs)

@@ -267,6 +267,10 @@ struct kpdi_ctx {
     int64_t kept = 0;
   } smp_counted;
 
+  // kpdi_orientation_*: the rows of the two sets, the output of a call or of one pass of the outer kernel, the operation
+  // index of a reduction or the window offsets of a KAM map, its in-data mask
+  kpdi::DevBuf ori_a, ori_b, ori_out, ori_tab, ori_mask;
+
   // dictionary chunk
   kpdi::DevBuf dict_raw, dict_y;
   // prepared chunks kept resident for sweeps against several experimental sets

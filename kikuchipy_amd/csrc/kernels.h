@@ -15,6 +15,7 @@
 #include "kinematical_plan.h"
 #include "geometrical_plan.h"
 #include "sampling_plan.h"
+#include "orientations_plan.h"
 #include "prep_plan.h"
 
 namespace kpdi {
@@ -582,6 +583,47 @@ struct SmpLaunch {
 };
 hipError_t launch_sampling_count(const SmpLaunch &l, hipStream_t s);  // the count pass and the scan
 hipError_t launch_sampling_emit(const SmpLaunch &l, hipStream_t s);
+
+// ---- disorientation angles, zone reduction, KAM (orientations.hip) ---------------------------
+struct OriPairsLaunch {
+  const double *q1, *q2;  // raw rows [.][4], device
+  OriShape shape;         // the broadcast leading axes (strides in rows, 0 where broadcast)
+  int64_t count;          // outputs: the product of shape.dim
+  OriOps ops1, ops2;      // equal groups: ops1 = {1}
+  int degrees;
+  double *out;            // [count], device
+};
+struct OriOuterLaunch {
+  const double *q1, *q2;  // [n][4], [m][4] raw rows, device
+  int64_t n, m;
+  int64_t row_first, pass_rows;  // the rows of q1 this launch computes
+  OriOps ops1, ops2;
+  int degrees;
+  int elem_bytes;         // 8: float64 output, 4: float32
+  void *out;              // [pass_rows][m], device
+};
+struct OriReduceLaunch {
+  const double *q;        // [n][4] raw rows, device
+  int64_t n;
+  OriOps ops;
+  double *out;            // [n][4], device
+  int32_t *index;         // [n]: the operation taken, -1 for a NaN row; device
+};
+struct OriKamLaunch {
+  const double *rot;      // [ny][nx][4] raw rows, device
+  int ny, nx;
+  OriOps ops;
+  const int32_t *offsets; // [n_offsets][2] (dy, dx) in window order, device
+  int n_offsets;
+  const uint8_t *in_data; // [ny][nx] or nullptr, device
+  double max_angle;       // radians; negative: no limit
+  int degrees;
+  double *out;            // [ny][nx], device
+};
+hipError_t launch_orientation_pairs(const OriPairsLaunch &l, hipStream_t s);
+hipError_t launch_orientation_outer(const OriOuterLaunch &l, hipStream_t s);
+hipError_t launch_orientation_reduce(const OriReduceLaunch &l, hipStream_t s);
+hipError_t launch_orientation_kam(const OriKamLaunch &l, hipStream_t s);
 
 // ---- geometrical simulations (geometrical.hip) ---------------------------------------------
 struct GeoVisLaunch {

@@ -1,7 +1,8 @@
 // simulation_ops.hip - host side of libkpdi.so, the simulations that need no resident patterns: the kinematical master
 // pattern (kinematical.hip) and the geometrical simulations (geometrical.hip), their tables formed on the host
-// (kinematical_plan.h, geometrical_plan.h), and the orientation sampling that feeds a dictionary (sampling.hip,
-// sampling_plan.h).
+// (kinematical_plan.h, geometrical_plan.h), the orientation sampling that feeds a dictionary (sampling.hip,
+// sampling_plan.h), and what is done with the orientations that come back: disorientation angles, zone reduction and
+// KAM maps (orientations.hip, orientations_plan.h).
 #include "context.h"
 
 using namespace kpdi;
@@ -352,6 +353,225 @@ int kpdi_sample_fundamental_fill(kpdi_ctx *c, int semi_edge_steps, const double 
     return fail(KPDI_EHIP, "sampling emit kernel: %s (semi_edge_steps %d, %lld orientations)", hipGetErrorString(e), semi_edge_steps,
                 (long long)kept);
   if (rc == KPDI_OK && c->profiling) c->cnt.sampling_ms = kernel_ms + emit_ms;
+  return rc;
+}
+
+// ---- disorientation angles, zone reduction, KAM maps (orientations.hip) ------------------------------------------------
+
+static int orientation_ops(const double *ops, int n_ops, const char *what, kpdi::OriOps *o) {
+  if (!ops) return fail(KPDI_EINVAL, "%s is NULL", what);
+  if (n_ops < 1 || n_ops > kpdi::ORI_MAX_OPS) return fail(KPDI_EINVAL, "%d operations in %s: between 1 and %d", n_ops, what, kpdi::ORI_MAX_OPS);
+  *o = kpdi::OriOps{};
+  o->n = n_ops;
+  memcpy(o->q, ops, (size_t)n_ops * 4 * sizeof(double));
+  return KPDI_OK;
+}
+
+// free device memory beyond what the context's buffers of this call already hold
+static int orientation_fits(size_t need, size_t held, const char *what) {
+  size_t free_bytes = 0, total_bytes = 0;
+  HIPCHK(hipMemGetInfo(&free_bytes, &total_bytes));
+  if (need > held && need - held > free_bytes)
+    return fail(KPDI_ENOMEM, "%s needs %zu bytes of device memory, %zu are held and %zu free", what, need, held, free_bytes);
+  return KPDI_OK;
+}
+
+static int orientation_upload(kpdi_ctx *c, kpdi::DevBuf &buf, const void *src, size_t bytes) {
+  HIPCHK(buf.reserve(bytes));
+  HIPCHK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+  return KPDI_OK;
+}
+
+int kpdi_orientation_pairs(kpdi_ctx *c, const double *q1, int64_t rows1, const double *q2, int64_t rows2, int ndim,
+                           const int64_t *shape, const int64_t *stride1, const int64_t *stride2, const double *ops1,
+                           int n_ops1, const double *ops2, int n_ops2, int degrees, double *out) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!q1 || !q2 || !out) return fail(KPDI_EINVAL, "q1, q2 or out is NULL");
+  if (rows1 < 1 || rows2 < 1) return fail(KPDI_EINVAL, "%lld and %lld rows: at least one each", (long long)rows1, (long long)rows2);
+  if (ndim < 0 || ndim > kpdi::ORI_MAX_DIMS) return fail(KPDI_EINVAL, "%d leading axes: between 0 and %d", ndim, kpdi::ORI_MAX_DIMS);
+  if (ndim > 0 && (!shape || !stride1 || !stride2)) return fail(KPDI_EINVAL, "shape, stride1 or stride2 is NULL");
+  kpdi::OriPairsLaunch l{};
+  int rc = orientation_ops(ops1, n_ops1, "ops1", &l.ops1);
+  if (rc) return rc;
+  rc = orientation_ops(ops2, n_ops2, "ops2", &l.ops2);
+  if (rc) return rc;
+  l.shape.nd = ndim;
+  int64_t count = 1, last1 = 0, last2 = 0;
+  for (int d = 0; d < ndim; ++d) {
+    if (shape[d] < 1 || stride1[d] < 0 || stride2[d] < 0 || shape[d] > INT64_MAX / 64 / count)
+      return fail(KPDI_EINVAL, "axis %d: length %lld, strides %lld and %lld", d, (long long)shape[d], (long long)stride1[d],
+                  (long long)stride2[d]);
+    l.shape.dim[d] = shape[d];
+    l.shape.stride1[d] = stride1[d];
+    l.shape.stride2[d] = stride2[d];
+    count *= shape[d];
+    if ((stride1[d] && (shape[d] - 1) > (rows1 - 1 - last1) / stride1[d]) || (stride2[d] && (shape[d] - 1) > (rows2 - 1 - last2) / stride2[d]))
+      return fail(KPDI_EINVAL, "axis %d of length %lld with strides %lld and %lld leaves an input of %lld and %lld rows", d,
+                  (long long)shape[d], (long long)stride1[d], (long long)stride2[d], (long long)rows1, (long long)rows2);
+    last1 += (shape[d] - 1) * stride1[d];
+    last2 += (shape[d] - 1) * stride2[d];
+  }
+  if (kpdi::ori_blocks(count) > kpdi::ORI_MAX_TILES) return fail(KPDI_EINVAL, "%lld pairs: more than one launch takes", (long long)count);
+  rc = use_device(c);
+  if (rc) return rc;
+  const size_t b1 = (size_t)rows1 * 32, b2 = (size_t)rows2 * 32, bo = (size_t)count * sizeof(double);
+  rc = orientation_fits(b1 + b2 + bo, c->ori_a.cap + c->ori_b.cap + c->ori_out.cap, "the disorientation angles of these pairs");
+  if (rc) return rc;
+  rc = orientation_upload(c, c->ori_a, q1, b1);
+  if (rc == KPDI_OK) rc = orientation_upload(c, c->ori_b, q2, b2);
+  if (rc) return rc;
+  HIPCHK(c->ori_out.reserve(bo));
+  l.q1 = c->ori_a.as<double>();
+  l.q2 = c->ori_b.as<double>();
+  l.count = count;
+  l.degrees = degrees != 0;
+  l.out = c->ori_out.as<double>();
+  hipError_t e = hipSuccess;
+  double ms = 0.0;
+  rc = launch_to_host(c, [&] { return kpdi::launch_orientation_pairs(l, c->stream); }, out, l.out, bo, &ms, &e);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(c->stream);  // the uploads read the caller's arrays
+    return fail(KPDI_EHIP, "orientation pairs kernel: %s (%lld pairs)", hipGetErrorString(e), (long long)count);
+  }
+  if (rc == KPDI_OK && c->profiling) c->cnt.orientation_ms = ms;
+  return rc;
+}
+
+int kpdi_orientation_outer(kpdi_ctx *c, const double *q1, int64_t n, const double *q2, int64_t m, const double *ops1,
+                           int n_ops1, const double *ops2, int n_ops2, int degrees, int dtype_out, void *out) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!q1 || !q2 || !out) return fail(KPDI_EINVAL, "q1, q2 or out is NULL");
+  if (n < 1 || m < 1 || n > INT64_MAX / 64 / m) return fail(KPDI_EINVAL, "%lld x %lld orientations: at least one each", (long long)n, (long long)m);
+  if (dtype_out != KPDI_F64 && dtype_out != KPDI_F32) return fail(KPDI_EINVAL, "dtype_out %d: the angles are float64 or float32", dtype_out);
+  kpdi::OriOps o1, o2;
+  int rc = orientation_ops(ops1, n_ops1, "ops1", &o1);
+  if (rc) return rc;
+  rc = orientation_ops(ops2, n_ops2, "ops2", &o2);
+  if (rc) return rc;
+  int64_t forced = 0;
+  if (const char *e = getenv("KPDI_ORIENT_PASS_ROWS")) {
+    forced = strtoll(e, nullptr, 10);
+    if (forced < 1) return fail(KPDI_EINVAL, "KPDI_ORIENT_PASS_ROWS=%s: a positive number of rows", e);
+  }
+  rc = use_device(c);
+  if (rc) return rc;
+  const int elem = dtype_out == KPDI_F64 ? 8 : 4;
+  const size_t b1 = (size_t)n * 32, b2 = (size_t)m * 32;
+  size_t free_bytes = 0, total_bytes = 0;
+  HIPCHK(hipMemGetInfo(&free_bytes, &total_bytes));
+  const size_t held = c->ori_a.cap + c->ori_b.cap + c->ori_out.cap, inputs = b1 + b2;
+  const size_t room = free_bytes + held > inputs ? free_bytes + held - inputs : 0;
+  const kpdi::OriOuterPlan plan = kpdi::ori_outer_plan(n, m, elem, room / 2, forced);
+  if (!plan.ok || plan.pass_bytes > room)
+    return fail(KPDI_ENOMEM, "the %lld x %lld disorientation angles: the inputs and one pass of rows need more than the %zu "
+                "bytes of device memory that are free", (long long)n, (long long)m, free_bytes);
+  rc = orientation_upload(c, c->ori_a, q1, b1);
+  if (rc == KPDI_OK) rc = orientation_upload(c, c->ori_b, q2, b2);
+  if (rc) return rc;
+  HIPCHK(c->ori_out.reserve(plan.pass_bytes));
+  kpdi::EventPair timer(c, c->profiling != 0);  // recorded again in every pass
+  double kernel_ms = 0.0;
+  hipError_t e = hipSuccess;
+  for (int64_t pass = 0; pass < plan.n_passes && rc == KPDI_OK; ++pass) {
+    kpdi::OriOuterLaunch l{};
+    l.q1 = c->ori_a.as<double>();
+    l.q2 = c->ori_b.as<double>();
+    l.n = n;
+    l.m = m;
+    l.row_first = pass * plan.pass_rows;
+    l.pass_rows = pass == plan.n_passes - 1 ? plan.tail_rows : plan.pass_rows;
+    l.ops1 = o1;
+    l.ops2 = o2;
+    l.degrees = degrees != 0;
+    l.elem_bytes = elem;
+    l.out = c->ori_out.p;
+    (void)timer.begin();
+    e = kpdi::launch_orientation_outer(l, c->stream);
+    (void)timer.end();
+    if (e != hipSuccess) break;
+    const size_t row_bytes = (size_t)m * (size_t)elem;
+    rc = kpdi::results_to_host(c, (char *)out + (size_t)l.row_first * row_bytes, c->ori_out.p, (size_t)l.pass_rows * row_bytes);
+    float ms = 0.f;
+    if (rc == KPDI_OK && timer.elapsed(&ms) == hipSuccess) kernel_ms += ms;
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(c->stream);
+    return fail(KPDI_EHIP, "orientation outer kernel: %s (%lld x %lld)", hipGetErrorString(e), (long long)n, (long long)m);
+  }
+  if (rc == KPDI_OK && timer.on()) c->cnt.orientation_ms = kernel_ms;
+  return rc;
+}
+
+int kpdi_orientation_reduce(kpdi_ctx *c, const double *q, int64_t n, const double *ops, int n_ops, double *out, int32_t *index) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!q || !out || !index) return fail(KPDI_EINVAL, "q, out or index is NULL");
+  if (n < 1 || kpdi::ori_blocks(n) > kpdi::ORI_MAX_TILES) return fail(KPDI_EINVAL, "%lld orientations: at least one is needed", (long long)n);
+  kpdi::OriReduceLaunch l{};
+  int rc = orientation_ops(ops, n_ops, "ops", &l.ops);
+  if (rc) return rc;
+  rc = use_device(c);
+  if (rc) return rc;
+  const size_t bq = (size_t)n * 32, bi = (size_t)n * sizeof(int32_t);
+  rc = orientation_fits(2 * bq + bi, c->ori_a.cap + c->ori_out.cap + c->ori_tab.cap, "the zone reduction of these orientations");
+  if (rc) return rc;
+  rc = orientation_upload(c, c->ori_a, q, bq);
+  if (rc) return rc;
+  HIPCHK(c->ori_out.reserve(bq));
+  HIPCHK(c->ori_tab.reserve(bi));
+  l.q = c->ori_a.as<double>();
+  l.n = n;
+  l.out = c->ori_out.as<double>();
+  l.index = c->ori_tab.as<int32_t>();
+  hipError_t e = hipSuccess;
+  double ms = 0.0;
+  rc = launch_to_host(c, [&] { return kpdi::launch_orientation_reduce(l, c->stream); }, out, l.out, bq, &ms, &e);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(c->stream);
+    return fail(KPDI_EHIP, "orientation reduce kernel: %s (%lld orientations)", hipGetErrorString(e), (long long)n);
+  }
+  if (rc == KPDI_OK) rc = results_to_host(c, index, l.index, bi);
+  if (rc == KPDI_OK && c->profiling) c->cnt.orientation_ms = ms;
+  return rc;
+}
+
+int kpdi_orientation_kam(kpdi_ctx *c, const double *q, int ny, int nx, const double *ops, int n_ops, const int32_t *offsets,
+                         int n_offsets, const uint8_t *in_data, double max_angle, int degrees, double *out) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!q || !out) return fail(KPDI_EINVAL, "q or out is NULL");
+  if (ny < 1 || nx < 1) return fail(KPDI_EINVAL, "a map of %d x %d points: at least one is needed", ny, nx);
+  if (n_offsets < 0 || n_offsets > kpdi::ORI_MAX_OFFSETS || (n_offsets > 0 && !offsets))
+    return fail(KPDI_EINVAL, "%d window offsets: between 0 and %d, offsets not NULL", n_offsets, kpdi::ORI_MAX_OFFSETS);
+  if (max_angle != max_angle) return fail(KPDI_EINVAL, "max_angle is NaN: negative for no limit");
+  kpdi::OriKamLaunch l{};
+  int rc = orientation_ops(ops, n_ops, "ops", &l.ops);
+  if (rc) return rc;
+  rc = use_device(c);
+  if (rc) return rc;
+  const size_t points = (size_t)ny * (size_t)nx, bq = points * 32, bo = points * sizeof(double), bt = (size_t)n_offsets * 2 * sizeof(int32_t);
+  rc = orientation_fits(bq + bo + bt + points, c->ori_a.cap + c->ori_out.cap + c->ori_tab.cap + c->ori_mask.cap, "the KAM map");
+  if (rc) return rc;
+  rc = orientation_upload(c, c->ori_a, q, bq);
+  if (rc == KPDI_OK && n_offsets > 0) rc = orientation_upload(c, c->ori_tab, offsets, bt);
+  if (rc == KPDI_OK && in_data) rc = orientation_upload(c, c->ori_mask, in_data, points);
+  if (rc) return rc;
+  HIPCHK(c->ori_out.reserve(bo));
+  l.rot = c->ori_a.as<double>();
+  l.ny = ny;
+  l.nx = nx;
+  l.offsets = n_offsets > 0 ? c->ori_tab.as<int32_t>() : nullptr;
+  l.n_offsets = n_offsets;
+  l.in_data = in_data ? c->ori_mask.as<uint8_t>() : nullptr;
+  l.max_angle = max_angle;
+  l.degrees = degrees != 0;
+  l.out = c->ori_out.as<double>();
+  hipError_t e = hipSuccess;
+  double ms = 0.0;
+  rc = launch_to_host(c, [&] { return kpdi::launch_orientation_kam(l, c->stream); }, out, l.out, bo, &ms, &e);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(c->stream);
+    return fail(KPDI_EHIP, "orientation KAM kernel: %s (%d x %d points)", hipGetErrorString(e), ny, nx);
+  }
+  if (rc == KPDI_OK && c->profiling) c->cnt.orientation_ms = ms;
   return rc;
 }
 
