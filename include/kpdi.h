@@ -486,6 +486,41 @@ int kpdi_orientation_kam(kpdi_ctx *ctx, const double *q, int ny, int nx, const d
                          const int32_t *offsets, int n_offsets, const uint8_t *in_data, double max_angle, int degrees,
                          double *out);
 
+/* ---- Hough indexing (kikuchipy_amd/indexing/_hough_indexing.py; csrc/hough.hip, csrc/hough_plan.h,
+ * csrc/hough_vote.h) ---------------------------------------------------------------------------------------------------
+ * kpdi_hough_bands: the Radon transform of every resident pattern (after the recorded background steps; the six pattern
+ *   dtypes) and the `n_bands` (1 ... 16) strongest bands of each into `bands_out` (m_all x n_bands records of 32 bytes:
+ *   float32 theta [rad], rho [px], value; int32 valid, a, k; float32 da, dk).  A pattern is masked by its inscribed circle
+ *   and its masked mean removed; S[a][k] sums it, sampled bilinearly at unit steps, along the line
+ *   cos(theta) (j - cx) + sin(theta) (i - cy) = rho, theta = a pi / n_theta, rho = (k - (n_rho - 1) / 2) drho,
+ *   drho = 2 floor(R) / (n_rho - 1), R = (min(ny, nx) - 1) / 2, cx = (nx - 1) / 2, cy = (ny - 1) / 2.  `cos_sin` holds
+ *   the n_theta cosines, then the n_theta sines, as float32: the caller's table, so that a restatement works from the same
+ *   bits.  The sinogram is smoothed along rho (zeros beyond the ends) by the 2 rho_radius + 1 float32 `rho_taps`, then
+ *   along theta (the axis wraps with rho flipped) by the 2 theta_radius + 1 `theta_taps` (radii 0 ... 16), `rim` >= 1
+ *   cells at either end of the rho axis hold no band, a band is a positive maximum of its 7 x 7
+ *   window (the first cell of a plateau), the strongest are kept (ties: the lower cell index a n_rho + k first) and placed
+ *   within their cell by a parabola per axis; bands that do not exist have valid = 0.  `sinogram_out` (NULL, or m_all x
+ *   n_theta x n_rho float32) receives the unsmoothed sinograms.  Deterministic: no atomics, fixed summation orders.  The
+ *   workspace is walked in passes sized from the free device memory; KPDI_HOUGH_PASS=n in the environment forces passes
+ *   of n patterns.  The result does not depend on the passes.
+ * kpdi_hough_index: per pattern the orientation that explains its bands under one phase.  `bands` (m x n_bands records,
+ *   host), `pcs` (n_pc x 3 Bruker projection centres, n_pc = 1 or m), the detector's shape and `s2d` (3 x 3
+ *   sample-to-detector matrix, row-major), the phase's reflectors as lines: `normals` (n x 3 unit vectors, crystal
+ *   Cartesian, one of g and -g), `family` (n, in [0, n_families)), `angles` (n x n folded interplanar angles, radians),
+ *   and the tolerance `tol` (radians).  Triplet voting with integer votes, hypotheses from band pairs, an orthogonal fit
+ *   (hough_vote.h).  Out: `quat` (m x 4, the convention of the refinement results), `fit` (mean angular deviation in
+ *   degrees, 180 when not indexed), `cm` (matched bands / n_bands), `nmatch` (0 when not indexed).
+ * kpdi_hough_plan_describe: {ok, lds, lds_bytes, pattern_bytes, pass_patterns, n_passes, tail_patterns} of the plan for
+ *   `room_bytes` of workspace; host arithmetic.  kpdi_hough_default_n_rho: one pixel per rho cell. */
+int kpdi_hough_default_n_rho(int ny, int nx);
+int kpdi_hough_plan_describe(int ny, int nx, int n_theta, int n_rho, int64_t m, int64_t room_bytes, int64_t forced,
+                             int64_t *desc);
+int kpdi_hough_bands(kpdi_ctx *ctx, int n_theta, int n_rho, const float *cos_sin, const float *theta_taps, int theta_radius,
+                     const float *rho_taps, int rho_radius, int rim, int n_bands, void *bands_out, float *sinogram_out);
+int kpdi_hough_index(kpdi_ctx *ctx, const void *bands, int64_t m, int n_bands, const double *pcs, int64_t n_pc, int ny, int nx,
+                     const double *s2d, const double *normals, const int32_t *family, int n_reflectors, int n_families,
+                     const double *angles, double tol, double *quat, double *fit, double *cm, int32_t *nmatch);
+
 /* ---- geometrical simulations: Kikuchi lines and zone axes on the detector (KikuchiPatternSimulator.on_detector,
  * simulations/kikuchi_pattern_simulator.py:217-380; _kikuchi_pattern_features.py; _kikuchi_pattern_simulation.py:468-534) -----
  * Independent of the resident patterns.  All arrays are host memory, float64 unless said otherwise, row vectors.

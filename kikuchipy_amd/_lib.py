@@ -169,6 +169,11 @@ SIGNATURES = {
     "kpdi_orientation_outer": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i, _vp, _i, _i, _i, _vp]),
     "kpdi_orientation_reduce": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp]),
     "kpdi_orientation_kam": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, C.c_double, _i, _vp]),
+    "kpdi_hough_default_n_rho": (_i, [_i, _i]),
+    "kpdi_hough_plan_describe": (_i, [_i, _i, _i, _i, _i64, _i64, _i64, _vp]),
+    "kpdi_hough_bands": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "kpdi_hough_index": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _vp, C.c_double, _vp, _vp, _vp,
+                              _vp]),
     "kpdi_geometrical_visibility": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "kpdi_geometrical_coordinates": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.c_double,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -371,6 +376,25 @@ def reduce_plan_describe(dtype, op, axis_mask, ny, nx, sy, sx):
     check(load().kpdi_reduce_plan_describe(dtype_code(dtype), REDUCE_OPS[op], int(axis_mask), int(ny), int(nx), int(sy),
                                            int(sx), desc))
     return dict(zip(REDUCE_PLAN_FIELDS, (int(v) for v in desc)))
+
+
+# csrc/hough_plan.h: one detected band (HoughBand), the limits, and what kpdi_hough_plan_describe fills in
+HOUGH_BAND_DTYPE = np.dtype([("theta", "<f4"), ("rho", "<f4"), ("value", "<f4"), ("valid", "<i4"), ("a", "<i4"), ("k", "<i4"),
+                             ("da", "<f4"), ("dk", "<f4")])
+HOUGH_MAX_BANDS, HOUGH_MAX_REFLECTORS, HOUGH_MAX_FAMILIES = 16, 96, 16
+HOUGH_PLAN_FIELDS = ("ok", "lds", "lds_bytes", "pattern_bytes", "pass_patterns", "n_passes", "tail_patterns")
+
+
+def hough_default_n_rho(ny, nx):
+    """One pixel per rho cell over the inscribed circle (csrc/hough_plan.h)."""
+    return int(load().kpdi_hough_default_n_rho(int(ny), int(nx)))
+
+
+def hough_plan_describe(ny, nx, n_theta, n_rho, m, room_bytes, forced=0):
+    """The launch plan of `Context.hough_bands` (csrc/hough_plan.h) as a dict of `HOUGH_PLAN_FIELDS`; host arithmetic."""
+    desc = (C.c_int64 * len(HOUGH_PLAN_FIELDS))()
+    check(load().kpdi_hough_plan_describe(int(ny), int(nx), int(n_theta), int(n_rho), int(m), int(room_bytes), int(forced), desc))
+    return dict(zip(HOUGH_PLAN_FIELDS, (int(v) for v in desc)))
 
 
 def _cstr(s):
@@ -786,6 +810,41 @@ class Context:
                                       int(off.shape[0]), _ptr(mask), -1.0 if max_angle is None else float(max_angle),
                                       int(bool(degrees)), _ptr(out)))
         return out
+
+    def hough_bands(self, n_rho, cos_sin, theta_taps, rho_taps, rim, n_bands, return_sinograms=False):
+        """The `n_bands` strongest bands of every resident pattern (include/kpdi.h, kpdi_hough_bands): (m_all, n_bands) of
+        `HOUGH_BAND_DTYPE`; with `return_sinograms` also the (m_all, n_theta, n_rho) float32 sinograms.  `cos_sin`
+        (2, n_theta) and the two odd-length tap tables are float32."""
+        m = int(self._exp_shape[0])
+        cs = np.ascontiguousarray(cos_sin, dtype=np.float32)
+        wt, wr = (np.ascontiguousarray(w, dtype=np.float32).reshape(-1) for w in (theta_taps, rho_taps))
+        if cs.ndim != 2 or cs.shape[0] != 2 or wt.size % 2 != 1 or wr.size % 2 != 1:
+            raise KpdiError(f"cos_sin of shape {cs.shape}, {wt.size} and {wr.size} taps: (2, n_theta) and odd numbers of taps")
+        n_theta = cs.shape[1]
+        bands = np.zeros((m, int(n_bands)), dtype=HOUGH_BAND_DTYPE)
+        sino = np.empty((m, int(n_theta), int(n_rho)), dtype=np.float32) if return_sinograms else None
+        check(self._f.hough_bands(self._h, n_theta, int(n_rho), _ptr(cs), _ptr(wt), wt.size // 2, _ptr(wr), wr.size // 2, int(rim),
+                                  int(n_bands), _ptr(bands), _ptr(sino)))
+        return (bands, sino) if return_sinograms else bands
+
+    def hough_index(self, bands, pcs, shape, sample_to_detector, normals, family, angles, tol):
+        """Orientations from bands under one phase (include/kpdi.h, kpdi_hough_index): `bands` (m, n_bands) of
+        `HOUGH_BAND_DTYPE`, `pcs` (1 or m, 3).  Returns (quat (m, 4), fit (m,), cm (m,), nmatch (m,) int32)."""
+        b = np.ascontiguousarray(bands, dtype=HOUGH_BAND_DTYPE)
+        m, nb = b.shape
+        pc = np.ascontiguousarray(pcs, dtype=np.float64).reshape(-1, 3)
+        s2d = np.ascontiguousarray(sample_to_detector, dtype=np.float64).reshape(3, 3)
+        g = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+        fam = np.ascontiguousarray(family, dtype=np.int32).reshape(-1)
+        ang = np.ascontiguousarray(angles, dtype=np.float64)
+        if fam.size != g.shape[0] or ang.shape != (g.shape[0], g.shape[0]):
+            raise KpdiError(f"{g.shape[0]} reflectors with {fam.size} families and angles of shape {ang.shape}")
+        quat, fit, cm = np.empty((m, 4)), np.empty(m), np.empty(m)
+        nmatch = np.empty(m, dtype=np.int32)
+        check(self._f.hough_index(self._h, _ptr(b), m, nb, _ptr(pc), pc.shape[0], int(shape[0]), int(shape[1]), _ptr(s2d),
+                                  _ptr(g), _ptr(fam), g.shape[0], int(fam.max()) + 1, _ptr(ang), float(tol), _ptr(quat),
+                                  _ptr(fit), _ptr(cm), _ptr(nmatch)))
+        return quat, fit, cm, nmatch
 
     @staticmethod
     def _geometrical_inputs(rotations, u_s, pcs, *bases):

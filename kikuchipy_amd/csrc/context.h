@@ -271,6 +271,10 @@ struct kpdi_ctx {
   // index of a reduction or the window offsets of a KAM map, its in-data mask
   kpdi::DevBuf ori_a, ori_b, ori_out, ori_tab, ori_mask;
 
+  // kpdi_hough_*: the sinogram workspace of one pass, the cos / sin tables or a phase's tables, the bands, the projection
+  // centres and the results of the indexing kernel
+  kpdi::DevBuf hough_ws, hough_tab, hough_bands, hough_pc, hough_out;
+
   // dictionary chunk
   kpdi::DevBuf dict_raw, dict_y;
   // prepared chunks kept resident for sweeps against several experimental sets

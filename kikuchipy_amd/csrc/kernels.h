@@ -16,6 +16,8 @@
 #include "geometrical_plan.h"
 #include "sampling_plan.h"
 #include "orientations_plan.h"
+#include "hough_plan.h"
+#include "hough_vote.h"
 #include "prep_plan.h"
 
 namespace kpdi {
@@ -648,5 +650,12 @@ GeoVisPlan geometrical_visibility_plan(int64_t m, int64_t n_points);            
 GeoCoordPlan geometrical_coord_plan(int64_t m, int64_t z, int64_t n_points, size_t budget_bytes);  // developer switch
 hipError_t launch_geometrical_visibility(const GeoVisLaunch &l, hipStream_t s);
 hipError_t launch_geometrical_coordinates(const GeoCoordLaunch &l, hipStream_t s);
+
+// ---- Hough indexing (hough.hip; the launch structs are in hough_plan.h and hough_vote.h) ---------------
+hipError_t launch_hough_radon(const HoughBandsLaunch &l, hipStream_t s);
+hipError_t launch_hough_bands(const HoughBandsLaunch &l, hipStream_t s);
+// one thread per pattern: `bands` [m][n_bands], `pcs` [n_pc][3] with n_pc = 1 or m, the phase's tables, all device
+hipError_t launch_hough_index(const HoughBand *bands, int64_t m, int n_bands, const double *pcs, int64_t n_pc, const HvDetector &det,
+                              const HvPhase &phase, double *quat, double *fit, double *cm, int32_t *nmatch, hipStream_t s);
 
 }  // namespace kpdi

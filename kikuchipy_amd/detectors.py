@@ -7,7 +7,8 @@ sample-to-detector orientation matrix that
 
 One PC, or one PC per map point (`pc` of shape navigation shape + (3,)):
 dictionary generation uses a single PC for the whole dictionary (SURVEY.md
-8(f1)), refinement takes either (8(f2)).  Plotting, calibration, PC
+8(f1)), refinement takes either (8(f2)).  `get_indexer` returns the indexer of
+Hough indexing.  Plotting, calibration, PC
 fitting/extrapolation and file I/O are out of scope.
 """
 
@@ -317,6 +318,17 @@ class EBSDDetector:
     def detector_to_sample(self):
         """`(~detector.sample_to_detector).to_matrix()`: the transpose."""
         return np.ascontiguousarray(self.sample_to_detector.T)
+
+    def get_indexer(self, phase_list, reflectors=None, **kwargs):
+        """A `HoughIndexer` for `EBSD.hough_indexing` and `EBSD.hough_indexing_optimize_pc` from this detector's shape,
+        PC(s), sample tilt and tilt (detectors/_ebsd_detector.py:1598 of the reference).  `phase_list`: a phase or a list
+        of phases, each a `Reflectors`, a (`Reflectors` or hkl array, point group) pair, or a point-group name (a cubic
+        lattice); `reflectors`: None, or per phase the hkl to index with.  `**kwargs` of the band detection: `nBands` (9),
+        `nTheta` (180), `nRho`, `tSigma`, `rSigma`, `rhoMaskFrac`; anything else raises `TypeError`.  The algorithm is
+        this package's own (kikuchipy_amd/indexing/_hough_indexing.py), not PyEBSDIndex's."""
+        from kikuchipy_amd.indexing._hough_indexing import indexer_from_detector
+
+        return indexer_from_detector(self, phase_list, reflectors, **kwargs)
 
     def crop(self, extent):
         """A new detector cropped to `extent` = (top, bottom, left, right) in pixels, its PC values updated

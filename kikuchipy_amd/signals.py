@@ -1054,6 +1054,24 @@ class EBSD:
                             compute, verbose, comm, devices)
 
     # ------------------------------------------------------------------ indexing
+    def hough_indexing(self, phase_list, indexer, chunksize=528, verbose=1, return_index_data=False, return_band_data=False):
+        """signals/ebsd.py:1600-1719: index the patterns - where they are, resident or on the host - by Hough indexing
+        with an indexer of `EBSDDetector.get_indexer` (kikuchipy_amd/indexing/_hough_indexing.py; this package's own
+        algorithm, not PyEBSDIndex's).  Returns a `HoughIndexingResult` (`rotations`, `fit`, `cm`, `pq`, `nmatch`,
+        `phase_id` with -1 where not indexed, `is_in_data`) and on request `index_data` (n_phases + 1, M) and `band_data`
+        (M, nBands)."""
+        from kikuchipy_amd.indexing import _hough_indexing
+
+        return _hough_indexing.hough_indexing(self, phase_list, indexer, chunksize, verbose, return_index_data, return_band_data)
+
+    def hough_indexing_optimize_pc(self, pc0, indexer, batch=False, method="Nelder-Mead", **kwargs):
+        """signals/ebsd.py:1721-1825: a detector with the PC (`batch=True`: one per pattern, in the navigation shape)
+        that minimises the mean `fit` of Hough indexing, found by a host Nelder-Mead search from `pc0` that detects the
+        bands once and runs only the indexing kernel per step.  `method="PSO"` is not implemented."""
+        from kikuchipy_amd.indexing import _hough_indexing
+
+        return _hough_indexing.hough_indexing_optimize_pc(self, pc0, indexer, batch, method, **kwargs)
+
     def dictionary_indexing(self, dictionary, metric="ncc", keep_n=20, n_per_iteration=None,
                             navigation_mask=None, signal_mask=None, rechunk=False, dtype=None, *,
                             devices=None, comm=None, verbose=True, compute=None):
