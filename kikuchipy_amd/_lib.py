@@ -436,7 +436,9 @@ def _mask_bytes(mask):
 
 class _Functions:
     """`f.set_problem` -> `libkpdi.kpdi_set_problem` (prefix "kpdi_") or `kpdi_group_set_problem`
-    (prefix "kpdi_group_"): lets `Group` reuse `Context`'s methods for every call that has a group form."""
+    (prefix "kpdi_group_"): lets `Group` reuse `Context`'s methods for every call that has a group form.  A `Context`
+    method without one is named in `Group._ON_ROOT` (runs on member 0) or `Group._ONE_GPU` (refused), or `Group`
+    overrides it by hand; tests/test_host_group.py checks that every public method is one of the four."""
 
     def __init__(self, prefix):
         self._prefix = prefix
@@ -461,6 +463,10 @@ class Context:
             self._h = C.c_void_p()
             check(self._f.create(int(device), C.byref(self._h)))
         self.device = int(device)
+        self._init_state()
+
+    def _init_state(self):
+        """The Python-side state of a fresh engine, `Context` or `Group` alike."""
         self._keep = {}  # host arrays the library may still be reading
         self._keep_n = None       # what kpdi_finalize will write per pattern
         self._compute = COMPUTE_F32
@@ -532,6 +538,10 @@ class Context:
         nm = _mask_bytes(navigation_mask)
         check(self._f.set_experimental_dev(self._h, C.c_void_p(d_ptr), dtype_code(dtype), int(m_all),
                                                _ptr(nm)))
+        self._record_experimental_dev(dtype, m_all)
+
+    def _record_experimental_dev(self, dtype, m_all):
+        """What `get_experimental` allocates after a `set_experimental_dev`."""
         self._exp_shape, self._exp_dtype = (int(m_all),) + getattr(self, "_detector", (-1,)), np.dtype(dtype)
 
     @property
@@ -1102,6 +1112,23 @@ class Context:
         hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64).reshape(x0.shape)
         return nvar, x0, f, lo, hi, np.empty((n, starts, REFINE_RESULT_STRIDE), dtype=np.float64)
 
+    @staticmethod
+    def _trace_buffer(nvar, trace_job, trace_capacity):
+        """The (trace_capacity, nvar + 1) rows a traced solve fills, or None without a `trace_job`."""
+        if trace_job is None:
+            return None
+        if int(trace_capacity) < 1:
+            raise KpdiError("a trace needs trace_capacity >= 1")
+        return np.zeros((int(trace_capacity), nvar + 1), dtype=np.float64)
+
+    @staticmethod
+    def _with_trace(res, trace, trace_job):
+        """`res`, or with a trace (res, the rows of it that were stored, how many evaluations `trace_job` made: its nfev)."""
+        if trace is None:
+            return res
+        total = int(res.reshape(-1, res.shape[2])[int(trace_job), 1])
+        return res, trace[:min(total, trace.shape[0])], total
+
     def _optimiser_selftest(self, entry, n_head, kind, x0, lower, upper, xtol, ftol, maxiter, maxfev):
         """One optimiser alone on an analytic objective: `n_head` result fields, then x."""
         x0 = np.ascontiguousarray(x0, dtype=np.float64).ravel()
@@ -1132,19 +1159,11 @@ class Context:
         fun, nfev, nit, x.  With `trace_job` (= pattern * n_starts + start) also the (n_stored, nvar + 1) rows (x, f)
         of that job's evaluations, the first `trace_capacity` of them, and how many there were in all."""
         nvar, x0, f, lo, hi, res = self._solve_arrays(mode, x0, fixed, lower, upper)
-        trace = None
-        if trace_job is not None:
-            if int(trace_capacity) < 1:
-                raise KpdiError("a trace needs trace_capacity >= 1")
-            trace = np.zeros((int(trace_capacity), nvar + 1), dtype=np.float64)
+        trace = self._trace_buffer(nvar, trace_job, trace_capacity)
         check(self._f.refine_solve_powell(self._h, int(mode), x0.shape[0], x0.shape[1], _ptr(x0), _ptr(f), _ptr(lo),
                                           _ptr(hi), float(xtol), float(ftol), int(maxiter or 0), int(maxfev or 0), _ptr(res),
-                                          int(trace_job or 0), _ptr(trace), int(trace_capacity) if trace is not None else 0))
-        res = res[:, :, :3 + nvar]
-        if trace is None:
-            return res
-        total = int(res.reshape(-1, 3 + nvar)[int(trace_job), 1])
-        return res, trace[:min(total, trace.shape[0])], total
+                                          int(trace_job or 0), _ptr(trace), 0 if trace is None else trace.shape[0]))
+        return self._with_trace(res[:, :, :3 + nvar], trace, trace_job)
 
     def powell_selftest(self, kind, x0, lower=None, upper=None, xtol=1e-4, ftol=1e-4, maxiter=0, maxfev=0):
         """csrc/powell.h alone on an analytic objective (kpdi_powell_selftest): fun, nfev, nit, status, x."""
@@ -1197,20 +1216,12 @@ class Context:
         n_jobs = lo.shape[0] * lo.shape[1]
         seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32).ravel(), (n_jobs,)))
         m_lo, m_hi = self._de_mutation(mutation)
-        trace = None
-        if trace_job is not None:
-            if int(trace_capacity) < 1:
-                raise KpdiError("a trace needs trace_capacity >= 1")
-            trace = np.zeros((int(trace_capacity), nvar + 1), dtype=np.float64)
+        trace = self._trace_buffer(nvar, trace_job, trace_capacity)
         check(self._f.refine_solve_de(self._h, int(mode), lo.shape[0], lo.shape[1], _ptr(f), _ptr(lo), _ptr(hi), int(members),
                                       int(maxiter), float(tol), float(atol), m_lo, m_hi, float(recombination), int(init),
                                       int(updating), _ptr(seeds), _ptr(res), int(trace_job or 0), _ptr(trace),
-                                      int(trace_capacity) if trace is not None else 0))
-        res = res[:, :, :3 + nvar]
-        if trace is None:
-            return res
-        total = int(res.reshape(-1, 3 + nvar)[int(trace_job), 1])
-        return res, trace[:min(total, trace.shape[0])], total
+                                      0 if trace is None else trace.shape[0]))
+        return self._with_trace(res[:, :, :3 + nvar], trace, trace_job)
 
     def de_selftest(self, kind, lower, upper, members, maxiter=1000, tol=0.01, atol=0.0, mutation=(0.5, 1.0),
                     recombination=0.7, init=0, updating=0, seed=0):
@@ -1666,11 +1677,30 @@ class Group(Context):
     `finalize()` returns the one merged result.  One Python thread drives it; the members' host
     work runs on the library's own threads.
 
+    A `Context` method does one of three things here.  With a group form of every symbol it calls it is inherited
+    and runs on all members (`self._f.X` is `kpdi_group_X`), unless the class overrides it by hand.  Named in
+    `_ON_ROOT` it runs on member 0.  Named in `_ONE_GPU` it raises `KpdiError`: use `group.members[i]`.
+
     gather: None (automatic: RCCL when the devices are distinct, peer copies otherwise,
     $KPDI_GATHER overrides), "rccl" or "p2p"."""
 
     _prefix = "kpdi_group_"
     _GATHER = {None: GATHER_AUTO, "auto": GATHER_AUTO, "rccl": GATHER_RCCL, "p2p": GATHER_P2P}
+    # calls without a group form that run on member 0: every member holds the same patterns and master pattern, and the
+    # merged lists of the last finalize live there
+    _ON_ROOT = ("get_direction_cosines", "project_patterns", "project_patterns_varying_pc", "refine_set_patterns",
+                "refine_get_prepared", "refine_objective", "refine_solve", "nelder_mead_selftest", "refine_solve_powell",
+                "powell_selftest", "refine_solve_nlopt", "nlopt_simplex_selftest", "refine_solve_de", "de_selftest",
+                "mt19937_selftest", "orientation_similarity_map", "kinematical_master_pattern", "sample_fundamental",
+                "orientation_pairs", "orientation_outer", "orientation_reduce", "orientation_kam", "geometrical_visibility",
+                "geometrical_coordinates")
+    # calls that belong to one GPU (its resident patterns, its device buffers) or to one rank: refused on a group
+    _ONE_GPU = ("image_quality", "region_sums", "reduce", "fft_filter", "rescale_intensity", "normalize_intensity",
+                "intensity_range", "adaptive_histogram_equalization", "downsample", "get_dynamic_background", "change_dtype",
+                "select_patterns", "set_navigation_mask", "decomposition_gram", "decomposition_apply", "decomposition_model",
+                "hough_bands", "hough_index", "average_neighbour_patterns", "neighbour_dot_products", "merge_selftest",
+                "merge64_selftest", "rescore_selftest", "fill_selftest", "comm_selftest", "comm_drop", "export_lists",
+                "import_lists", "dev_alloc", "dev_free", "h2d", "d2h", "comm_init")
 
     def __init__(self, devices="all", gather=None):
         ids = resolve_devices(devices)
@@ -1685,14 +1715,8 @@ class Group(Context):
         self.device = ids[0]
         self.members = [Context(d, _borrowed=self._f.member(self._h, i)) for i, d in enumerate(ids)]
         self.root = self.members[0]
-        self._keep = {}
+        self._init_state()
         self._borrowed = []  # (ticket, array): host chunks the members' uploads may still be reading
-        self._host_gather = None
-        self._keep_n = None
-        self._compute = COMPUTE_F32
-        self._projection_key = None
-        self.result_token = 0
-        self._last_valid = False
 
     def __len__(self):
         return len(self.devices)
@@ -1820,6 +1844,7 @@ class Group(Context):
         nm = _mask_bytes(navigation_mask)
         arr = (C.c_void_p * len(d_ptrs))(*[int(p) for p in d_ptrs])
         check(self._f.set_experimental_dev(self._h, arr, dtype_code(dtype), int(m_all), _ptr(nm)))
+        self._record_experimental_dev(dtype, m_all)
 
     def push_dictionary_chunk_dev(self, d_ptrs, dtype, n_chunk, global_start):
         """One device chunk per member: d_ptrs[i], n_chunk[i] patterns (0 = none), first dictionary
@@ -1847,14 +1872,6 @@ class Group(Context):
         super().set_detector(gnomonic_bounds, pcz, nrows, ncols, om_detector_to_sample)
         self.root._dc_npix = self._dc_npix
 
-    # -- calls without a group form run on member 0 (every member holds the same patterns / master pattern; the merged
-    # lists of the last finalize live there)
-    def get_direction_cosines(self):
-        return self.root.get_direction_cosines()
-
-    def project_patterns(self, *args, **kwargs):
-        return self.root.project_patterns(*args, **kwargs)
-
     def push_rotations_chunk_varying_pc(self, rotations, pcs, global_start, om_detector_to_sample, rescale=False,
                                         out_min=-1.0, out_max=1.0):
         """One contiguous block of the chunk per member (the members' queues are joined first: this path drives the member
@@ -1867,83 +1884,9 @@ class Group(Context):
             if b > a:
                 m.push_rotations_chunk_varying_pc(rot[a:b], pc[a:b], global_start + a, om_detector_to_sample, rescale, out_min, out_max)
 
-    def project_patterns_varying_pc(self, *args, **kwargs):
-        return self.root.project_patterns_varying_pc(*args, **kwargs)
-
-    def refine_set_patterns(self, *args, **kwargs):
-        return self.root.refine_set_patterns(*args, **kwargs)
-
-    def refine_get_prepared(self):
-        return self.root.refine_get_prepared()
-
-    def refine_objective(self, *args, **kwargs):
-        return self.root.refine_objective(*args, **kwargs)
-
-    def refine_solve(self, *args, **kwargs):
-        return self.root.refine_solve(*args, **kwargs)
-
-    def nelder_mead_selftest(self, *args, **kwargs):
-        return self.root.nelder_mead_selftest(*args, **kwargs)
-
-    def refine_solve_powell(self, *args, **kwargs):
-        return self.root.refine_solve_powell(*args, **kwargs)
-
-    def powell_selftest(self, *args, **kwargs):
-        return self.root.powell_selftest(*args, **kwargs)
-
-    def refine_solve_nlopt(self, *args, **kwargs):
-        return self.root.refine_solve_nlopt(*args, **kwargs)
-
-    def nlopt_simplex_selftest(self, *args, **kwargs):
-        return self.root.nlopt_simplex_selftest(*args, **kwargs)
-
-    def refine_solve_de(self, *args, **kwargs):
-        return self.root.refine_solve_de(*args, **kwargs)
-
-    def de_selftest(self, *args, **kwargs):
-        return self.root.de_selftest(*args, **kwargs)
-
-    def mt19937_selftest(self, *args, **kwargs):
-        return self.root.mt19937_selftest(*args, **kwargs)
-
-    def orientation_similarity_map(self, *args, **kwargs):
-        return self.root.orientation_similarity_map(*args, **kwargs)
-
-    def kinematical_master_pattern(self, *args, **kwargs):
-        return self.root.kinematical_master_pattern(*args, **kwargs)
-
-    def sample_fundamental(self, *args, **kwargs):
-        return self.root.sample_fundamental(*args, **kwargs)
-
-    def orientation_pairs(self, *args, **kwargs):
-        return self.root.orientation_pairs(*args, **kwargs)
-
-    def orientation_outer(self, *args, **kwargs):
-        return self.root.orientation_outer(*args, **kwargs)
-
-    def orientation_reduce(self, *args, **kwargs):
-        return self.root.orientation_reduce(*args, **kwargs)
-
-    def orientation_kam(self, *args, **kwargs):
-        return self.root.orientation_kam(*args, **kwargs)
-
-    def geometrical_visibility(self, *args, **kwargs):
-        return self.root.geometrical_visibility(*args, **kwargs)
-
-    def geometrical_coordinates(self, *args, **kwargs):
-        return self.root.geometrical_coordinates(*args, **kwargs)
-
     def holds_result(self, simulation_indices):
         self.root._last_valid = self._last_valid
         return self.root.holds_result(simulation_indices)
-
-    def comm_init(self, rank, nranks, unique_id):
-        raise KpdiError("a Group gathers inside one process; ranks of a multi-process job attach a Context each")
-
-    def dev_alloc(self, nbytes):
-        raise KpdiError("device buffers belong to one GPU: use group.members[i].dev_alloc()")
-
-    dev_free = h2d = d2h = dev_alloc
 
     # -- measurement
     def counters(self):
@@ -1953,3 +1896,26 @@ class Group(Context):
         out["members"] = per
         out["gather"] = self.gather
         return out
+
+
+def _on_root(name):
+    def method(self, *args, **kwargs):
+        return getattr(self.root, name)(*args, **kwargs)
+    return method
+
+
+def _one_gpu(name):
+    def method(self, *args, **kwargs):
+        if name == "comm_init":
+            raise KpdiError("comm_init: a Group gathers inside one process; ranks of a multi-process job attach a "
+                            "Context each (group.members[i] is one)")
+        raise KpdiError(f"{name} works on one GPU's own state or buffers and has no group form: use "
+                        f"group.members[i].{name}(...)")
+    return method
+
+
+for _make, _names in ((_on_root, Group._ON_ROOT), (_one_gpu, Group._ONE_GPU)):
+    for _name in _names:
+        _method = _make(_name)
+        _method.__name__, _method.__doc__ = _name, getattr(Context, _name).__doc__
+        setattr(Group, _name, _method)

@@ -493,3 +493,31 @@ def test_a_held_chunk_larger_than_the_announced_dictionary_keeps_every_row():
         g.sweep_held()
         got = g.finalize(10)
     assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+
+
+def test_a_group_runs_member_0_calls_and_refuses_one_gpu_calls_cleanly():
+    """`Group._ON_ROOT` calls give member 0's bits, which are a single context's; a `Group._ONE_GPU` call is refused on
+    entry with the library's own error type and leaves the group as it was: the sweep after it is the single sweep."""
+    from kikuchipy_amd import _lib, sampling
+
+    faces, ops = sampling.fundamental_zone_faces("432"), sampling.rotation_group_operations("432")
+    rng = np.random.default_rng(33)
+    q = rng.standard_normal((37, 4))
+    q /= np.linalg.norm(q, axis=1)[:, None]
+    exp, dic = patterns(5, 6, (8, 8), np.uint8), patterns(6, 16, (8, 8))
+    with _lib.Context(0) as c, _lib.Group([0, 0]) as g:
+        want = c.sample_fundamental(5, faces)
+        got = g.sample_fundamental(5, faces)
+        assert 0 < len(want) < 11 ** 3 and got.dtype == want.dtype and np.array_equal(got, want)
+        for a, b in zip(g.orientation_reduce(q, ops), c.orientation_reduce(q, ops)):
+            assert a.dtype == b.dtype and np.array_equal(a, b)
+        for e in (c, g):
+            e.set_problem(8, 8, None, _lib.METRIC_NCC, 3)
+            e.set_experimental(exp)
+        with pytest.raises(_lib.KpdiError, match=r"fft_filter.*members\[i\]\.fft_filter"):
+            g.fft_filter(_lib.DOMAIN_FREQUENCY, np.ones((8, 5), dtype=np.complex64))
+        assert np.array_equal(g.get_experimental(), exp)  # untouched
+        for e in (c, g):
+            e.push_dictionary_chunk(dic, 0)
+        (s1, i1), (s2, i2) = c.finalize(), g.finalize()
+    assert s1.shape == (6, 3) and np.array_equal(s1, s2) and np.array_equal(i1, i2)
