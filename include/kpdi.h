@@ -781,6 +781,25 @@ int kpdi_refine_solve_de(kpdi_ctx *ctx, int mode, int64_t n_patterns, int n_star
 int kpdi_de_selftest(kpdi_ctx *ctx, int kind, int nvar, const double *lower, const double *upper, int members,
                      int maxiter, double tol, double atol, double mutation_lo, double mutation_hi,
                      double recombination, int init, int updating, uint32_t seed, double *result);
+/* scipy.optimize.basinhopping of SciPy 1.15.3 around minimize(method="Nelder-Mead"), with the default step and the
+ * default (Metropolis) acceptance test (csrc/basinhopping.h), from every start of every pattern, each from
+ * numpy.random.RandomState(seeds[job]).  Unbounded.  niter >= 0 hops after the initial quench; T: the temperature (0:
+ * no uphill hop is taken); stepsize finite; interval >= 1; niter_success < 0: SciPy's None (niter + 2);
+ * target_accept_rate and stepwise_factor within (0, 1); a NaN among the options is refused.  xatol / fatol / maxiter /
+ * maxfev: the options of every quench, as kpdi_refine_solve takes them.  seeds: one per job, n_patterns x n_starts.
+ * Result rows and trace as kpdi_refine_solve_powell: fun and x of the lowest result, nfev the sum over all quenches
+ * (the initial one included), nit. */
+int kpdi_refine_solve_basinhopping(kpdi_ctx *ctx, int mode, int64_t n_patterns, int n_starts, const double *x0,
+                                   const double *fixed, int niter, double T, double stepsize, int interval,
+                                   int niter_success, double target_accept_rate, double stepwise_factor,
+                                   double xatol, double fatol, int maxiter, int maxfev, const uint32_t *seeds,
+                                   double *results, int64_t trace_job, double *trace, int trace_capacity);
+/* csrc/basinhopping.h alone on an analytic f64 objective, nvar <= 6: kinds 0..4 of kpdi_powell_selftest.  Options as
+ * kpdi_refine_solve_basinhopping.  result: fun, nfev, nit, success (1 | 0), minimization_failures, x[0..nvar). */
+int kpdi_basinhopping_selftest(kpdi_ctx *ctx, int kind, int nvar, const double *x0, int niter, double T,
+                               double stepsize, int interval, int niter_success, double target_accept_rate,
+                               double stepwise_factor, double xatol, double fatol, int maxiter, int maxfev,
+                               uint32_t seed, double *result);
 /* The random stream of csrc/differential_evolution.h alone, from numpy.random.RandomState(seed): `program` holds n
  * rows (op, a, b) of doubles - 0: uniform(), 1: uniform(a, b), 2: randint(0, a) with 1 <= a < 2^31, 3: shuffle of a
  * persistent arange(a) (made anew when a changes), 4: permutation(range(a)); a <= KPDI_DE_POP_MAX for 3 and 4.

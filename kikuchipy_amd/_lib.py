@@ -209,6 +209,10 @@ SIGNATURES = {
                                   C.c_double, _i, _i, _vp, _vp, _i64, _vp, _i]),
     "kpdi_de_selftest": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                               _i, _i, C.c_uint32, _vp]),
+    "kpdi_refine_solve_basinhopping": (_i, [_vp, _i, _i64, _i, _vp, _vp, _i, C.c_double, C.c_double, _i, _i, C.c_double,
+                                            C.c_double, C.c_double, C.c_double, _i, _i, _vp, _vp, _i64, _vp, _i]),
+    "kpdi_basinhopping_selftest": (_i, [_vp, _i, _i, _vp, _i, C.c_double, C.c_double, _i, _i, C.c_double, C.c_double,
+                                        C.c_double, C.c_double, _i, _i, C.c_uint32, _vp]),
     "kpdi_mt19937_selftest": (_i, [_vp, C.c_uint32, _vp, _i, _vp, _i64]),
     "kpdi_merge_selftest": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.c_uint32,
                                  _vp, _vp, _i, _vp, _vp]),
@@ -1237,6 +1241,40 @@ class Context:
                                   _ptr(res)))
         return res
 
+    def refine_solve_basinhopping(self, mode, x0, fixed=None, niter=100, T=1.0, stepsize=0.5, interval=50,
+                                  niter_success=None, target_accept_rate=0.5, stepwise_factor=0.9, xatol=1e-4, fatol=1e-4,
+                                  maxiter=0, maxfev=0, seeds=0, trace_job=None, trace_capacity=0):
+        """`scipy.optimize.basinhopping` around `minimize(method="Nelder-Mead")` from every start on the device
+        (kpdi_refine_solve_basinhopping), job j from `numpy.random.RandomState(seeds[j])`, unbounded.  x0: (n_patterns,
+        n_starts, nvar); niter_success None: niter + 2; xatol, fatol, maxiter, maxfev: the options of every quench
+        (None or 0: SciPy's budget rule); seeds: one integer for every job or one per job.  Returns the (n_patterns,
+        n_starts, 3 + nvar) rows fun, nfev, nit, x of the lowest result, and with `trace_job` the trace as
+        `refine_solve_powell`."""
+        nvar, x0, f, _, _, res = self._solve_arrays(mode, x0, fixed, None, None)
+        n_jobs = x0.shape[0] * x0.shape[1]
+        seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint32).ravel(), (n_jobs,)))
+        trace = self._trace_buffer(nvar, trace_job, trace_capacity)
+        check(self._f.refine_solve_basinhopping(self._h, int(mode), x0.shape[0], x0.shape[1], _ptr(x0), _ptr(f), int(niter),
+                                                float(T), float(stepsize), int(interval),
+                                                -1 if niter_success is None else int(niter_success),
+                                                float(target_accept_rate), float(stepwise_factor), float(xatol),
+                                                float(fatol), int(maxiter or 0), int(maxfev or 0), _ptr(seeds), _ptr(res),
+                                                int(trace_job or 0), _ptr(trace), 0 if trace is None else trace.shape[0]))
+        return self._with_trace(res[:, :, :3 + nvar], trace, trace_job)
+
+    def basinhopping_selftest(self, kind, x0, niter=100, T=1.0, stepsize=0.5, interval=50, niter_success=None,
+                              target_accept_rate=0.5, stepwise_factor=0.9, xatol=1e-4, fatol=1e-4, maxiter=0, maxfev=0,
+                              seed=0):
+        """csrc/basinhopping.h alone on an analytic objective (kpdi_basinhopping_selftest): fun, nfev, nit, success,
+        minimization_failures, x."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).ravel()
+        res = np.empty(5 + x0.size, dtype=np.float64)
+        check(self._f.basinhopping_selftest(self._h, int(kind), x0.size, _ptr(x0), int(niter), float(T), float(stepsize),
+                                            int(interval), -1 if niter_success is None else int(niter_success),
+                                            float(target_accept_rate), float(stepwise_factor), float(xatol), float(fatol),
+                                            int(maxiter or 0), int(maxfev or 0), int(seed), _ptr(res)))
+        return res
+
     def mt19937_selftest(self, seed, program):
         """The random stream of csrc/differential_evolution.h alone (kpdi_mt19937_selftest).  program: rows (op, a, b) -
         0: uniform(), 1: uniform(a, b), 2: randint(0, a), 3: shuffle of a persistent arange(a), 4: permutation(range(a)).
@@ -1888,6 +1926,13 @@ class Group(Context):
         self.root._last_valid = self._last_valid
         return self.root.holds_result(simulation_indices)
 
+    # the two calls of the basinhopping solver have no group form and run on member 0, like the calls of `_ON_ROOT`
+    def refine_solve_basinhopping(self, *args, **kwargs):
+        return self.root.refine_solve_basinhopping(*args, **kwargs)
+
+    def basinhopping_selftest(self, *args, **kwargs):
+        return self.root.basinhopping_selftest(*args, **kwargs)
+
     # -- measurement
     def counters(self):
         """Member 0's counters (its merge / gather figures are the group's) + `members`: every member's."""
@@ -1919,3 +1964,5 @@ for _make, _names in ((_on_root, Group._ON_ROOT), (_one_gpu, Group._ONE_GPU)):
         _method = _make(_name)
         _method.__name__, _method.__doc__ = _name, getattr(Context, _name).__doc__
         setattr(Group, _name, _method)
+for _name in ("refine_solve_basinhopping", "basinhopping_selftest"):
+    getattr(Group, _name).__doc__ = getattr(Context, _name).__doc__

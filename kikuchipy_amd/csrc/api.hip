@@ -202,7 +202,7 @@ void set_detector_layout(kpdi_ctx *c, int sy, int sx, bool have_mask, std::vecto
 
 extern "C" {
 
-const char *kpdi_version(void) { return "kpdi 0.18.0 (gfx950)"; }
+const char *kpdi_version(void) { return "kpdi 0.19.0 (gfx950)"; }
 
 size_t kpdi_counters_size(void) { return sizeof(kpdi_counters); }
 

@@ -392,6 +392,24 @@ int de_check_options(const kpdi::DeOptions &de) {
   return KPDI_OK;
 }
 
+// SciPy's own validation of the options the device solver takes (scipy/optimize/_basinhopping.py:644-647) and what
+// would not end or not run there: an interval of 0 divides by zero, `range` of a negative niter is empty (refused here
+// rather than guessed), a NaN among the options
+int bh_check_options(const kpdi::BhOptions &bh, double xatol, double fatol) {
+  if (bh.niter < 0) return fail(KPDI_EINVAL, "basinhopping - niter must not be negative");
+  if (bh.interval < 1) return fail(KPDI_EINVAL, "basinhopping - interval must be at least 1");
+  if (std::isnan(bh.T) || std::isnan(bh.stepsize) || std::isnan(bh.target_accept_rate) || std::isnan(bh.stepwise_factor) ||
+      std::isnan(xatol) || std::isnan(fatol))
+    return fail(KPDI_EINVAL, "basinhopping - an option is NaN");
+  if (!std::isfinite(bh.stepsize) || !std::isfinite(2.0 * bh.stepsize))
+    return fail(KPDI_EINVAL, "basinhopping - stepsize must be finite, and twice it too");
+  if (!(bh.target_accept_rate > 0.0 && bh.target_accept_rate < 1.0))
+    return fail(KPDI_EINVAL, "basinhopping - target_accept_rate has to be in range (0, 1)");
+  if (!(bh.stepwise_factor > 0.0 && bh.stepwise_factor < 1.0))
+    return fail(KPDI_EINVAL, "basinhopping - stepwise_factor has to be in range (0, 1)");
+  return KPDI_OK;
+}
+
 int de_check_bounds(const double *lower, const double *upper, size_t count) {
   for (size_t i = 0; i < count; ++i) {
     if (!std::isfinite(lower[i]) || !std::isfinite(upper[i]))
@@ -415,8 +433,9 @@ struct RefineSolver {
 int refine_solve(kpdi_ctx *c, const RefineSolver &solver, int mode, int64_t n_patterns, int n_starts, const double *x0,
                  const double *fixed, const double *lower, const double *upper, double xtol, double ftol, int maxiter,
                  int maxfev, double *results, int64_t trace_job, double *trace, int trace_capacity,
-                 const kpdi::NloptStep *xstep = nullptr, const kpdi::DeOptions *de = nullptr) {
-  // de: differential evolution - no x0, `de->seeds` one seed per job on the HOST
+                 const kpdi::NloptStep *xstep = nullptr, const kpdi::DeOptions *de = nullptr,
+                 const kpdi::BhOptions *bh = nullptr) {
+  // de: differential evolution - no x0, `de->seeds` one seed per job on the HOST; bh: basinhopping - `bh->seeds` alike
   if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
   if ((!x0 && !de) || !results) return fail(KPDI_EINVAL, "NULL argument");
   if ((lower == nullptr) != (upper == nullptr)) return fail(KPDI_EINVAL, "give both bounds or neither");
@@ -450,11 +469,17 @@ int refine_solve(kpdi_ctx *c, const RefineSolver &solver, int mode, int64_t n_pa
     HIPCHK(hipMemcpyAsync(d_lo, lower, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_hi, upper, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
   }
-  if (de) {
-    a.de = *de;
+  if (de || bh) {
     HIPCHK(c->ref_idx.reserve((size_t)jobs * sizeof(uint32_t)));
-    HIPCHK(hipMemcpyAsync(c->ref_idx.p, de->seeds, (size_t)jobs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    a.de.seeds = c->ref_idx.as<uint32_t>();
+    HIPCHK(hipMemcpyAsync(c->ref_idx.p, de ? de->seeds : bh->seeds, (size_t)jobs * sizeof(uint32_t),
+                          hipMemcpyHostToDevice, c->stream));
+    if (de) {
+      a.de = *de;
+      a.de.seeds = c->ref_idx.as<uint32_t>();
+    } else {
+      a.bh = *bh;
+      a.bh.seeds = c->ref_idx.as<uint32_t>();
+    }
   }
   HIPCHK(hipMemsetAsync(c->ref_out.p, 0, (result_doubles + trace_doubles) * sizeof(double), c->stream));
   a.n_jobs = jobs;
@@ -636,6 +661,43 @@ int kpdi_de_selftest(kpdi_ctx *c, int kind, int nvar, const double *lower, const
   if (rc) return rc;
   HIPCHK(kpdi::launch_de_selftest(kind, nvar, in.lo, in.hi, de, seed, c->ref_out.as<double>(), c->stream));
   return selftest_download(c, result, 4 + nvar);
+}
+
+int kpdi_refine_solve_basinhopping(kpdi_ctx *c, int mode, int64_t n_patterns, int n_starts, const double *x0,
+                                   const double *fixed, int niter, double T, double stepsize, int interval,
+                                   int niter_success, double target_accept_rate, double stepwise_factor, double xatol,
+                                   double fatol, int maxiter, int maxfev, const uint32_t *seeds, double *results,
+                                   int64_t trace_job, double *trace, int trace_capacity) {
+  // unbounded: check_bounds is never called
+  static const RefineSolver basinhopping = {nelder_mead_check_bounds, resolve_budget,
+                                            kpdi::launch_refine_solve_basinhopping};
+  if (!x0 || !seeds) return fail(KPDI_EINVAL, "NULL argument (starts and seeds are required)");
+  const kpdi::BhOptions bh{niter, interval, niter_success, T, stepsize, target_accept_rate, stepwise_factor, seeds};
+  int rc = bh_check_options(bh, xatol, fatol);
+  if (rc) return rc;
+  return refine_solve(c, basinhopping, mode, n_patterns, n_starts, x0, fixed, nullptr, nullptr, xatol, fatol, maxiter,
+                      maxfev, results, trace_job, trace, trace_capacity, nullptr, nullptr, &bh);
+}
+
+int kpdi_basinhopping_selftest(kpdi_ctx *c, int kind, int nvar, const double *x0, int niter, double T, double stepsize,
+                               int interval, int niter_success, double target_accept_rate, double stepwise_factor,
+                               double xatol, double fatol, int maxiter, int maxfev, uint32_t seed, double *result) {
+  if (!c || !x0 || !result) return fail(KPDI_EINVAL, "NULL argument");
+  if (kind < 0 || kind > 4) return fail(KPDI_EINVAL, "kind must be within 0..4");
+  if (nvar < 1 || nvar > 6) return fail(KPDI_EINVAL, "nvar must be within 1..6");
+  const kpdi::BhOptions bh{niter, interval, niter_success, T, stepsize, target_accept_rate, stepwise_factor, nullptr};
+  int rc = bh_check_options(bh, xatol, fatol);
+  if (rc) return rc;
+  rc = use_device(c);
+  if (rc) return rc;
+  SelftestIn in;
+  rc = selftest_upload(c, nvar, x0, nullptr, nullptr, 5 + nvar, &in);
+  if (rc) return rc;
+  int it, fev;
+  resolve_budget(nvar, maxiter, maxfev, &it, &fev);
+  HIPCHK(kpdi::launch_basinhopping_selftest(kind, nvar, in.x, bh, xatol, fatol, it, fev, seed, c->ref_out.as<double>(),
+                                            c->stream));
+  return selftest_download(c, result, 5 + nvar);
 }
 
 int kpdi_mt19937_selftest(kpdi_ctx *c, uint32_t seed, const double *program, int n, uint64_t *out, int64_t out_words) {

@@ -328,6 +328,11 @@ struct DeOptions {  // differential evolution (differential_evolution.h)
   double tol, atol, mutation_lo, mutation_hi, recombination;  // mutation_hi = NaN: `mutation` is one number
   const uint32_t *seeds;  // [n_jobs] on the device (launch_refine_solve_de only)
 };
+struct BhOptions {  // basinhopping around Nelder-Mead (basinhopping.h)
+  int niter, interval, niter_success;  // niter_success < 0: SciPy's None (niter + 2)
+  double T, stepsize, target_accept_rate, stepwise_factor;
+  const uint32_t *seeds;  // [n_jobs] on the device (launch_refine_solve_basinhopping only)
+};
 struct RefineLaunch {
   int mode, nvar, nfixed, n_starts;
   int64_t n_jobs;        // solve: patterns * starts; objective: evaluations
@@ -345,6 +350,7 @@ struct RefineLaunch {
   int maxiter, maxfun;
   NloptStep xstep;              // launch_refine_solve_nlopt only
   DeOptions de;                 // launch_refine_solve_de only
+  BhOptions bh;                 // launch_refine_solve_basinhopping only
   double *results;              // [n_jobs][REFINE_RESULT_STRIDE]: fun, nfev, nit, x[nvar]
 };
 constexpr int REFINE_RESULT_STRIDE = 9;
@@ -372,6 +378,14 @@ hipError_t launch_refine_solve_de(const RefineLaunch &a, int64_t trace_job, doub
 // result: fun, nfev, nit, success, x[0..nvar)
 hipError_t launch_de_selftest(int kind, int nvar, const double *lower, const double *upper, const DeOptions &de,
                               unsigned seed, double *result, hipStream_t s);
+// SciPy's basinhopping around Nelder-Mead (basinhopping.h): a.bh, a.xatol / a.fatol / a.maxiter / a.maxfun the
+// quench's (the resolved budget), no bounds; trace as for Powell
+hipError_t launch_refine_solve_basinhopping(const RefineLaunch &a, int64_t trace_job, double *trace, int trace_capacity,
+                                            hipStream_t s);
+// kinds 0..4.  result: fun, nfev, nit, success, minimization_failures, x[0..nvar)
+hipError_t launch_basinhopping_selftest(int kind, int nvar, const double *x0, const BhOptions &bh, double xatol,
+                                        double fatol, int maxiter, int maxfun, unsigned seed, double *result,
+                                        hipStream_t s);
 // out: capacity + 1 words, the last one the number of words the program makes
 hipError_t launch_mt19937_selftest(unsigned seed, const double *program, int n, uint64_t *out, long long capacity,
                                    hipStream_t s);

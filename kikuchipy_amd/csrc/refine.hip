@@ -12,11 +12,12 @@
 //   powell.h                  scipy.optimize.minimize(method="Powell")
 //   nlopt_simplex.h           the search NLopt offers as LN_NELDERMEAD, from the text of DESIGN.md section 21
 //   differential_evolution.h  scipy.optimize.differential_evolution, strategy="best1bin", NumPy's legacy RandomState
+//   basinhopping.h            scipy.optimize.basinhopping around the Nelder-Mead above, on the same RandomState
 // Every other optimiser stays on the host and calls `refine_objective_kernel`.
 //
 // One workgroup per (experimental pattern, start) runs the WHOLE optimisation.  In
-// `refine_solve_kernel` thread 0 owns the simplex (LDS) and decides the next point; in the
-// other three solve kernels every thread runs the optimiser on the same values.  All 256
+// `refine_solve_kernel` and `refine_solve_basinhopping_kernel` thread 0 owns the search (LDS) and decides the next
+// point; in the other three solve kernels every thread runs the optimiser on the same values.  All 256
 // threads evaluate the objective (each pixel: direction cosine for the current PC -> rotate
 // -> Lambert -> one 16-byte master-pattern gather -> float32 value; three f64 block sums give
 // the NCC).  No host round trip and no kernel launch per evaluation: a refinement of M
@@ -32,6 +33,7 @@
 #include <climits>
 
 #include "analytic_objectives.h"
+#include "basinhopping.h"
 #include "differential_evolution.h"
 #include "nelder_mead.h"
 #include "nlopt_simplex.h"
@@ -429,6 +431,58 @@ __global__ void de_selftest_kernel(int kind, int nvar, const double *lower, cons
                         nvar);
 }
 
+// ---- SciPy's basinhopping around Nelder-Mead (basinhopping.h) on the device, run like `refine_solve_kernel`: thread 0
+// owns the search - the hops, the quench that runs, the lowest result - and the random stream, both in LDS (the 624
+// words of the stream where the differential evolution keeps them), and decides the next point; all 256 threads
+// evaluate it through `RefineEval`.  Unbounded: the reference's basinhopping takes no trust region.
+// LDS: BasinHopping<6> (the simplex of the quench and three points, ~1 KiB) + 2500 B (stream) + `red`.
+// result row: fun, nfev, nit, x of the lowest result
+using BhState = BasinHopping<NV_MAX>;
+
+__global__ __launch_bounds__(REF_THREADS, 4) void refine_solve_basinhopping_kernel(
+    int mode, int nvar, int nfixed, int n_starts, const double *x0, const double *fixed, RefineGeom g,
+    const float *patterns, const double *sqnorm, BhOptions opt, double xatol, double fatol, int maxiter, int maxfun,
+    double *results, long long trace_job, double *trace, int trace_capacity) {
+  __shared__ BhState bh;
+  __shared__ Mt19937 mt;
+  __shared__ double red[3 * REF_THREADS / 64];
+  const int64_t job = blockIdx.x;  // (pattern, start)
+  RefineEval ev = RefineEval::of_job(mode, nvar, nfixed, n_starts, fixed, g, patterns, sqnorm, red, trace_job, trace,
+                                     trace_capacity);
+  if (threadIdx.x == 0) {
+    mt_seed(mt, opt.seeds[job]);
+    bh.begin(mt, nvar, x0 + job * nvar, opt.niter, opt.T, opt.stepsize, opt.interval, (long long)opt.niter_success,
+             opt.target_accept_rate, opt.stepwise_factor, xatol, fatol, maxiter, maxfun);
+  }
+  __syncthreads();
+  while (bh.state != BhState::S_DONE) {
+    const double f = ev.eval(bh.xeval());
+    __syncthreads();  // every thread has read the point and the state
+    if (threadIdx.x == 0) bh.feed(mt, f);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) write_result(results, job, bh.fun, (double)bh.nfev, (double)bh.nit, bh.xbest, nvar);
+}
+
+// basinhopping.h alone, kinds 0..4.  result: fun, nfev, nit, success, minimization_failures, x[0..nvar)
+__global__ void basinhopping_selftest_kernel(int kind, int nvar, const double *x0, BhOptions opt, double xatol,
+                                             double fatol, int maxiter, int maxfun, unsigned seed, double *result) {
+  __shared__ BhState bh;
+  __shared__ Mt19937 mt;
+  if (threadIdx.x != 0) return;
+  const AnalyticObjective ev{kind, nvar};
+  mt_seed(mt, seed);
+  bh.begin(mt, nvar, x0, opt.niter, opt.T, opt.stepsize, opt.interval, (long long)opt.niter_success,
+           opt.target_accept_rate, opt.stepwise_factor, xatol, fatol, maxiter, maxfun);
+  while (bh.state != BhState::S_DONE) bh.feed(mt, ev.eval(bh.xeval()));
+  result[0] = bh.fun;
+  result[1] = (double)bh.nfev;
+  result[2] = (double)bh.nit;
+  result[3] = bh.success ? 1.0 : 0.0;
+  result[4] = (double)bh.minimization_failures;
+  for (int i = 0; i < nvar; ++i) result[5 + i] = bh.xbest[i];
+}
+
 // the random stream alone: `mt_program` from RandomState(seed); out[0..capacity) the words, out[capacity] their count
 __global__ void mt19937_selftest_kernel(unsigned seed, const double *program, int n, unsigned long long *out,
                                         long long capacity) {
@@ -543,6 +597,28 @@ hipError_t launch_de_selftest(int kind, int nvar, const double *lower, const dou
                               unsigned seed, double *result, hipStream_t s) {
   if (de.members < 5 || de.members > DE_POP_MAX || nvar < 1 || nvar > NV_MAX) return hipErrorInvalidValue;
   hipLaunchKernelGGL(de_selftest_kernel, dim3(1), dim3(64), 0, s, kind, nvar, lower, upper, de, seed, result);
+  return hipGetLastError();
+}
+
+// a.bh: the options and the device array of one seed per job; the quench's budget is resolved (both >= 1)
+hipError_t launch_refine_solve_basinhopping(const RefineLaunch &a, int64_t trace_job, double *trace, int trace_capacity,
+                                            hipStream_t s) {
+  if (a.n_jobs <= 0) return hipSuccess;
+  if (a.bh.niter < 0 || a.bh.interval < 1 || a.maxiter < 1 || a.maxfun < 1 || !a.x0 || !a.bh.seeds)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(refine_solve_basinhopping_kernel, dim3((unsigned)a.n_jobs), dim3(REF_THREADS), 0, s, a.mode, a.nvar,
+                     a.nfixed, a.n_starts, a.x0, a.fixed, make_geom(a), a.patterns, a.sqnorm, a.bh, a.xatol, a.fatol,
+                     a.maxiter, a.maxfun, a.results, (long long)trace_job, trace, trace_capacity);
+  return hipGetLastError();
+}
+
+hipError_t launch_basinhopping_selftest(int kind, int nvar, const double *x0, const BhOptions &bh, double xatol,
+                                        double fatol, int maxiter, int maxfun, unsigned seed, double *result,
+                                        hipStream_t s) {
+  if (bh.niter < 0 || bh.interval < 1 || maxiter < 1 || maxfun < 1 || nvar < 1 || nvar > NV_MAX)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(basinhopping_selftest_kernel, dim3(1), dim3(64), 0, s, kind, nvar, x0, bh, xatol, fatol, maxiter,
+                     maxfun, seed, result);
   return hipGetLastError();
 }
 

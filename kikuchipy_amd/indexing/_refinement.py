@@ -28,8 +28,15 @@ default) the L-BFGS-B polish that `DifferentialEvolutionSolver.solve` ends with 
 is the part still paid per evaluation (one objective launch and one synchronisation each); `polish=False` makes no
 objective call from the host.  KPDI_REFINE_DE=host, read at each call, sends the call to the host path below.
 
+`method="basinhopping"` around `minimizer_kwargs=dict(method="Nelder-Mead", ...)` with its plain keywords (`niter`, `T`,
+`stepsize`, `interval`, `niter_success`, `seed`, `target_accept_rate`, `stepwise_factor`) runs whole on the device
+(`kpdi_refine_solve_basinhopping`, `_device_basinhopping_options`): the hops, the adaptive step size, the Metropolis test
+and every Nelder-Mead quench of a (pattern, start) in one workgroup from its own `numpy.random.RandomState`, bit for bit
+what SciPy returns for the same seed, unbounded as in the reference, with no objective call from the host.
+KPDI_REFINE_BASINHOPPING=host, read at each call, sends the call to the host path below.
+
 Every other optimiser the reference can dispatch to (SciPy's other local methods, Powell with `direc`, `callback` or
-`return_all`, its other global methods, differential evolution with anything else) keeps ITS optimiser on the host, called with the reference's
+`return_all`, its other global methods, differential evolution or basinhopping with anything else) keeps ITS optimiser on the host, called with the reference's
 arguments, with the objective evaluated on the device (`_HostOptimizer`); `compute=False` returns a
 `DeferredRefinement` in place of the reference's lazy Dask array.
 """
@@ -200,7 +207,9 @@ class _HostOptimizer:
     """Every optimiser of the reference other than plain Nelder-Mead (SciPy local methods with their
     options, the SciPy global methods, NLopt's LN_NELDERMEAD; plain Powell only when `_device_powell_options`
     declines it or KPDI_REFINE_POWELL=host asks for this path, plain differential evolution only when
-    `_device_de_options` / `_de_members` decline it or KPDI_REFINE_DE=host asks for it): the OPTIMISER runs on the host exactly as
+    `_device_de_options` / `_de_members` decline it or KPDI_REFINE_DE=host asks for it, plain basinhopping around
+    Nelder-Mead only when `_device_basinhopping_options` declines it or KPDI_REFINE_BASINHOPPING=host asks for it): the
+    OPTIMISER runs on the host exactly as
     in the reference (indexing/_refinement/_solvers.py:79-250, :464-600: same call, same keyword
     arguments), the OBJECTIVE - master-pattern projection + NCC of one pattern - is one call into the
     device per evaluation (`kpdi_refine_objective`).  Slow next to the on-device simplex search (one
@@ -391,6 +400,56 @@ def _de_seeds(seed, n_jobs):
     if seed is None:
         return np.random.SeedSequence().generate_state(n_jobs).astype(np.uint32)
     return np.full(n_jobs, seed, dtype=np.uint32)
+
+
+def _device_basinhopping_options(host):
+    """dict(niter, T, stepsize, interval, niter_success, seed, target_accept_rate, stepwise_factor, xatol, fatol, maxiter,
+    maxfev) if `host` is `scipy.optimize.basinhopping` around `minimize(method="Nelder-Mead")` with nothing but the
+    keywords the device solver restates (csrc/basinhopping.h), else None.  `niter_success`, `seed`, `maxiter` and
+    `maxfev` may come back as None (SciPy's defaults: niter + 2, fresh entropy, the budget rule of Nelder-Mead).
+    `take_step`, `accept_test`, `callback`, `rng`, a generator instance as `seed`, `disp=True`, a missing `method` in
+    `minimizer_kwargs` (SciPy's BFGS) or any other minimiser, `bounds` or any other key of `minimizer_kwargs`, every
+    keyword this function does not know and every value SciPy would refuse keep the optimiser on the host (where SciPy
+    runs or raises as it does today)."""
+    if host is None or host.method != "basinhopping":
+        return None
+    kw = host.kwargs
+    if set(kw) - {"niter", "T", "stepsize", "interval", "niter_success", "seed", "target_accept_rate", "stepwise_factor",
+                  "disp", "minimizer_kwargs"}:
+        return None
+    if kw.get("disp"):
+        return None
+    quench = kw.get("minimizer_kwargs")
+    if not isinstance(quench, dict) or set(quench) - {"method", "tol", "options"}:
+        return None
+    if not isinstance(quench.get("method"), str) or quench["method"].lower() != "nelder-mead":
+        return None
+    options = quench.get("options")
+    if options is None:
+        options = {}
+    if not isinstance(options, dict) or set(options) - {"xatol", "fatol", "maxiter", "maxfev", "disp"} or options.get("disp"):
+        return None
+    out = {}
+    out["niter"] = _integer(kw.get("niter", 100), 0, 2**31)
+    out["T"], out["stepsize"] = _real(kw.get("T", 1.0)), _real(kw.get("stepsize", 0.5))
+    if out["stepsize"] is not None and not abs(out["stepsize"]) < 1e300:  # numpy refuses a range that overflows
+        return None
+    out["interval"] = _integer(kw.get("interval", 50), 1, 2**31)
+    for name in ("target_accept_rate", "stepwise_factor"):  # SciPy raises outside (0, 1)
+        out[name] = _real(kw.get(name, 0.5 if name == "target_accept_rate" else 0.9))
+        if out[name] is not None and not 0.0 < out[name] < 1.0:
+            return None
+    tol = quench.get("tol")
+    for name in ("xatol", "fatol"):  # scipy.optimize.minimize: options.setdefault(name, tol)
+        out[name] = _real(options.get(name, 1e-4 if tol is None else tol))
+    if any(value is None for value in out.values()):
+        return None
+    for name, source, low in (("niter_success", kw, 0), ("seed", kw, 0), ("maxiter", options, 1), ("maxfev", options, 1)):
+        value = source.get(name)
+        out[name] = None if value is None else _integer(value, low, 2**32 if name == "seed" else 2**31)
+        if value is not None and out[name] is None:
+            return None
+    return out
 
 
 def _job_objective(ctx, mode_code, i, fx):
@@ -721,6 +780,14 @@ def _run_refinement(mode, n, starts, x0, fixed, lower, upper, pats, signal_mask,
                                         de["atol"], de["mutation"], de["recombination"], de["init"], de["updating"],
                                         _de_seeds(de["seed"], block[2].shape[0] * block[2].shape[1]))
                 return _de_polish(c, MODES[mode], res, *block[1:]) if de["polish"] else res
+        bh = _device_basinhopping_options(host)
+        if bh is not None and os.environ.get("KPDI_REFINE_BASINHOPPING", "").lower() != "host":
+            # SciPy's basinhopping around Nelder-Mead on the device: one launch, no objective call from the host;
+            # unbounded, as the reference's basinhopping takes no trust region
+            return c.refine_solve_basinhopping(MODES[mode], block[0], block[1], bh["niter"], bh["T"], bh["stepsize"],
+                                               bh["interval"], bh["niter_success"], bh["target_accept_rate"],
+                                               bh["stepwise_factor"], bh["xatol"], bh["fatol"], bh["maxiter"],
+                                               bh["maxfev"], _de_seeds(bh["seed"], block[0].shape[0] * block[0].shape[1]))
         # the reference's optimiser on the host, the objective on the device
         return _host_solve(c, MODES[mode], host, *block)
 
