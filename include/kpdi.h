@@ -511,7 +511,20 @@ int kpdi_orientation_kam(kpdi_ctx *ctx, const double *q, int ny, int nx, const d
  *   (hough_vote.h).  Out: `quat` (m x 4, the convention of the refinement results), `fit` (mean angular deviation in
  *   degrees, 180 when not indexed), `cm` (matched bands / n_bands), `nmatch` (0 when not indexed).
  * kpdi_hough_plan_describe: {ok, lds, lds_bytes, pattern_bytes, pass_patterns, n_passes, tail_patterns} of the plan for
- *   `room_bytes` of workspace; host arithmetic.  kpdi_hough_default_n_rho: one pixel per rho cell. */
+ *   `room_bytes` of workspace; host arithmetic.  kpdi_hough_default_n_rho: one pixel per rho cell.
+ * kpdi_hough_optimize_pc: per pattern the projection centre that explains its bands best under one phase (DESIGN.md
+ *   section 28; csrc/hough_search.h): SciPy 1.15.3's Nelder-Mead (csrc/nelder_mead.h) from `pc0` (3 doubles, the same
+ *   start for every pattern) over the objective "mean `fit` of kpdi_hough_index with every valid band that found no
+ *   reflector charged `tol_deg`; 180 where PCz <= 0; `tol_deg` for a pattern without a valid band", one search per
+ *   pattern on one lane each, the whole search on the device.  `bands`, the detector, the phase tables and `tol` as for
+ *   kpdi_hough_index; `tol_deg` is `tol` in degrees as the caller rounds it.  `xatol`, `fatol`; `maxiter`, `maxfev`: <= 0
+ *   = unset, resolved as SciPy does (both unset: 600 each; one unset: that one unlimited); a budget that allows a search
+ *   more than 10000 evaluations (maxfev, or 4 + 5 maxiter where maxfev is unlimited) is refused with KPDI_EINVAL.  The kernel is launched until
+ *   every search has ended, each launch advancing every search by at most `evals_per_launch` evaluations (0: the
+ *   environment's KPDI_HOUGH_SEARCH_EVALS, else 6) - a bound on the duration of one kernel; `lanes` patterns share a
+ *   workgroup (0: from the plan, few while m is small so that the searches spread over the CUs, 64 at the most).  Neither
+ *   changes a bit of the result.  Out: `pc` (m x 3, the best vertex), `fun` (m), `nfev`, `nit` and `status` (m each;
+ *   SciPy's: 0 converged, 1 evaluations ran out, 2 iterations ran out). */
 int kpdi_hough_default_n_rho(int ny, int nx);
 int kpdi_hough_plan_describe(int ny, int nx, int n_theta, int n_rho, int64_t m, int64_t room_bytes, int64_t forced,
                              int64_t *desc);
@@ -520,6 +533,11 @@ int kpdi_hough_bands(kpdi_ctx *ctx, int n_theta, int n_rho, const float *cos_sin
 int kpdi_hough_index(kpdi_ctx *ctx, const void *bands, int64_t m, int n_bands, const double *pcs, int64_t n_pc, int ny, int nx,
                      const double *s2d, const double *normals, const int32_t *family, int n_reflectors, int n_families,
                      const double *angles, double tol, double *quat, double *fit, double *cm, int32_t *nmatch);
+int kpdi_hough_optimize_pc(kpdi_ctx *ctx, const void *bands, int64_t m, int n_bands, const double *pc0, int ny, int nx,
+                           const double *s2d, const double *normals, const int32_t *family, int n_reflectors, int n_families,
+                           const double *angles, double tol, double tol_deg, double xatol, double fatol, int maxiter, int maxfev,
+                           int evals_per_launch, int lanes, double *pc, double *fun, int32_t *nfev, int32_t *nit,
+                           int32_t *status);
 
 /* ---- geometrical simulations: Kikuchi lines and zone axes on the detector (KikuchiPatternSimulator.on_detector,
  * simulations/kikuchi_pattern_simulator.py:217-380; _kikuchi_pattern_features.py; _kikuchi_pattern_simulation.py:468-534) -----

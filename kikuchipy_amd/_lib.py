@@ -174,6 +174,8 @@ SIGNATURES = {
     "kpdi_hough_bands": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "kpdi_hough_index": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _vp, C.c_double, _vp, _vp, _vp,
                               _vp]),
+    "kpdi_hough_optimize_pc": (_i, [_vp, _vp, _i64, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, C.c_double, C.c_double,
+                                    C.c_double, C.c_double, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "kpdi_geometrical_visibility": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "kpdi_geometrical_coordinates": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, C.c_double,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -386,6 +388,8 @@ def reduce_plan_describe(dtype, op, axis_mask, ny, nx, sy, sx):
 HOUGH_BAND_DTYPE = np.dtype([("theta", "<f4"), ("rho", "<f4"), ("value", "<f4"), ("valid", "<i4"), ("a", "<i4"), ("k", "<i4"),
                              ("da", "<f4"), ("dk", "<f4")])
 HOUGH_MAX_BANDS, HOUGH_MAX_REFLECTORS, HOUGH_MAX_FAMILIES = 16, 96, 16
+HOUGH_SEARCH_MAX_EVALS = 10000  # csrc/hough_plan.h: a budget that allows one search more evaluations is refused by the kernel call
+HOUGH_SEARCH_EVALS = 6  # csrc/hough_plan.h: evaluations per lane and launch of the projection-centre search by default
 HOUGH_PLAN_FIELDS = ("ok", "lds", "lds_bytes", "pattern_bytes", "pass_patterns", "n_passes", "tail_patterns")
 
 
@@ -859,6 +863,33 @@ class Context:
                                   _ptr(g), _ptr(fam), g.shape[0], int(fam.max()) + 1, _ptr(ang), float(tol), _ptr(quat),
                                   _ptr(fit), _ptr(cm), _ptr(nmatch)))
         return quat, fit, cm, nmatch
+
+    def hough_optimize_pc(self, bands, pc0, shape, sample_to_detector, normals, family, angles, tol, xatol=1e-3, fatol=1e-3,
+                          maxiter=None, maxfev=None, evals_per_launch=0, lanes=0):
+        """One Nelder-Mead search over the projection centre per pattern, on the device (include/kpdi.h,
+        kpdi_hough_optimize_pc): `bands` (m, n_bands) of `HOUGH_BAND_DTYPE`, `pc0` (3,), the rest as `hough_index`.
+        `maxiter`, `maxfev`: None = unset, as in SciPy.  `evals_per_launch` (0: $KPDI_HOUGH_SEARCH_EVALS, else
+        `HOUGH_SEARCH_EVALS`) and `lanes` per workgroup (0: from the plan) bound a kernel's duration and lay the
+        searches on the chip; the result does not depend on them.  Returns (pc (m, 3), fun (m,), nfev, nit, status (m,) int32)."""
+        b = np.ascontiguousarray(bands, dtype=HOUGH_BAND_DTYPE)
+        m, nb = b.shape
+        start = np.ascontiguousarray(pc0, dtype=np.float64).reshape(3)
+        s2d = np.ascontiguousarray(sample_to_detector, dtype=np.float64).reshape(3, 3)
+        g = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+        fam = np.ascontiguousarray(family, dtype=np.int32).reshape(-1)
+        ang = np.ascontiguousarray(angles, dtype=np.float64)
+        if fam.size != g.shape[0] or ang.shape != (g.shape[0], g.shape[0]):
+            raise KpdiError(f"{g.shape[0]} reflectors with {fam.size} families and angles of shape {ang.shape}")
+        budget = [0 if v is None else int(min(v, 2**31 - 1)) for v in (maxiter, maxfev)]
+        if min(budget) < 0 or any(v is not None and v < 1 for v in (maxiter, maxfev)):
+            raise KpdiError(f"maxiter {maxiter} and maxfev {maxfev}: None or at least 1")
+        pc, fun = np.empty((m, 3)), np.empty(m)
+        nfev, nit, status = (np.empty(m, dtype=np.int32) for _ in range(3))
+        check(self._f.hough_optimize_pc(self._h, _ptr(b), m, nb, _ptr(start), int(shape[0]), int(shape[1]), _ptr(s2d), _ptr(g),
+                                        _ptr(fam), g.shape[0], int(fam.max()) + 1, _ptr(ang), float(tol), float(np.degrees(tol)),
+                                        float(xatol), float(fatol), budget[0], budget[1], int(evals_per_launch), int(lanes),
+                                        _ptr(pc), _ptr(fun), _ptr(nfev), _ptr(nit), _ptr(status)))
+        return pc, fun, nfev, nit, status
 
     @staticmethod
     def _geometrical_inputs(rotations, u_s, pcs, *bases):
@@ -1933,6 +1964,11 @@ class Group(Context):
     def basinhopping_selftest(self, *args, **kwargs):
         return self.root.basinhopping_selftest(*args, **kwargs)
 
+    # belongs to one GPU like the calls of `_ONE_GPU`, next to `hough_index` there: refused on a group
+    def hough_optimize_pc(self, *args, **kwargs):
+        raise KpdiError("hough_optimize_pc works on one GPU's own state or buffers and has no group form: use "
+                        "group.members[i].hough_optimize_pc(...)")
+
     # -- measurement
     def counters(self):
         """Member 0's counters (its merge / gather figures are the group's) + `members`: every member's."""
@@ -1964,5 +2000,5 @@ for _make, _names in ((_on_root, Group._ON_ROOT), (_one_gpu, Group._ONE_GPU)):
         _method = _make(_name)
         _method.__name__, _method.__doc__ = _name, getattr(Context, _name).__doc__
         setattr(Group, _name, _method)
-for _name in ("refine_solve_basinhopping", "basinhopping_selftest"):
+for _name in ("refine_solve_basinhopping", "basinhopping_selftest", "hough_optimize_pc"):
     getattr(Group, _name).__doc__ = getattr(Context, _name).__doc__

@@ -274,6 +274,8 @@ struct kpdi_ctx {
   // kpdi_hough_*: the sinogram workspace of one pass, the cos / sin tables or a phase's tables, the bands, the projection
   // centres and the results of the indexing kernel
   kpdi::DevBuf hough_ws, hough_tab, hough_bands, hough_pc, hough_out;
+  // kpdi_hough_optimize_pc: the searches (one HoughPcSearch per pattern) and their done flags
+  kpdi::DevBuf hough_search, hough_done;
 
   // dictionary chunk
   kpdi::DevBuf dict_raw, dict_y;
@@ -508,6 +510,8 @@ void dtype_range(int dtype, float *omin, float *omax);
 // BEFORE it looks at the float64 certification of the previous chunk
 int use_device(kpdi_ctx *c, bool keep_pending = false);
 int results_to_host(kpdi_ctx *c, void *dst, const void *d_src, size_t bytes);
+// SciPy's Nelder-Mead budget from maxiter / maxfev, <= 0 = unset (extras.hip): both unset 200 nvar each, one unset: that one unlimited
+void resolve_budget(int nvar, int maxiter, int maxfev, int *it, int *fev);
 void set_detector_layout(kpdi_ctx *c, int sy, int sx, bool have_mask, std::vector<int> keep);
 // the navigation mask (m_all bytes, or nullptr: none) of the resident patterns: which of them are matched
 int set_navigation_mask(kpdi_ctx *c, const uint8_t *nav_mask);

@@ -317,9 +317,8 @@ int kpdi_refine_objective(kpdi_ctx *c, int mode, int64_t n_eval, const int32_t *
 
 }  // extern "C"
 
-namespace {
-// SciPy's resolution of maxiter / maxfev (scipy/optimize/_optimize.py, _minimize_neldermead)
-void resolve_budget(int nvar, int maxiter, int maxfev, int *it, int *fev) {
+// SciPy's resolution of maxiter / maxfev (scipy/optimize/_optimize.py, _minimize_neldermead); declared in context.h
+void kpdi::resolve_budget(int nvar, int maxiter, int maxfev, int *it, int *fev) {
   const bool no_it = maxiter <= 0, no_fev = maxfev <= 0;
   if (no_it && no_fev) {
     *it = nvar * 200;
@@ -336,6 +335,7 @@ void resolve_budget(int nvar, int maxiter, int maxfev, int *it, int *fev) {
   }
 }
 
+namespace {
 int nelder_mead_check_bounds(const double *lower, const double *upper, size_t count) {
   for (size_t i = 0; i < count; ++i)
     if (lower[i] > upper[i])

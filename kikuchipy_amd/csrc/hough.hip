@@ -10,10 +10,13 @@
 //   bands: one workgroup per pattern: smoothing along rho, then along theta across the seam, the local maxima, and
 //          n_bands rounds of a workgroup arg-max under a total order (value, then cell index) - order-independent.
 //   index: one thread per pattern and phase (hough_vote.h), float64; the phase's tables staged in LDS.
+//   pc search: one lane per pattern runs that pattern's Nelder-Mead search over the projection centre around the same
+//          vote (hough_search.h), a bounded number of evaluations per launch; the searches rest in device memory.
 #include "../../include/kpdi.h"
 #include "kernels.h"
 #include "hough_plan.h"
 #include "hough_vote.h"
+#include "hough_search.h"
 
 namespace kpdi {
 
@@ -144,6 +147,42 @@ __global__ __launch_bounds__(64) void hough_index_kernel(IndexArgs a) {
   a.nmatch[i] = r.indexed ? r.nmatch : 0;
 }
 
+// One lane per pattern advances that pattern's search by at most `evals` evaluations; the searches live in `states`
+// between launches.  Every lane walks the same bounded loop (hv_pc_search_advance), one that is done idling
+// through it, so a wave diverges inside the vote and not around it.  done[i]: 1 once search i has ended.
+__global__ __launch_bounds__(HOUGH_SEARCH_MAX_LANES) void hough_pc_search_kernel(HoughPcSearchLaunch a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char index_lds[];
+  const int P = a.phase.n, lanes = (int)blockDim.x;
+  double *angles = reinterpret_cast<double *>(index_lds), *refl = angles + (size_t)P * P;
+  int32_t *family = reinterpret_cast<int32_t *>(refl + 3 * (size_t)P);
+  for (int o = threadIdx.x; o < P * P; o += lanes) angles[o] = a.phase.angles[o];
+  for (int o = threadIdx.x; o < 3 * P; o += lanes) refl[o] = a.phase.normals[o];
+  for (int o = threadIdx.x; o < P; o += lanes) family[o] = a.phase.family[o];
+  __syncthreads();
+  a.phase.angles = angles;
+  a.phase.normals = refl;
+  a.phase.family = family;
+  const int64_t i = (int64_t)blockIdx.x * lanes + threadIdx.x;
+  if (i >= a.m) return;
+  HoughPcSearch s = a.states[i];
+  const bool done = hv_pc_search_advance(s, a.bands + i * a.n_bands, a.n_bands, a.det, a.phase, a.options, a.evals);
+  a.states[i] = s;
+  a.done[i] = done ? 1 : 0;
+}
+
+// pc, fun, nfev, nit and status of the finished searches
+__global__ __launch_bounds__(64) void hough_pc_search_result_kernel(const HoughPcSearch *states, int64_t m, double *pc, double *fun,
+                                                                   int32_t *nfev, int32_t *nit, int32_t *status) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= m) return;
+  const HoughPcSearch &s = states[i];
+  for (int k = 0; k < 3; ++k) pc[3 * i + k] = s.nm.sim[0][k];
+  fun[i] = s.nm.fun();
+  nfev[i] = s.nm.fcalls;
+  nit[i] = s.nm.iterations;
+  status[i] = hv_pc_search_status(s);
+}
+
 template <typename T>
 hipError_t launch_radon_t(const HoughBandsLaunch &l, hipStream_t s) {
   const size_t floats = l.plan.pattern_bytes / sizeof(float);
@@ -194,6 +233,30 @@ hipError_t launch_hough_index(const HoughBand *bands, int64_t m, int n_bands, co
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(hough_index_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), lds, s, a);
+  return hipGetLastError();
+}
+
+// one launch of the projection-centre searches: every search that is not done advances by at most l.evals evaluations
+hipError_t launch_hough_pc_search(const HoughPcSearchLaunch &l, const HoughSearchPlan &plan, hipStream_t s) {
+  if (!l.bands || !l.states || !l.done || l.m < 1 || !plan.ok || plan.lanes < 1 || plan.lanes > HOUGH_SEARCH_MAX_LANES ||
+      plan.workgroups != (l.m + plan.lanes - 1) / plan.lanes || l.n_bands < 1 || l.n_bands > HV_MAX_BANDS || l.evals < 1 ||
+      l.phase.n < 1 || l.phase.n > HV_MAX_REFLECTORS || l.phase.n_families < 1 || l.phase.n_families > HV_MAX_FAMILIES ||
+      l.options.maxiter < 1 || l.options.maxfun < 1)
+    return hipErrorInvalidValue;
+  const size_t lds = index_lds_bytes(l.phase.n);
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void *)hough_pc_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(hough_pc_search_kernel, dim3((unsigned)plan.workgroups), dim3((unsigned)plan.lanes), lds, s, l);
+  return hipGetLastError();
+}
+
+hipError_t launch_hough_pc_search_results(const HoughPcSearch *states, int64_t m, double *pc, double *fun, int32_t *nfev,
+                                          int32_t *nit, int32_t *status, hipStream_t s) {
+  if (!states || !pc || !fun || !nfev || !nit || !status || m < 1 || (m + 63) / 64 > 2147483647LL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hough_pc_search_result_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s, states, m, pc, fun, nfev, nit,
+                     status);
   return hipGetLastError();
 }
 

@@ -11,6 +11,14 @@ int64_t forced_pass() {
   return e && atoll(e) > 0 ? atoll(e) : 0;
 }
 
+// evaluations per lane and launch of the projection-centre search: the caller's number, else KPDI_HOUGH_SEARCH_EVALS, else
+// HOUGH_SEARCH_EVALS (6).  A bound on how long one kernel runs, not a tuning knob.
+int search_evals(int asked) {
+  if (asked > 0) return asked;
+  const char *e = getenv("KPDI_HOUGH_SEARCH_EVALS");
+  return e && atoi(e) > 0 ? atoi(e) : HOUGH_SEARCH_EVALS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -132,6 +140,87 @@ int kpdi_hough_index(kpdi_ctx *c, const void *bands, int64_t m, int n_bands, con
   if (rc == KPDI_OK) rc = results_to_host(c, fit, o + 4 * m, (size_t)m * 8);
   if (rc == KPDI_OK) rc = results_to_host(c, cm, o + 5 * m, (size_t)m * 8);
   if (rc == KPDI_OK) rc = results_to_host(c, nmatch, o + 6 * m, (size_t)m * 4);
+  return rc;
+}
+
+int kpdi_hough_optimize_pc(kpdi_ctx *c, const void *bands, int64_t m, int n_bands, const double *pc0, int ny, int nx, const double *s2d,
+                           const double *normals, const int32_t *family, int n_reflectors, int n_families, const double *angles,
+                           double tol, double tol_deg, double xatol, double fatol, int maxiter, int maxfev, int evals_per_launch,
+                           int lanes, double *pc, double *fun, int32_t *nfev, int32_t *nit, int32_t *status) {
+  if (!c) return fail(KPDI_EINVAL, "ctx is NULL");
+  if (!bands || !pc0 || !s2d || !normals || !family || !angles || !pc || !fun || !nfev || !nit || !status)
+    return fail(KPDI_EINVAL, "an array is NULL");
+  if (m < 1 || m > 2147483647LL) return fail(KPDI_EINVAL, "%lld patterns: between 1 and 2^31 - 1", (long long)m);
+  if (n_bands < 1 || n_bands > HV_MAX_BANDS) return fail(KPDI_EINVAL, "%d bands: between 1 and %d", n_bands, HV_MAX_BANDS);
+  if (n_reflectors < 1 || n_reflectors > HV_MAX_REFLECTORS || n_families < 1 || n_families > HV_MAX_FAMILIES)
+    return fail(KPDI_EINVAL, "%d reflectors in %d families: at most %d in %d", n_reflectors, n_families, HV_MAX_REFLECTORS, HV_MAX_FAMILIES);
+  for (int p = 0; p < n_reflectors; ++p)
+    if (family[p] < 0 || family[p] >= n_families) return fail(KPDI_EINVAL, "reflector %d is of family %d of %d", p, family[p], n_families);
+  if (ny < 2 || nx < 2 || !(tol > 0) || !(tol_deg > 0))
+    return fail(KPDI_EINVAL, "a detector of %d x %d pixels, a tolerance of %g rad (%g degrees)", ny, nx, tol, tol_deg);
+  if (evals_per_launch < 0 || lanes < 0 || lanes > HOUGH_SEARCH_MAX_LANES)
+    return fail(KPDI_EINVAL, "%d evaluations per launch, %d lanes per workgroup: 0 (the default) or more, at most %d lanes",
+                evals_per_launch, lanes, HOUGH_SEARCH_MAX_LANES);
+  int rc = use_device(c);
+  if (rc) return rc;
+  HoughPcSearchLaunch l{};
+  resolve_budget(3, maxiter, maxfev, &l.options.maxiter, &l.options.maxfun);
+  std::copy(pc0, pc0 + 3, l.options.pc0);
+  l.options.xatol = xatol;
+  l.options.fatol = fatol;
+  l.options.tol_deg = tol_deg;
+  const HoughSearchPlan plan = hough_search_plan(m, c->n_cu, lanes);
+  if (!plan.ok) return fail(KPDI_EINVAL, "no launch plan for %lld searches", (long long)m);
+  const size_t P = (size_t)n_reflectors, bn = 3 * P * 8, ba = P * P * 8, bf = P * 4;
+  const size_t bb = (size_t)m * n_bands * sizeof(HoughBand), bo = (size_t)m * (4 * 8 + 3 * 4);
+  HIPCHK(c->hough_tab.reserve(bn + ba + bf));
+  HIPCHK(c->hough_bands.reserve(bb));
+  HIPCHK(c->hough_out.reserve(bo));
+  HIPCHK(c->hough_search.reserve((size_t)m * sizeof(HoughPcSearch)));
+  HIPCHK(c->hough_done.reserve((size_t)m));
+  char *tab = (char *)c->hough_tab.p;
+  HIPCHK(hipMemcpyAsync(tab, normals, bn, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(tab + bn, angles, ba, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(tab + bn + ba, family, bf, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->hough_bands.p, bands, bb, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(c->hough_search.p, 0, (size_t)m * sizeof(HoughPcSearch), c->stream));  // all zero: not begun
+  HIPCHK(hipStreamSynchronize(c->stream));  // (the uploads read the caller's arrays)
+  l.bands = c->hough_bands.as<HoughBand>();
+  l.m = m;
+  l.n_bands = n_bands;
+  l.det.ny = ny;
+  l.det.nx = nx;
+  std::copy(s2d, s2d + 9, l.det.s2d);
+  l.phase = HvPhase{n_reflectors, n_families, (const double *)tab, (const int32_t *)(tab + bn + ba), (const double *)(tab + bn), tol};
+  l.evals = search_evals(evals_per_launch);
+  l.states = c->hough_search.as<HoughPcSearch>();
+  l.done = c->hough_done.as<uint8_t>();
+  // every search ends within its budget of evaluations, and with an unlimited one (maxiter given, maxfev not) within
+  // maxiter iterations of at most 5 evaluations (reflection, contraction, three shrunk vertices) after the first 4
+  const int64_t most_evals = l.options.maxfun < INT_MAX ? (int64_t)l.options.maxfun : 4 + 5 * (int64_t)l.options.maxiter;
+  if (most_evals > HOUGH_SEARCH_MAX_EVALS)
+    return fail(KPDI_EINVAL, "a budget of up to %lld evaluations per search (maxiter %d, maxfev %d): at most %lld on the device",
+                (long long)most_evals, maxiter, maxfev, (long long)HOUGH_SEARCH_MAX_EVALS);
+  const int64_t most_launches = (most_evals + l.evals - 1) / l.evals + 1;
+  std::vector<uint8_t> done((size_t)m);
+  bool all = false;
+  for (int64_t launch = 0; launch < most_launches && !all; ++launch) {
+    hipError_t e = launch_hough_pc_search(l, plan, c->stream);
+    if (e != hipSuccess) return fail(KPDI_EHIP, "Hough projection-centre search kernel: %s (%lld patterns)", hipGetErrorString(e), (long long)m);
+    rc = results_to_host(c, done.data(), l.done, (size_t)m);
+    if (rc) return rc;
+    all = std::all_of(done.begin(), done.end(), [](uint8_t d) { return d != 0; });
+  }
+  if (!all) return fail(KPDI_EHIP, "Hough projection-centre search: not every search ended within its budget of %lld evaluations", (long long)most_evals);
+  double *o = c->hough_out.as<double>();
+  int32_t *oi = (int32_t *)(o + 4 * m);
+  hipError_t e = launch_hough_pc_search_results(l.states, m, o, o + 3 * m, oi, oi + m, oi + 2 * m, c->stream);
+  if (e != hipSuccess) return fail(KPDI_EHIP, "Hough projection-centre results kernel: %s", hipGetErrorString(e));
+  rc = results_to_host(c, pc, o, (size_t)m * 24);
+  if (rc == KPDI_OK) rc = results_to_host(c, fun, o + 3 * m, (size_t)m * 8);
+  if (rc == KPDI_OK) rc = results_to_host(c, nfev, oi, (size_t)m * 4);
+  if (rc == KPDI_OK) rc = results_to_host(c, nit, oi + m, (size_t)m * 4);
+  if (rc == KPDI_OK) rc = results_to_host(c, status, oi + 2 * m, (size_t)m * 4);
   return rc;
 }
 

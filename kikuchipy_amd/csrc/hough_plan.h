@@ -222,6 +222,41 @@ inline HoughPlan hough_plan(int ny, int nx, int n_theta, int n_rho, int64_t m, s
   return p;
 }
 
+// ---- the launch plan of the projection-centre search (hough.hip, hough_pc_search_kernel; hough_search.h) -------------------
+// One lane per pattern, and a lane's evaluation costs the same however many of its wave are idle: while there are fewer
+// patterns than a full wave per CU would take, a workgroup holds fewer lanes - the power of two that still covers
+// ceil(m / n_cu) - so that a small grid spreads over the CUs instead of filling one wave of one CU; 64 once m is large.
+// `forced` > 0: lanes per workgroup (tests).  The result of a search does not depend on the plan.
+constexpr int HOUGH_SEARCH_MAX_LANES = 64;
+// evaluations per lane and launch by default: a bound on a kernel's duration.  A launch of ONE evaluation per lane of a 10 x 10
+// grid of 60 x 60 patterns was measured at 81 ms (profiles/hough_pc_search.json): 6 stay under half a second, 16 did not
+constexpr int HOUGH_SEARCH_EVALS = 6;
+// the most evaluations one search may be allowed (its maxfev, or 4 + 5 maxiter where maxfev is unlimited): 16 times SciPy's
+// default budget of 600.  A larger budget is refused, so that no single call can hold a GPU for an unbounded time
+constexpr int64_t HOUGH_SEARCH_MAX_EVALS = 10000;
+
+struct HoughSearchPlan {
+  bool ok;
+  int lanes;           // per workgroup: 1, 2, 4, ... 64
+  int64_t workgroups;  // ceil(m / lanes)
+};
+
+HOUGH_HD HoughSearchPlan hough_search_plan(int64_t m, int n_cu, int forced = 0) {
+  HoughSearchPlan p{};
+  if (m < 1 || n_cu < 1 || forced < 0 || forced > HOUGH_SEARCH_MAX_LANES) return p;
+  int lanes = 1;
+  if (forced > 0) {
+    lanes = forced;
+  } else {
+    const int64_t per_cu = (m + n_cu - 1) / n_cu;
+    while (lanes < HOUGH_SEARCH_MAX_LANES && lanes < per_cu) lanes *= 2;
+  }
+  p.lanes = lanes;
+  p.workgroups = (m + lanes - 1) / lanes;
+  p.ok = p.workgroups <= 2147483647LL;
+  return p;
+}
+
 // what the launches take
 struct HoughBandsLaunch {
   const void *patterns;  // [n][ny][nx] of `dtype`, device

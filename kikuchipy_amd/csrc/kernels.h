@@ -18,6 +18,7 @@
 #include "orientations_plan.h"
 #include "hough_plan.h"
 #include "hough_vote.h"
+#include "hough_search.h"
 #include "prep_plan.h"
 
 namespace kpdi {
@@ -671,5 +672,9 @@ hipError_t launch_hough_bands(const HoughBandsLaunch &l, hipStream_t s);
 // one thread per pattern: `bands` [m][n_bands], `pcs` [n_pc][3] with n_pc = 1 or m, the phase's tables, all device
 hipError_t launch_hough_index(const HoughBand *bands, int64_t m, int n_bands, const double *pcs, int64_t n_pc, const HvDetector &det,
                               const HvPhase &phase, double *quat, double *fit, double *cm, int32_t *nmatch, hipStream_t s);
+// the projection-centre searches (hough_search.h): one bounded launch, and the results of the finished searches
+hipError_t launch_hough_pc_search(const HoughPcSearchLaunch &l, const HoughSearchPlan &plan, hipStream_t s);
+hipError_t launch_hough_pc_search_results(const HoughPcSearch *states, int64_t m, double *pc, double *fun, int32_t *nfev,
+                                          int32_t *nit, int32_t *status, hipStream_t s);
 
 }  // namespace kpdi

@@ -8,9 +8,15 @@ sample-to-detector orientation matrix that
 One PC, or one PC per map point (`pc` of shape navigation shape + (3,)):
 dictionary generation uses a single PC for the whole dictionary (SURVEY.md
 8(f1)), refinement takes either (8(f2)).  `get_indexer` returns the indexer of
-Hough indexing.  Plotting, calibration, PC
-fitting/extrapolation and file I/O are out of scope.
+Hough indexing.  Calibration from a grid of PCs -
+`estimate_xtilt`, `estimate_xtilt_ztilt`, `fit_pc`, `extrapolate_pc` - and the
+PC in the other vendors' conventions (`pc_emsoft`, `pc_bruker`, `pc_tsl`,
+`pc_oxford`) are host NumPy (kikuchipy_amd/_pc_fit.py).
+Plotting and file I/O are out of scope: `plot` and `figure_kwargs` are accepted
+and nothing is drawn.
 """
+
+import warnings
 
 from collections.abc import Iterable
 from numbers import Number
@@ -329,6 +335,175 @@ class EBSDDetector:
         from kikuchipy_amd.indexing._hough_indexing import indexer_from_detector
 
         return indexer_from_detector(self, phase_list, reflectors, **kwargs)
+
+    # ---- the PC in the vendors' conventions (detectors/_ebsd_detector.py:1660-1775, :2317-2336): the inverses of `_to_bruker`
+    def pc_emsoft(self, version=5):
+        """The PC(s) in EMsoft's convention (xpc, ypc, L): xpc = Nx b (1 / 2 - PCx), ypc = Ny b (1 / 2 - PCy),
+        L = Ny b px_size PCz; xpc changes sign before `version` 5."""
+        new_pc = np.zeros_like(self.pc, dtype=float)
+        new_pc[..., 0] = (0.5 - self.pcx) * self.ncols * self._binning
+        if version < 5:
+            new_pc[..., 0] = -new_pc[..., 0]
+        new_pc[..., 1] = (0.5 - self.pcy) * self.nrows * self._binning
+        new_pc[..., 2] = self.pcz * self.nrows * self._binning * self.px_size
+        return new_pc
+
+    def pc_bruker(self):
+        """The PC(s) in Bruker's convention, the one they are stored in."""
+        return self.pc
+
+    def pc_tsl(self):
+        """The PC(s) in EDAX TSL's convention: (PCx, 1 - PCy, PCz Ny / min(Ny, Nx))."""
+        new_pc = self.pc.copy()
+        new_pc[..., 1] = 1 - self.pcy
+        new_pc[..., 2] /= min([self.nrows, self.ncols]) / self.nrows
+        return new_pc
+
+    def pc_oxford(self):
+        """The PC(s) in Oxford Instruments' convention: (PCx, (1 - PCy) / aspect ratio, PCz / aspect ratio)."""
+        new_pc = self.pc.copy()
+        new_pc[..., 1] = (1 - self.pcy) / self.aspect_ratio
+        new_pc[..., 2] /= self.aspect_ratio
+        return new_pc
+
+    # ---- calibration from a grid of PCs (detectors/_ebsd_detector.py:1045-1596; _fit_projection_center.py)
+    def _warn_if_angles_ignored(self, msg):
+        if self.azimuthal != 0.0 or self.twist != 0.0:
+            warnings.warn(msg + f" azimuthal={self.azimuthal} and twist={self.twist} will be ignored.", UserWarning, stacklevel=3)
+
+    @staticmethod
+    def _no_figure(name):
+        raise NotImplementedError(f"`{name}(return_figure=True)` needs Matplotlib, which this package does not use: plot the "
+                                  "PCs of the returned detector")
+
+    def estimate_xtilt(self, detect_outliers=False, plot=True, degrees=False, return_figure=False, return_outliers=False,
+                       figure_kwargs=None):
+        """An estimate of the tilt about the detector X_d axis that brings the sample normal onto the detector normal:
+        pi / 2 + atan(slope) of the straight line PCy(PCz) through the PCs - ordinary least squares with an intercept,
+        or with `detect_outliers` (which `return_outliers` implies) a robust fit that also names the outliers, returned
+        as a mask of the navigation shape.  Radians unless `degrees`.
+
+        The reference's robust fit is scikit-learn's `RANSACRegressor` with its random trials.  scikit-learn is not
+        available to this package, so the robust fit is this package's own and deterministic: scikit-learn's rules and
+        defaults - a model through two PCs, the median absolute deviation of PCy as the residual threshold - over ALL
+        pairs of PCs in lexicographic order; most inliers win, then the higher R^2 on the inliers, then the first
+        pair; the line is fitted again to the inliers (kikuchipy_amd/_pc_fit.py).  Where the outliers stand clear of the
+        threshold the two name the same PCs; its numbers are NOT scikit-learn's otherwise.
+
+        `plot` and `figure_kwargs` are accepted and nothing is drawn; `return_figure` is refused."""
+        from kikuchipy_amd import _pc_fit
+
+        if self.navigation_size == 1:
+            raise ValueError("Estimation requires more than one projection center")
+        if return_figure:
+            self._no_figure("estimate_xtilt")
+        self._warn_if_angles_ignored("estimate_xtilt() assumes azimuthal and twist angles are zero, but")
+        if return_outliers:
+            detect_outliers = True
+        pcy, pcz = self.pcy.reshape(-1), self.pcz.reshape(-1)
+        if detect_outliers:
+            slope, _, is_inlier = _pc_fit.robust_linear_fit(pcz, pcy)
+            is_outlier = ~is_inlier
+        else:
+            slope, _ = _pc_fit.linear_fit(pcz, pcy)
+            is_outlier = None
+        x_tilt = float(np.pi / 2 + np.arctan(slope))
+        out = (float(np.rad2deg(x_tilt)),) if degrees else (x_tilt,)
+        if is_outlier is not None:
+            out += (is_outlier.reshape(self.navigation_shape),)
+        return out[0] if len(out) == 1 else out
+
+    def estimate_xtilt_ztilt(self, degrees=False, is_outlier=None):
+        """Estimates of the tilts about the detector X_d and Z_d axes that bring the sample normal onto the detector
+        normal, from a plane fitted to the PCs (those not `is_outlier`, a mask of the navigation shape) by a singular
+        value decomposition about their 10 % trimmed mean."""
+        from kikuchipy_amd import _pc_fit
+
+        if self.navigation_size == 1:
+            raise ValueError("Estimation requires more than one projection center")
+        self._warn_if_angles_ignored("estimate_xtilt_ztilt() assumes azimuthal and twist angles are zero, but")
+        pc = self.pc
+        if isinstance(is_outlier, np.ndarray):
+            pc = pc[~is_outlier]
+        pc = pc.reshape((-1, 3))
+        x_tilt, z_tilt, *_ = _pc_fit.fit_hyperplane(pc - pc.mean(axis=0))
+        if degrees:
+            x_tilt, z_tilt = np.rad2deg(x_tilt), np.rad2deg(z_tilt)
+        return x_tilt, z_tilt
+
+    def extrapolate_pc(self, pc_indices, navigation_shape, step_sizes, shape=None, px_size=None, binning=None, is_outlier=None):
+        """A new detector with a PC for every point of a map of `navigation_shape`, extrapolated from the average of
+        this detector's PCs (those not `is_outlier`), taken to belong to the rounded average of `pc_indices` - (row,
+        column) of each PC, shape (2,) + the number of PCs, possibly outside the map:
+        PCx = mean PCx + (mean column - column) dx / (px_size binning Nx),
+        PCy = mean PCy + (mean row - row) dy cos(alpha) / (px_size binning Ny),
+        PCz = mean PCz - (mean row - row) dy sin(alpha) / (px_size binning Ny), alpha = 90 - sample tilt + detector tilt
+        in degrees, (dy, dx) = `step_sizes`; `shape`, `px_size` and `binning` default to the detector's and are those of
+        the new detector.  (The average position is taken exactly as the reference takes it: the indices are
+        transposed to one row per PC and averaged along the second axis.)"""
+        dy, dx = step_sizes
+        pc_indices = np.atleast_2d(pc_indices).T
+        ny, nx = navigation_shape
+        if shape is None:
+            shape = self.shape
+        nrows, ncols = shape
+        if px_size is None:
+            px_size = self.px_size
+        if binning is None:
+            binning = float(self.binning)
+        pc = self.pc_flattened
+        if is_outlier is not None:
+            is_inlier = ~np.asarray(is_outlier)
+            pc = pc[is_inlier]
+            pc_indices = pc_indices[is_inlier]
+        pc_mean = pc.mean(axis=0)
+        pc_indices_mean = np.round(pc_indices.mean(axis=1)).astype(int)
+        self._warn_if_angles_ignored("extrapolate_pc() assumes azimuthal and twist angles are zero, but")
+        alpha = np.deg2rad(90 - self.sample_tilt + self.tilt)
+        y, x = np.indices((ny, nx), dtype=float)
+        factor = px_size * binning
+        d_pcx = -(pc_indices_mean[1] - x) * dx / (factor * ncols)
+        d_pcy = -(pc_indices_mean[0] - y) * dy * np.cos(alpha) / (factor * nrows)
+        d_pcz = +(pc_indices_mean[0] - y) * dy * np.sin(alpha) / (factor * nrows)
+        new_detector = self.deepcopy()
+        new_detector.shape = shape
+        new_detector.pc = np.stack((pc_mean[0] - d_pcx, pc_mean[1] - d_pcy, pc_mean[2] - d_pcz), axis=2)
+        new_detector.px_size = px_size
+        new_detector.binning = int(binning)
+        return new_detector
+
+    def fit_pc(self, pc_indices, map_indices, transformation="projective", is_outlier=None, plot=True, return_figure=False,
+               figure_kwargs=None):
+        """A new detector with a PC for every map point of `map_indices` - (2, m) or (2, n, m) rows and columns - from a
+        plane fitted to this detector's PCs at `pc_indices`, (2,) + the navigation shape, leaving out those `is_outlier`.
+        "affine": a least-squares affine map from (row, column, 1) to the PC.  "projective" (default): the PCs are turned
+        into their fitted plane (`estimate_xtilt_ztilt`'s), a homography from the indices to the in-plane coordinates is
+        estimated by the normalised direct linear transformation, and the projected indices are turned back.  The new
+        detector's `sample_tilt` is 90 - x tilt - detector tilt, the x tilt from the straight line through the fitted
+        (PCz, PCy).  `plot` and `figure_kwargs` are accepted and nothing is drawn; `return_figure` is refused."""
+        from kikuchipy_amd import _pc_fit
+
+        n_pc = self.navigation_size
+        if n_pc == 1:
+            raise ValueError("Fitting requires multiple projection centers (PCs)")
+        if return_figure:
+            self._no_figure("fit_pc")
+        pc_indices, map_indices = np.asarray(pc_indices), np.asarray(map_indices)
+        nav_shape = self.navigation_shape
+        if pc_indices.shape != (2,) + nav_shape:
+            raise ValueError(f"`pc_indices` array shape {pc_indices.shape} must be equal to {(2,) + nav_shape}")
+        if map_indices.ndim not in [2, 3] or map_indices.shape[0] != 2:
+            raise ValueError(f"`map_indices` array shape {map_indices.shape} must be (2, m columns) or (2, n rows, m columns)")
+        if is_outlier is not None and (not isinstance(is_outlier, np.ndarray) or not np.issubdtype(is_outlier.dtype, np.bool_)
+                                       or is_outlier.size != n_pc):
+            raise ValueError("`is_outlier` must be a boolean array of a size equal to the number of PCs")
+        _, pc_fit_map, _, x_tilt, _, _ = _pc_fit.fit_plane_to_pc(self.pc_flattened, pc_indices, map_indices, is_outlier,
+                                                                 transformation)
+        new_detector = self.deepcopy()
+        new_detector.pc = pc_fit_map
+        self._warn_if_angles_ignored("fit_pc() assumes azimuthal and twist angles are zero when estimating sample_tilt, but")
+        new_detector.sample_tilt = float(90 - np.rad2deg(x_tilt) - new_detector.tilt)
+        return new_detector
 
     def crop(self, extent):
         """A new detector cropped to `extent` = (top, bottom, left, right) in pixels, its PC values updated

@@ -1,6 +1,6 @@
 """Hough indexing on the GPU engine: `EBSDDetector.get_indexer`, `EBSD.hough_indexing`,
-`EBSD.hough_indexing_optimize_pc` and `xmap_from_hough_indexing_data` (csrc/hough.hip,
-csrc/hough_plan.h, csrc/hough_vote.h).
+`EBSD.hough_indexing_optimize_pc` and `xmap_from_hough_indexing_data` (DESIGN.md sections 26 and 28; csrc/hough.hip,
+csrc/hough_plan.h, csrc/hough_vote.h, csrc/hough_search.h).
 
 The reference hands these calls to PyEBSDIndex (indexing/_hough_indexing.py, signals/ebsd.py:1600-1825 of the reference),
 which is not available to this project: the interface - the names, the attributes the reference reads from an indexer,
@@ -344,13 +344,72 @@ def hough_indexing(signal, phase_list, indexer, chunksize=528, verbose=1, return
     return out[0] if len(out) == 1 else out
 
 
-def hough_indexing_optimize_pc(signal, pc0, indexer, batch=False, method="Nelder-Mead", **kwargs):
-    """`EBSD.hough_indexing_optimize_pc` (signals/ebsd.py:1721-1825 of the reference): the bands are detected once, a host
-    Nelder-Mead search (`scipy.optimize.minimize`, which takes `**kwargs`) over the PC runs only the indexing kernel, on
-    the first phase, and minimises the mean `fit` - every unmatched band counted at the tolerance of the vote - of all
-    patterns, or with `batch` of each pattern on its own."""
+def _device_search_options(kwargs):
+    """The keywords of `hough_indexing_optimize_pc(batch=True)` as the search kernel takes them - dict(xatol, fatol,
+    maxiter, maxfev) -, or None where SciPy has to run the search on the host: anything but `tol` and `options` within
+    xatol, fatol, maxiter, maxfev and a false disp (`bounds`, `callback`, `adaptive`, `initial_simplex`, `return_all`, a true
+    `disp`, a budget of more than `_lib.HOUGH_SEARCH_MAX_EVALS` evaluations per search, ...), and every call under
+    KPDI_HOUGH_PC_SEARCH=host.  The parsing is that of `_nelder_mead_options` of the refinement."""
+    import os
+
+    if os.environ.get("KPDI_HOUGH_PC_SEARCH", "").lower() == "host":
+        return None
+    kwargs = dict(kwargs)
+    options = dict(kwargs.pop("options", None) or {})
+    tol = kwargs.pop("tol", None)
+    if kwargs or set(options) - {"xatol", "fatol", "maxiter", "maxfev", "disp"}:
+        return None
+    # (`tol`: scipy.optimize.minimize lets it set xatol and fatol only where the options name none, and the host path
+    # below names both, 1e-3 by default, before SciPy looks: it changes nothing there, so nothing here)
+    del tol
+    if options.get("disp"):
+        return None  # SciPy prints its termination message and warns when the budget runs out: the kernel is silent
+    budget = [options.get("maxiter"), options.get("maxfev")]
+    if any(v is not None and (not isinstance(v, (int, np.integer)) or v < 1) for v in budget):
+        return None  # (SciPy takes infinities and floats too: its business)
+    # the kernel refuses a budget that lets one search run on without a sane end (csrc/hough_plan.h); on the host every
+    # step is a launch of its own
+    most = budget[1] if budget[1] is not None else (600 if budget[0] is None else 4 + 5 * int(budget[0]))
+    if most > _lib.HOUGH_SEARCH_MAX_EVALS:
+        return None
+    return dict(xatol=float(options.get("xatol", 1e-3)), fatol=float(options.get("fatol", 1e-3)), maxiter=budget[0], maxfev=budget[1])
+
+
+def _host_search(ctx, bands, pc0, args, **kwargs):
+    """SciPy's Nelder-Mead on the host over the mean objective of `bands` (k, n_bands), each step one launch of the
+    indexing kernel; `args`: what `Context.hough_index` takes after the PC, the tolerance last.  Returns SciPy's
+    `OptimizeResult`.  xatol = fatol = 1e-3 unless the options name them."""
     from scipy.optimize import minimize
 
+    kwargs = dict(kwargs)
+    options = dict(kwargs.pop("options", None) or {})
+    options.setdefault("xatol", 1e-3)
+    options.setdefault("fatol", 1e-3)
+    tol_deg = float(np.degrees(args[-1]))
+    n_valid = (bands["valid"] != 0).sum(axis=1)
+
+    def objective(pc):
+        # the mean fit, with every band that found no reflector charged the tolerance: a PC under which bands stop
+        # matching must not look better for it (where all bands match this IS the mean fit)
+        if not pc[2] > 0:
+            return 180.0
+        _, fit, _, nmatch = ctx.hough_index(bands, pc, *args)
+        charged = np.where(nmatch > 0, fit * nmatch, 0.0) + tol_deg * (n_valid - nmatch)
+        return float(np.mean(np.where(n_valid > 0, charged / np.maximum(n_valid, 1), tol_deg)))
+
+    return minimize(objective, pc0, method="Nelder-Mead", options=options, **kwargs)
+
+
+def hough_indexing_optimize_pc(signal, pc0, indexer, batch=False, method="Nelder-Mead", **kwargs):
+    """`EBSD.hough_indexing_optimize_pc` (signals/ebsd.py:1721-1825 of the reference): the bands are detected once, a
+    Nelder-Mead search over the PC runs only the indexing, on the first phase, and minimises the mean `fit` - every
+    unmatched band counted at the tolerance of the vote - of all patterns, or with `batch` of each pattern on its own.
+
+    With `batch` and plain keywords (`_device_search_options`) every pattern's search runs on the device, one lane per
+    pattern, SciPy's Nelder-Mead restated bit for bit (`Context.hough_optimize_pc`).  Otherwise
+    the search is `scipy.optimize.minimize` on the host, which takes `**kwargs`, and each step one launch of the
+    indexing kernel: `batch=False` (one search over the mean of all patterns), keywords the kernel does not know, and
+    every call under KPDI_HOUGH_PC_SEARCH=host.  Both paths return the same bits."""
     from kikuchipy_amd.detectors import EBSDDetector
 
     pc0 = np.asarray(pc0)
@@ -370,29 +429,13 @@ def hough_indexing_optimize_pc(signal, pc0, indexer, batch=False, method="Nelder
     phase = indexer.phaselist[0]
     tol = indexer.tolerance(pc0)
     args = (indexer.bandDetectPlan.patDim, indexer.sample_to_detector, phase.normals, phase.family, phase.angles, tol)
-    options = dict(kwargs.pop("options", None) or {})
-    options.setdefault("xatol", 1e-3)
-    options.setdefault("fatol", 1e-3)
-    kwargs.setdefault("options", options)
-
-    tol_deg = float(np.degrees(tol))
-
-    def solve(bands):
-        n_valid = (bands["valid"] != 0).sum(axis=1)
-
-        def objective(pc):
-            # the mean fit, with every band that found no reflector charged the tolerance: a PC under which bands stop
-            # matching must not look better for it (where all bands match this IS the mean fit)
-            if not pc[2] > 0:
-                return 180.0
-            _, fit, _, nmatch = ctx.hough_index(bands, pc, *args)
-            charged = np.where(nmatch > 0, fit * nmatch, 0.0) + tol_deg * (n_valid - nmatch)
-            return float(np.mean(np.where(n_valid > 0, charged / np.maximum(n_valid, 1), tol_deg)))
-
-        return minimize(objective, pc0, method="Nelder-Mead", **kwargs).x
-
+    device = _device_search_options(kwargs) if batch else None
+    if device is not None:
+        pc = ctx.hough_optimize_pc(band_data, pc0, *args, **device)[0].reshape(nav + (3,))
+        return EBSDDetector(shape=sig, pc=pc, sample_tilt=indexer.sampleTilt, tilt=indexer.camElev)
     if batch:
-        pc = np.stack([solve(band_data[i:i + 1]) for i in range(band_data.shape[0])]).reshape(nav + (3,))
+        pc = np.stack([_host_search(ctx, band_data[i:i + 1], pc0, args, **kwargs).x for i in range(band_data.shape[0])])
+        pc = pc.reshape(nav + (3,))
     else:
-        pc = solve(band_data)
+        pc = _host_search(ctx, band_data, pc0, args, **kwargs).x
     return EBSDDetector(shape=sig, pc=pc, sample_tilt=indexer.sampleTilt, tilt=indexer.camElev)

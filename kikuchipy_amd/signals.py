@@ -1066,8 +1066,10 @@ class EBSD:
 
     def hough_indexing_optimize_pc(self, pc0, indexer, batch=False, method="Nelder-Mead", **kwargs):
         """signals/ebsd.py:1721-1825: a detector with the PC (`batch=True`: one per pattern, in the navigation shape)
-        that minimises the mean `fit` of Hough indexing, found by a host Nelder-Mead search from `pc0` that detects the
-        bands once and runs only the indexing kernel per step.  `method="PSO"` is not implemented."""
+        that minimises the mean `fit` of Hough indexing, found by a Nelder-Mead search from `pc0` that detects the bands
+        once and runs only the indexing per step: with `batch` and plain `options` (xatol, fatol, maxiter, maxfev) all
+        searches on the device, one lane per pattern, else SciPy's on the host with one kernel
+        launch per step - the same bits either way.  `method="PSO"` is not implemented."""
         from kikuchipy_amd.indexing import _hough_indexing
 
         return _hough_indexing.hough_indexing_optimize_pc(self, pc0, indexer, batch, method, **kwargs)
